@@ -18,6 +18,10 @@ configs[4] shapes (short runs; `--no-secondary` skips them).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launches one rank per GPU itself through torch.distributed.run,
                                                           or is started by it -- WORLD_SIZE set -- as the driver does)
+
+`--dump-outputs DIR` writes, after the K timed steps and before anything else runs, what the last timed step handed its
+caller (rank 0's shard) as DIR/<name>.npy in float32 / float64: see dump_outputs().  Inputs are seeded by the configs, so two
+builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -146,6 +150,34 @@ def pmc_update_traffic(updates_per_step, ms_per_step):
                 "algorithmic_bytes_per_update": round(ALGORITHMIC_BYTES_PER_ENV_STEP * 524288 / 160),
                 "counter_to_algorithmic_ratio": round(per_update / (ALGORITHMIC_BYTES_PER_ENV_STEP * 524288 / 160), 1)}
     return None
+
+
+DUMP_SAMPLE_ENVS = 512         # env columns of the (T, N, width) rollout arrays --dump-outputs keeps (fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, batch, state, metrics):
+    """What one train_iteration returns or leaves for its caller: the next observation, the per-update metric rows, the 12
+    logged host scalars, both networks' parameters, the PRNG key, and the rollout batch it trained on -- the (T, N) arrays
+    whole, the (T, N, width) ones at DUMP_SAMPLE_ENVS env columns drawn once from a fixed seed."""
+    import numpy as np
+    host = lambda t: t.detach().float().cpu().numpy()
+    n = batch.rewards.shape[1]
+    cols = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE_ENVS), replace=False))
+    arrays = {"next_obs": host(state), "update_metrics": host(metrics),
+              "host_metrics": np.asarray(model.last_host_metrics, np.float64),
+              "policy_params": host(model.pparams), "critic_params": host(model.cparams),
+              "prng_key": np.asarray(model.key, np.float64), "sample_env_index": cols.astype(np.float64)}
+    for name in ("rewards", "terminations", "values", "next_values", "log_probs", "advantages", "returns"):
+        arrays["batch_" + name] = host(getattr(batch, name))
+    for name in ("states", "next_states", "actions"):
+        arrays["batch_%s_sample" % name] = host(getattr(batch, name))[:, cols]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _plugin(alg, env_overrides, alg_overrides):
@@ -334,7 +366,11 @@ def main():
     ap.add_argument("--no-prof", action="store_true", help="diagnostic: no per-kernel HIP events in the timed region")
     ap.add_argument("--lib-option", action="append", default=[], metavar="NAME=VALUE",
                     help="diagnostic: rlx_dbg_set_option before the run (e.g. two_streams=0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started as `python bench.py --gpus N` (the way the driver starts N = 1): become the launcher -- one rank per GPU under
@@ -418,6 +454,8 @@ def main():
     ar0 = model.ctx.get_counter("allreduce_calls")
     elapsed = timed(args.steps, 0, not args.no_prof)
     collectives_per_step = (model.ctx.get_counter("allreduce_calls") - ar0) / max(args.steps, 1)
+    if args.dump_outputs and rank == 0:               # before the untimed iterations below move the state on
+        dump_outputs(args.dump_outputs, model, batch, state, metrics)
     if args.no_prof:
         print(json.dumps({"value": args.steps * NR_STEPS * config.environment.nr_envs / elapsed,
                           "ms_per_step": 1e3 * elapsed / args.steps}))

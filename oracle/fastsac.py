@@ -109,8 +109,11 @@ def sample(mean, log_std, eps, action_scale):
     t = torch.tanh(raw)
     logp = -((raw - mean) ** 2) / (2.0 * std * std) - log_std - math.log(math.sqrt(2.0 * math.pi))
     # (policy.py:36-43 builds action_scale from float32 tensors and it is no module buffer: it STAYS float32 whatever the module's
-    #  dtype, so this one term is float32 arithmetic in the reference)
-    log_scale = torch.log(action_scale.to(torch.float32) + 1e-6).to(mean.dtype)
+    #  dtype, so this one term is float32 arithmetic in the reference).  The float32 log is taken as the correctly rounded one:
+    #  torch's own float32 log comes from a vector-math library whose last bit depends on the CPU it runs on, and one ulp
+    #  here moves a Q value by ~5e-9 (tests/test_oracle_fastsac.py asserts 1e-10 relative)
+    x32 = action_scale.to(torch.float32) + 1e-6
+    log_scale = torch.log(x32.to(torch.float64)).to(torch.float32).to(mean.dtype)
     logp = logp - torch.log((1.0 - t * t) + 1e-6) - log_scale
     return t * action_scale, logp.sum(dim=1)
 
