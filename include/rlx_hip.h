@@ -653,6 +653,58 @@ int rlx_fastsac_policy_update_f32(rlx_ctx*, const rlx_lnmlp_desc* pdesc, float* 
                                   const float* critic_states, const float* action_scale, int64_t B, uint32_t key_io[2], int scheme,
                                   int64_t* opt_count_io, const rlx_fastsac_hparams* hp, float* metrics_out, void* stream);
 
+/* ---- FastTD3: networks and update steps (rl_x/algorithms/fasttd3/pytorch) ------------------------------------------------
+ * Networks: rlx_mlp_desc with act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0 -- Dense -> ReLU per hidden layer, then a Dense
+ * head (policy.py:38-47: 512-256-128, head act_dim wide, tanh applied by the entry points below; q_network.py:28-36: input
+ * [critic obs | action], 1024-512-256, head nr_atoms wide).  FLAT LAYOUT: per hidden layer W[in, out] row-major, b[out]; then
+ * head W[in, out_dim], b[out_dim] (rlx_mlp_param_count).  FastTD3's own check: 1..3 hidden layers, widths multiples of 64 up to
+ * 1024, act_dim <= 64.  Sampling: rlx_fastsac_replay_sample_f32 (the same ring, fasttd3/pytorch/replay_buffer.py); normaliser:
+ * rlx_obs_norm_* (observation_normalizer.py).  Noise: threefry, key, subkey = split(key) per call; rlx_dbg_set_sac_noise(eps_next,
+ * .) injects the N(0, 1) draws of the exploration noise (act, [N, A]) and of the smoothing noise (critic update, [B, A]).        */
+typedef struct rlx_fasttd3_hparams { /* fasttd3/pytorch/default_config.py:12-38 */
+  float gamma, tau, v_min, v_max;
+  float lr_policy, lr_critic, weight_decay, adam_b1, adam_b2, adam_eps; /* torch.optim.AdamW, default betas (fasttd3.py:88-89) */
+  float max_grad_norm;        /* -1: none; else torch.nn.utils.clip_grad_norm_ before each AdamW step (fasttd3.py:125-126, :214-215);
+                               * the reported gradient norm is the un-clipped one                                                */
+  float smoothing_epsilon;    /* target-policy smoothing: noise = clamp(randn * smoothing_epsilon, +-smoothing_clip_value) */
+  float smoothing_clip_value; /* (fasttd3.py:143-144)                                                                     */
+  int32_t nr_atoms;           /* 2..128 */
+  int32_t clipped_double_q;   /* clipped_double_q_learning */
+} rlx_fasttd3_hparams;
+
+/* noise_scales[N] = U[0, 1) (noise_std_max - noise_std_min) + noise_std_min (fasttd3.py:241 at reset; :274-278 after a step:
+ * only where dones[i] > 0).  dones: NULL (every env) or DEVICE float[N].  key, subkey = split(key); u_i = bits(subkey, i of N).  */
+int rlx_fasttd3_noise_scales_f32(rlx_ctx*, uint32_t key_io[2], int scheme, float* noise_scales, const float* dones, int N,
+                                 float noise_std_min, float noise_std_max, void* stream);
+/* Policy.get_action (policy.py:57-66): action[N, A] = tanh(policy(obs)) + eps * noise_scales[n] (what the ring stores, unclipped);
+ * processed_action = clip_and_rescale ? low + 0.5 (clamp(action, -1, 1) + 1)(high - low) : action (what the env gets; low / high:
+ * DEVICE float[A]).  deterministic: no noise, key untouched (evaluation, test()).  obs: normalised, column-selected policy
+ * observations [N, pdesc->in_dim].  eps[n, j] = normal(bits(subkey, (n + row_offset) * A + j of N_global * A)).                 */
+int rlx_fasttd3_act_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const float* obs, const float* noise_scales,
+                        uint32_t key_io[2], int scheme, float* action, float* processed_action, int N, int deterministic,
+                        int clip_and_rescale, const float* low, const float* high, int row_offset, int N_global, void* stream);
+/* ONE critic_loss_fn call plus the Polyak update that follows it (fasttd3.py:140-225, :316-320): next action = clamp(tanh(policy(s'))
+ * + clamp(eps * smoothing_epsilon, +-smoothing_clip_value), -1, 1) (no gradient, no target policy), target critics on (s', a'),
+ * categorical projection of the n-step target without an entropy term (rlx_c51_critic_loss_f32 with alpha = 0), both online
+ * critics' backward, ONE AdamW step over the 2 * nq critic parameters, target <- (1 - tau) target + tau params.
+ * qparams / qm / qv / qtarget: the two critics back to back.  states / next_states: policy columns [B, pdesc->in_dim];
+ * critic_states / critic_next_states: NULL, or the critics' own columns [B, qdesc->in_dim - act_dim].  opt_count_io (HOST): critic
+ * optimizer steps so far, advanced by 1.  metrics_out: DEVICE float[4] = {q_loss, q_min, q_max (of q1's projected expectation,
+ * fasttd3.py:208-209), critic_grad_norm}.                                                                                      */
+int rlx_fasttd3_critic_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const rlx_mlp_desc* qdesc, float* qparams,
+                                  float* qm, float* qv, float* qtarget, const float* states, const float* next_states,
+                                  const float* critic_states, const float* critic_next_states, const float* actions,
+                                  const float* rewards, const float* dones, const float* truncations, const float* effective_n_steps,
+                                  int64_t B, uint32_t key_io[2], int scheme, int64_t* opt_count_io, const rlx_fasttd3_hparams* hp,
+                                  float* metrics_out, void* stream);
+/* ONE policy_loss_fn call (fasttd3.py:105-136): loss = -mean(q), q = min(q1, q2) (torch.minimum: a tie splits the gradient 1/2 each)
+ * or (q1 + q2) / 2 of the critics' EXPECTED values sum_j softmax(logits)_j z_j on (s, tanh(policy(s))); gradient through both
+ * critics to the action, through the tanh to the policy; AdamW step of the policy.  metrics_out: DEVICE float[2] =
+ * {policy_loss, policy_grad_norm}.                                                                                             */
+int rlx_fasttd3_policy_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* qdesc,
+                                  const float* qparams, const float* states, const float* critic_states, int64_t B,
+                                  int64_t* opt_count_io, const rlx_fasttd3_hparams* hp, float* metrics_out, void* stream);
+
 /* =================================== PPO + LSTM =======================================
  * Recurrent policy (rl_x/algorithms/ppo_lstm/flax_full_jit/policy.py:32-142, "concat" and "film" decoders):
  *   lstm_obs_encode / obs_encode: Dense(E)+LN+ELU on obs; OptimizedLSTMCell(H); LN+ELU on h;

@@ -14,6 +14,7 @@
 #include "gemm_bx.h"
 #include "ln_kernels.h"
 #include "mlp.h"
+#include "fs_sched.h"
 
 extern "C" int rlx_c51_critic_loss_f32(rlx_ctx* ctx, const float* q1_logits, const float* q2_logits, const float* q1_next_logits,
                                        const float* q2_next_logits, const float* rewards, const float* dones,
@@ -92,7 +93,8 @@ static inline int ln_bwd_rows_grid(const rlx_ctx* ctx, int64_t M) {   // 16 rows
 
 int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
 int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st);
-int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st);
+int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
+                bool relu_mask = false);
 
 // Split-operand weight images for the trunk GEMMs of a pass with >= 4096 rows (gemm_bx.h): launch_gemm_fwd / stage_dx pick them up
 // by weight pointer.  nets[i]: parameter vector, layout, whether the pass needs the transposed images (input gradients).
@@ -115,42 +117,6 @@ static int fs_images(rlx_ctx* ctx, const FsNet* nets, int n, int64_t M, hipStrea
   ctx->bx_n[1] = ctx->bx_n[0];
   return RLX_OK;
 }
-
-// Fork / join of the update's two independent halves (critic 1 || critic 2; target passes || online passes): the side half runs
-// on ctx->side under scratch bank 1.  With option two_streams = 0 both halves stay on the caller's stream.
-struct FsFork {
-  rlx_ctx* c;
-  hipStream_t main_st, side_st;
-  bool on;
-  int next_ev = 0;
-  FsFork(rlx_ctx* ctx, hipStream_t st) : c(ctx), main_st(st), side_st(st), on(false) {}
-  int begin() {
-    if (!c->two_streams) return RLX_OK;
-    const int rc = ctx_sac_streams(c);
-    if (rc) return rc;
-    side_st = c->side;
-    on = side_st != main_st;
-    return RLX_OK;
-  }
-  int fork() {   // the side stream sees everything issued on the main stream so far
-    if (!on) return RLX_OK;
-    hipEvent_t e = c->sac_ev[next_ev++ % 6];
-    RLX_HIP_TRY(hipEventRecord(e, main_st));
-    RLX_HIP_TRY(hipStreamWaitEvent(side_st, e, 0));
-    return RLX_OK;
-  }
-  int join() {   // the main stream waits for the side stream
-    c->bank = 0;
-    if (!on) return RLX_OK;
-    hipEvent_t e = c->sac_ev[next_ev++ % 6];
-    RLX_HIP_TRY(hipEventRecord(e, side_st));
-    RLX_HIP_TRY(hipStreamWaitEvent(main_st, e, 0));
-    return RLX_OK;
-  }
-  hipStream_t side() { c->bank = on ? 1 : 0; return side_st; }   // (sets the scratch bank the following launches use)
-  hipStream_t main() { c->bank = 0; return main_st; }
-  ~FsFork() { c->bank = 0; }
-};
 
 // forward through all hidden layers and the head; x: [M, in] with row stride ldx (a multiple of four, zero padded)
 static int ln_fwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* x, int ldx, const LnBufs& b, float* head_out, int64_t M,
@@ -181,24 +147,6 @@ static size_t ln_bwd_stage_floats(const rlx_ctx* ctx, const LnLayout& L, int64_t
   }
   return n;
 }
-// One reduction launch for ALL the parameter-gradient partials of an update's backward passes (head slabs, LayerNorm scale /
-// bias partials, weight-gradient slabs of every layer of every network): 14 launches of ~12 us per network otherwise.
-struct FsDefer {
-  rlx_ctx* c;
-  ReduceDefer d;
-  explicit FsDefer(rlx_ctx* ctx) : c(ctx) {}
-  int begin(size_t floats) {
-    d.base = (float*)scratch(c, SL_STAGE, floats * sizeof(float));
-    if (!d.base) return RLX_ENOMEM;
-    d.cap = floats;
-    d.off = 0;
-    d.tab.n = 0;
-    c->defer = &d;
-    return RLX_OK;
-  }
-  ~FsDefer() { if (c->defer == &d) c->defer = nullptr; }
-};
-
 // backward from d_head [M, head_out].  grads != NULL: parameter gradients (flat layout); dx != NULL: input gradient [M, in] (row
 // stride lddx).  The activation buffers are consumed (dH_l / dZ_l overwrite H_l).
 // dx_nc > 0: only the input columns [dx_c0, dx_c0 + dx_nc) (the policy loss wants dQ/da, 12 of 60 columns: the column-restricted
@@ -279,7 +227,9 @@ __global__ __launch_bounds__(128) void k_fs_head_fwd(const float* __restrict__ H
       if (r0 + r < M) out[(r0 + r) * N + n] = acc[r] + bv;
   }
 }
-// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k
+// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k.  RELU_MASK (FastTD3): H_dH
+// holds the ReLU output H on entry and dH * (H > 0) on exit (each entry is read by the thread that overwrites it).
+template <bool RELU_MASK>
 __global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d, const float* __restrict__ W, float* __restrict__ dH,
                                                     int64_t M, int K, int N) {
   extern __shared__ float s_d[];   // [8][N]
@@ -301,7 +251,10 @@ __global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d,
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r)
-      if (r0 + r < M) dH[(r0 + r) * K + k] = acc[r];
+      if (r0 + r < M) {
+        if (RELU_MASK) acc[r] = dH[(r0 + r) * K + k] > 0.f ? acc[r] : 0.f;
+        dH[(r0 + r) * K + k] = acc[r];
+      }
   }
 }
 // partial[s][K * N + N]: dW = H^T d and db = column sums of d over the rows [s * rows, (s + 1) * rows) -- summed in row order;
@@ -574,7 +527,8 @@ int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int6
   return RLX_OK;
 }
 
-int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st) {
+int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
+                bool relu_mask) {
   if (gW) {
     const int boff = (K * N + 3) & ~3;
     const int64_t PS = boff + ((N + 3) & ~3);
@@ -605,7 +559,8 @@ int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float
     const int rc = stage_reduce(ctx, tab, nullptr, nullptr, st);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_fs_head_dx, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
+  if (relu_mask) hipLaunchKernelGGL(k_fs_head_dx<true>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
+  else hipLaunchKernelGGL(k_fs_head_dx<false>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }

@@ -1,0 +1,544 @@
+// fasttd3.hip -- FastTD3 update steps (rl_x/algorithms/fasttd3/pytorch/fasttd3.py:105-225, :316-324): distributional (C51) twin
+// critics with clipped double Q, a deterministic tanh policy with per-env Gaussian exploration noise, target-policy smoothing,
+// AdamW, Polyak targets.  No entropy term and no target policy.
+//
+// Networks (policy.py:38-47, q_network.py:28-36): plain Dense -> ReLU trunks and a Dense head -- rlx_mlp_desc with act = RELU,
+// ln_first = 0, has_logstd = 0 (flat layout: per layer W[in, out] row-major, b[out]; then the head), hidden widths multiples of
+// 64 up to 1024 (td3_check: the PPO / SAC check mlp_check_desc stays as it is).  The trunks are the library's GEMM stages with
+// the fused bias + ReLU epilogue (launch_gemm_fwd) and the ReLU' input-gradient epilogue (stage_dx), the split-operand engine
+// for passes of >= 4096 rows (td3_images), stage_dw for the weight gradients; the heads are fastsac.hip's k_fs_head_* kernels
+// (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head kernel k_td3_head_act below.
+//
+// fp16 window: the split-operand engine holds |weight| < 1023, |activation| < 4094, per-sample gradient < 8190.
+// ReLU activations are not bounded by a LayerNorm; a value outside the window turns the affected products into inf / NaN, the
+// AdamW launch skips a step whose gradient norm is non-finite, and the metrics carry the NaN -- the plugin raises on it, as
+// fastsac.hip does.  Nothing is silently wrong.
+//
+// Noise: the reference draws with torch's CUDA generator; the library uses its counter RNG (threefry, the key split per call
+// like rlx_fastsac_*), and rlx_dbg_set_sac_noise(eps_next, .) injects the given N(0, 1) draws of the exploration noise
+// (rlx_fasttd3_act_f32, [N, A]) and of the smoothing noise (rlx_fasttd3_critic_update_f32, [B, A]) for parity tests.
+// CPU twin: tests/fasttd3_twin.py, pinned by outputs of the reference's own modules and closures (tests/golden/fasttd3_reference.npz).
+#include "gemm_bx.h"
+#include "mlp.h"
+#include "fs_sched.h"
+
+extern "C" int rlx_c51_critic_loss_f32(rlx_ctx* ctx, const float* q1_logits, const float* q2_logits, const float* q1_next_logits,
+                                       const float* q2_next_logits, const float* rewards, const float* dones,
+                                       const float* truncations, const float* effective_n_steps, const float* next_log_probs,
+                                       const float* log_alpha, int64_t B, int nr_atoms, float gamma, float v_min, float v_max,
+                                       int clipped_double_q, float* d_q1_logits, float* d_q2_logits, float* out4, void* stream);
+
+namespace rlx {
+
+// fastsac.hip
+int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
+int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st);
+int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
+                bool relu_mask);
+
+static int td3_check(const rlx_mlp_desc& d) {
+  RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL,
+              "fasttd3: network descriptor needs 1..3 hidden layers and positive widths");
+  RLX_REQUIRE(d.act == RLX_ACT_RELU && !d.ln_first && !d.has_logstd, RLX_EINVAL,
+              "fasttd3: network descriptor must be act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0");
+  for (int l = 0; l < d.n_hidden; ++l)
+    RLX_REQUIRE(d.hidden[l] > 0 && d.hidden[l] % 64 == 0 && d.hidden[l] <= 1024, RLX_EUNSUP,
+                "fasttd3: hidden widths must be multiples of 64, at most 1024");
+  return RLX_OK;
+}
+
+struct TdBufs { float* H[3]; };   // [M, out_l] ReLU outputs (the backward overwrites H_l with dZ_l)
+
+static size_t td3_buf_floats(const MlpLayout& L, int64_t M) {
+  size_t n = 0;
+  for (int l = 0; l < L.n_hidden; ++l) n += ((size_t)M * L.layer[l].out + 63) & ~size_t(63);
+  return n;
+}
+static void td3_carve(const MlpLayout& L, int64_t M, float*& cur, TdBufs* b) {
+  for (int l = 0; l < L.n_hidden; ++l) {
+    b->H[l] = cur;
+    cur += ((size_t)M * L.layer[l].out + 63) & ~size_t(63);
+  }
+}
+
+// split-operand weight images of the trunk GEMMs of a pass with >= 4096 rows (as fastsac.hip: fs_images)
+struct TdNet { const float* p; const MlpLayout* L; bool bwd; };
+static int td3_images(rlx_ctx* ctx, const TdNet* nets, int n, int64_t M, hipStream_t st) {
+  if (M < 4096 || !ctx->gemm_bx) return RLX_OK;
+  BxMat mats[BX_MAX_JOBS];
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    for (int l = 0; l < nets[i].L->n_hidden; ++l) {
+      const LayerOff& o = nets[i].L->layer[l];
+      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
+      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
+    }
+  if (!k) return RLX_OK;
+  const int rc = bx_prepare_mats(ctx, mats, k, st);
+  if (rc) return rc;
+  for (int i = 0; i < ctx->bx_n[0]; ++i) ctx->bx_img[1][i] = ctx->bx_img[0][i];   // the side stream's bank sees the same images
+  ctx->bx_n[1] = ctx->bx_n[0];
+  return RLX_OK;
+}
+
+// trunk forward (Dense + bias + ReLU fused in the GEMM epilogue), then the head when head_out != NULL; x: [M, in], row stride
+// ldx (a multiple of four, zero padded)
+static int td3_fwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float* x, int ldx, const TdBufs& b, float* head_out, int64_t M,
+                   hipStream_t st) {
+  const float* h = x;
+  int ld = ldx;
+  for (int l = 0; l < L.n_hidden; ++l) {
+    const LayerOff& o = L.layer[l];
+    const int rc = launch_gemm_fwd(ctx, h, p + o.W, p + o.b, b.H[l], M, o.out, o.in, RLX_ACT_RELU, st, ld, nullptr);
+    if (rc) return rc;
+    h = b.H[l];
+    ld = o.out;
+  }
+  if (!head_out) return RLX_OK;
+  return fs_head_fwd(h, p + L.head.W, p + L.head.b, head_out, M, L.head.in, L.head.out, st);
+}
+
+// floats the partial-sum buffers of one td3_bwd take from the deferred-reduction arena (head slabs: fs_head_bwd uses at most
+// div_up(M, 32) of them)
+static size_t td3_stage_floats(const rlx_ctx* ctx, const MlpLayout& L, int64_t M, bool grads) {
+  if (!grads) return 0;
+  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
+  const size_t K = L.head.in, N = L.head.out;
+  size_t n = a64((size_t)div_up(M, 32) * (((K * N + 3) & ~size_t(3)) + ((N + 3) & ~size_t(3))));
+  for (int l = 0; l < L.n_hidden; ++l) n += a64(stage_dw_floats(ctx, M, L.layer[l].in, L.layer[l].out));
+  return n;
+}
+
+// backward from d_head [M, head_out].  grads != NULL: parameter gradients (flat layout); dx != NULL: input gradient (row stride
+// lddx), only the columns [dx_c0, dx_c0 + dx_nc) when dx_nc > 0 (the policy loss wants dQ/da: the column-restricted product).
+// The activation buffers are consumed (dZ_l overwrites H_l; ReLU' = (H_l > 0) is applied by the launch that overwrites it).
+static int td3_bwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float* x, int ldx, const TdBufs& b, const float* d_head,
+                   float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
+  const int last = L.n_hidden - 1;
+  int rc = fs_head_bwd(ctx, b.H[last], p + L.head.W, d_head, grads ? grads + L.head.W : nullptr, grads ? grads + L.head.b : nullptr, M,
+                       L.head.in, L.head.out, st, /*relu_mask*/ true);
+  if (rc) return rc;
+  for (int l = last; l >= 0; --l) {
+    const LayerOff& o = L.layer[l];
+    if (grads) {
+      rc = stage_dw(ctx, l == 0 ? x : b.H[l - 1], l == 0 ? ldx : o.in, b.H[l], M, o.in, o.out, grads + o.W, grads + o.b, nullptr, nullptr, st);
+      if (rc) return rc;
+    }
+    if (l > 0) rc = stage_dx(ctx, b.H[l], p + o.W, b.H[l - 1], M, o.out, o.in, o.in, RLX_ACT_RELU, 1, st);
+    else if (dx && dx_nc > 0 && dx_cols_ok(o.out, dx_nc))
+      rc = launch_dx_cols(b.H[0], p + o.W + (int64_t)dx_c0 * o.out, dx + dx_c0, M, o.out, dx_nc, lddx, st);
+    else if (dx) rc = stage_dx(ctx, b.H[0], p + o.W, dx, M, o.out, o.in, lddx, RLX_ACT_NONE, 0, st);
+    if (rc) return rc;
+  }
+  return RLX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- kernels
+enum TdNoise { TD_NOISE_NONE = 0, TD_NOISE_EXPLORE = 1, TD_NOISE_SMOOTH = 2 };
+
+// The policy's head fused with what follows it: one thread per (row, action) computes head = H[i, :] . W[:, j] + b[j] (one
+// ascending fmaf chain; K <= 1024 and A <= 64, small next to the trunk) and a = tanh(head), then
+//   EXPLORE (policy.get_action, policy.py:57-66): a += eps * noise_scale[i]; act[i, j] = a (what the ring stores);
+//            proc[i, j] = clip_rescale ? low + 0.5 (clamp(a, -1, 1) + 1)(high - low) : a (what the env gets)
+//   SMOOTH   (critic_loss_fn, fasttd3.py:143-144): a = clamp(a + clamp(eps * smoothing_eps, +-clip), -1, 1), written straight into
+//            the action columns [c0, c0 + A) of the target critics' input rows (row stride ld): no concat pass
+//   NONE     a itself (the policy step's action columns; evaluation)
+// eps: eps_inject[i, j] (test hook) or normal(bits(key, (i + row_off) * A + j of M_global * A)).
+__global__ __launch_bounds__(256) void k_td3_head_act(const float* __restrict__ H, const float* __restrict__ W, const float* __restrict__ b,
+                                                      int64_t M, int K, int A, int mode, const float* __restrict__ noise_scale, float smooth_eps,
+                                                      float smooth_clip, uint32_t k0, uint32_t k1, int scheme,
+                                                      const float* __restrict__ eps_inject, int64_t row_off, int64_t M_global,
+                                                      float* __restrict__ act, int ld, int c0, float* __restrict__ proc, int clip_rescale,
+                                                      const float* __restrict__ low, const float* __restrict__ high) {
+  const int64_t n = M * A;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const int64_t i = e / A;
+    const int j = (int)(e - i * A);
+    const float* hr = H + i * K;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) acc = fmaf(hr[k], W[(int64_t)k * A + j], acc);
+    float a = tanhf(acc + b[j]);
+    if (mode != TD_NOISE_NONE) {
+      const float eps = eps_inject ? eps_inject[i * A + j]
+                                   : normal_from_bits(random_bits_at(k0, k1, (uint64_t)(i + row_off) * A + j, (uint64_t)M_global * A, scheme));
+      if (mode == TD_NOISE_EXPLORE) {
+        a = a + eps * noise_scale[i];
+      } else {
+        const float nz = fminf(fmaxf(eps * smooth_eps, -smooth_clip), smooth_clip);
+        a = fminf(fmaxf(a + nz, -1.0f), 1.0f);
+      }
+    }
+    act[i * ld + c0 + j] = a;
+    if (proc) proc[i * A + j] = clip_rescale ? low[j] + 0.5f * (fminf(fmaxf(a, -1.0f), 1.0f) + 1.0f) * (high[j] - low[j]) : a;
+  }
+}
+
+// noise_scales[i] = U[0, 1) (noise_std_max - noise_std_min) + noise_std_min for every env (dones == NULL: fasttd3.py:241) or for
+// the envs whose done is set (fasttd3.py:274-278); u = bits(key, i of N) -> [0, 1) as jax.random.uniform
+__global__ __launch_bounds__(256) void k_td3_noise_scales(float* __restrict__ scales, const float* __restrict__ dones, int N, uint32_t k0,
+                                                          uint32_t k1, int scheme, float lo, float hi) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N || (dones && !(dones[i] > 0.f))) return;
+  scales[i] = bits_to_unit(random_bits_at(k0, k1, (uint64_t)i, (uint64_t)N, scheme)) * (hi - lo) + lo;
+}
+
+// policy loss seeds (fasttd3.py:105-120): q_k = sum_j softmax(l_k)_j z_j, q = min(q1, q2) (clipped) or (q1 + q2) / 2,
+// loss = -mean(q); d loss / d l_kj = -(w_k / B) p_kj (z_j - q_k) with torch.minimum's weights: all to the smaller one, 1/2 each on
+// a tie.  One wave per row; partial[block] = sum of -q_b over its four rows.
+__global__ __launch_bounds__(256) void k_td3_policy_seed(const float* __restrict__ l1, const float* __restrict__ l2, float* __restrict__ d1,
+                                                         float* __restrict__ d2, float* __restrict__ partial, int64_t M, int NA, float v_min,
+                                                         float v_max, int clipped, float inv_b) {
+  __shared__ float s_loss[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  const float dz = (v_max - v_min) / (float)(NA - 1);
+  float loss = 0.f;
+  if (row < M) {
+    float q[2], p[2][4];
+    const float* lg[2] = {l1 + row * NA, l2 + row * NA};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      float v[4], mx = -3.4e38f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int a = lane + 64 * u;
+        v[u] = a < NA ? lg[k][a] : -3.4e38f;
+        mx = fmaxf(mx, v[u]);
+      }
+      mx = wave_max(mx);
+      float se = 0.f, sq = 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int a = lane + 64 * u;
+        p[k][u] = a < NA ? expf(v[u] - mx) : 0.f;
+        se += p[k][u];
+        sq += p[k][u] * (v_min + dz * (float)a);
+      }
+      se = wave_sum(se);
+      sq = wave_sum(sq);
+      q[k] = sq / se;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) p[k][u] /= se;
+    }
+    float w1 = 0.5f, w2 = 0.5f, qv = (q[0] + q[1]) * 0.5f;
+    if (clipped) {
+      w1 = q[0] < q[1] ? 1.f : (q[0] > q[1] ? 0.f : 0.5f);
+      w2 = 1.f - w1;
+      qv = fminf(q[0], q[1]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int a = lane + 64 * u;
+      if (a < NA) {
+        const float z = v_min + dz * (float)a;
+        d1[row * NA + a] = -(w1 * inv_b) * p[0][u] * (z - q[0]);
+        d2[row * NA + a] = -(w2 * inv_b) * p[1][u] * (z - q[1]);
+      }
+    }
+    loss = -qv;
+  }
+  if (lane == 0) s_loss[w] = loss;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
+}
+
+// d loss / d head [M, A] of the policy through its tanh: (da1 + da2) (1 - a^2), a = the action the critics saw (their input
+// columns [c0, c0 + A), row stride lda), da_k = the critics' input gradients on those columns
+__global__ __launch_bounds__(256) void k_td3_tanh_bwd(const float* __restrict__ x, const float* __restrict__ da1, const float* __restrict__ da2,
+                                                      int lda, int c0, float* __restrict__ dhead, int64_t M, int A) {
+  const int64_t n = M * A;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const int64_t i = e / A;
+    const int j = (int)(e - i * A);
+    const float a = x[i * lda + c0 + j];
+    dhead[e] = (da1[i * lda + c0 + j] + da2[i * lda + c0 + j]) * (1.0f - a * a);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_td3_policy_loss(const float* __restrict__ partial, int n, float inv_b, float* __restrict__ metrics) {
+  __shared__ float s_buf[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_buf[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) metrics[0] = ((s_buf[0] + s_buf[1]) + (s_buf[2] + s_buf[3])) * inv_b;
+}
+
+static inline int td3_grid(int64_t n) {
+  int g = div_up(n, 256);
+  return g > 4096 ? 4096 : (g < 1 ? 1 : g);
+}
+
+static int td3_head_act(const MlpLayout& L, const float* p, const float* H, int64_t M, int mode, const float* noise_scale, float smooth_eps,
+                        float smooth_clip, const uint32_t ks[2], int scheme, const float* inject, int64_t row_off, int64_t M_global, float* act,
+                        int ld, int c0, float* proc, int clip_rescale, const float* low, const float* high, hipStream_t st) {
+  const int A = L.head.out;
+  hipLaunchKernelGGL(k_td3_head_act, dim3(td3_grid(M * A)), dim3(256), 0, st, H, p + L.head.W, p + L.head.b, M, L.head.in, A, mode, noise_scale,
+                     smooth_eps, smooth_clip, ks[0], ks[1], scheme, inject, row_off, M_global, act, ld, c0, proc, clip_rescale, low, high);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+static int td3_check_pair(const rlx_mlp_desc& pd, const rlx_mlp_desc& qd, const rlx_fasttd3_hparams& hp, int* A_out, int* Oc_out) {
+  int rc = td3_check(pd);
+  if (rc) return rc;
+  rc = td3_check(qd);
+  if (rc) return rc;
+  const int A = pd.out_dim;
+  RLX_REQUIRE(A <= 64, RLX_EUNSUP, "fasttd3: act_dim (policy out_dim) at most 64");
+  RLX_REQUIRE(qd.in_dim > A && qd.out_dim == hp.nr_atoms && hp.nr_atoms >= 2 && hp.nr_atoms <= 128, RLX_EINVAL,
+              "fasttd3: critic in_dim = critic obs + act, out_dim = nr_atoms (2..128)");
+  RLX_REQUIRE(hp.v_max > hp.v_min, RLX_EINVAL, "fasttd3: v_max > v_min");
+  *A_out = A;
+  *Oc_out = qd.in_dim - A;
+  return RLX_OK;
+}
+
+struct BxAllRelease { rlx_ctx* c; ~BxAllRelease() { bx_release_all(c); } };
+
+}  // namespace rlx
+
+using namespace rlx;
+
+extern "C" {
+
+int rlx_fasttd3_noise_scales_f32(rlx_ctx* ctx, uint32_t key_io[2], int scheme, float* noise_scales, const float* dones, int N,
+                                 float noise_std_min, float noise_std_max, void* stream) {
+  RLX_REQUIRE(ctx && key_io && noise_scales && N > 0, RLX_EINVAL, "rlx_fasttd3_noise_scales_f32: bad args");
+  uint32_t ks[4];
+  split_host(key_io, ks, 2, scheme);      // key, subkey = split(key)
+  key_io[0] = ks[0];
+  key_io[1] = ks[1];
+  hipLaunchKernelGGL(k_td3_noise_scales, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, noise_scales, dones, N, ks[2], ks[3], scheme,
+                     noise_std_min, noise_std_max);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int rlx_fasttd3_act_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pparams, const float* obs, const float* noise_scales,
+                        uint32_t key_io[2], int scheme, float* action, float* processed_action, int N, int deterministic,
+                        int clip_and_rescale, const float* low, const float* high, int row_offset, int N_global, void* stream) {
+  RLX_REQUIRE(ctx && pdesc && pparams && obs && key_io && action && processed_action && N > 0 && N_global >= N &&
+                  (deterministic || noise_scales) && (!clip_and_rescale || (low && high)),
+              RLX_EINVAL, "rlx_fasttd3_act_f32: bad args");
+  int rc = td3_check(*pdesc);
+  if (rc) return rc;
+  RLX_REQUIRE(pdesc->out_dim <= 64, RLX_EUNSUP, "rlx_fasttd3_act_f32: act_dim at most 64");
+  hipStream_t st = (hipStream_t)stream;
+  bx_release_all(ctx);
+  const MlpLayout L = make_layout(*pdesc);
+  const int ldp = (pdesc->in_dim + 3) & ~3;
+  float* base = (float*)scratch(ctx, SL_SAC, (td3_buf_floats(L, N) + (size_t)N * ldp + 64) * sizeof(float));
+  if (!base) return RLX_ENOMEM;
+  TdBufs b;
+  float* cur = base;
+  td3_carve(L, N, cur, &b);
+  float* xs = cur;
+  rc = fs_concat(obs, pdesc->in_dim, nullptr, 0, xs, ldp, N, st);
+  if (!rc) rc = td3_fwd(ctx, L, pparams, xs, ldp, b, nullptr, N, st);
+  if (rc) return rc;
+  uint32_t ks[4] = {key_io[0], key_io[1], 0, 0};
+  if (!deterministic) {
+    split_host(key_io, ks, 2, scheme);
+    key_io[0] = ks[0];
+    key_io[1] = ks[1];
+  }
+  return td3_head_act(L, pparams, b.H[L.n_hidden - 1], N, deterministic ? TD_NOISE_NONE : TD_NOISE_EXPLORE, noise_scales, 0.f, 0.f, ks + 2,
+                      scheme, ctx->dbg_sac_eps[0], row_offset, N_global, action, pdesc->out_dim, 0, processed_action, clip_and_rescale, low,
+                      high, st);
+}
+
+int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pparams, const rlx_mlp_desc* qdesc, float* qparams,
+                                  float* qm, float* qv, float* qtarget, const float* states, const float* next_states,
+                                  const float* critic_states, const float* critic_next_states, const float* actions, const float* rewards,
+                                  const float* dones, const float* truncations, const float* effective_n_steps, int64_t B,
+                                  uint32_t key_io[2], int scheme, int64_t* opt_count_io, const rlx_fasttd3_hparams* hp, float* metrics_out,
+                                  void* stream) {
+  RLX_REQUIRE(ctx && pdesc && pparams && qdesc && qparams && qm && qv && qtarget && states && next_states && actions && rewards && dones &&
+                  truncations && effective_n_steps && key_io && opt_count_io && hp && metrics_out && B > 0,
+              RLX_EINVAL, "rlx_fasttd3_critic_update_f32: bad args");
+  int A, Oc;
+  int rc = td3_check_pair(*pdesc, *qdesc, *hp, &A, &Oc);
+  if (rc) return rc;
+  RLX_REQUIRE((critic_states != nullptr) == (critic_next_states != nullptr) && (critic_states || Oc == pdesc->in_dim), RLX_EINVAL,
+              "rlx_fasttd3_critic_update_f32: critic obs width != policy obs width needs critic_states AND critic_next_states");
+  const float* cs = critic_states ? critic_states : states;
+  const float* cn = critic_next_states ? critic_next_states : next_states;
+  hipStream_t st = (hipStream_t)stream;
+  bx_release_all(ctx);
+  const MlpLayout LP = make_layout(*pdesc), LQ = make_layout(*qdesc);
+  const int64_t nq = LQ.n_params;
+  const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
+  // ---- arena: policy trunk, one set for the two target passes (inference, one after the other), two sets for the online critics
+  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
+  const size_t np_b = td3_buf_floats(LP, B), nq_b = td3_buf_floats(LQ, B);
+  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA);
+  const size_t total = np_b + 3 * nq_b + 2 * n_x + 6 * n_log + a64(B) + a64(2 * nq) + a64((size_t)B * ldp) + 128;
+  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (!base || !sq) return RLX_ENOMEM;
+  float* cur = base;
+  TdBufs bp, bt, b1, b2;
+  td3_carve(LP, B, cur, &bp);
+  td3_carve(LQ, B, cur, &bt);
+  td3_carve(LQ, B, cur, &b1);
+  td3_carve(LQ, B, cur, &b2);
+  float* xc = cur; cur += n_x;
+  float* xn = cur; cur += n_x;
+  float *lt1 = cur, *lt2 = cur + n_log, *l1 = cur + 2 * n_log, *l2 = cur + 3 * n_log, *d1 = cur + 4 * n_log, *d2 = cur + 5 * n_log;
+  cur += 6 * n_log;
+  float* zeros = cur; cur += a64(B);                            // next_log_probs of the C51 target: 0 (no entropy term)
+  float* gq = cur; cur += a64(2 * nq);
+  float* xs = cur; cur += a64((size_t)B * ldp);                 // policy observations of s' at a 16-byte row pitch
+  float* ninf = cur;                                            // log_alpha of the C51 target: -inf (alpha = 0)
+  uint32_t ks[4];
+  split_host(key_io, ks, 2, scheme);
+  key_io[0] = ks[0];
+  key_io[1] = ks[1];
+  BxAllRelease bx_all{ctx};
+  {
+    const TdNet nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    rc = td3_images(ctx, nets, 5, B, st);
+    if (rc) return rc;
+  }
+  // Two streams: the online critics on (s, a) on the side stream; the policy on s', the smoothed next action and both target
+  // critics on (s', a') on the caller's stream.  After the C51 loss one critic's backward on each.
+  FsFork fk(ctx, st);
+  rc = fk.begin();
+  if (!rc) rc = fs_concat(cs, Oc, actions, A, xc, ldc, B, st);
+  if (!rc) rc = fk.fork();
+  if (!rc) rc = td3_fwd(ctx, LQ, qparams, xc, ldc, b1, l1, B, fk.side());
+  if (!rc) rc = td3_fwd(ctx, LQ, qparams + nq, xc, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = fs_concat(cn, Oc, nullptr, A, xn, ldc, B, fk.main());
+  if (!rc) rc = fs_concat(next_states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
+  if (!rc) rc = td3_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
+  if (!rc) rc = td3_head_act(LP, pparams, bp.H[LP.n_hidden - 1], B, TD_NOISE_SMOOTH, nullptr, hp->smoothing_epsilon, hp->smoothing_clip_value,
+                             ks + 2, scheme, ctx->dbg_sac_eps[0], 0, B, xn, ldc, Oc, nullptr, 0, nullptr, nullptr, st);
+  if (!rc) rc = td3_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
+  if (!rc) rc = td3_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
+  if (rc) return rc;
+  RLX_HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * sizeof(float), st));
+  RLX_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ninf, (int)0xff800000u, 1, st));
+  rc = fk.join();
+  // ---- C51 target with alpha = exp(-inf) = 0 and zero log-probs: r - discount * 0 * 0 == r exactly; out4 = metrics_out[0..3]
+  if (!rc) rc = rlx_c51_critic_loss_f32(ctx, l1, l2, lt1, lt2, rewards, dones, truncations, effective_n_steps, zeros, ninf, B, NA, hp->gamma,
+                                        hp->v_min, hp->v_max, hp->clipped_double_q, d1, d2, metrics_out, stream);
+  if (rc) return rc;
+  {
+    GradScaleScope gscope(ctx, bx_grad_scale(B));   // d logits ~ 1 / B
+    FsDefer defer(ctx);
+    rc = defer.begin(2 * td3_stage_floats(ctx, LQ, B, true));
+    if (!rc) rc = fk.fork();
+    if (!rc) rc = td3_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
+    if (!rc) rc = td3_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
+    if (!rc) rc = fk.join();
+    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    if (rc) return rc;
+  }
+  // ---- one AdamW over both critics (fasttd3.py:89), clip_grad_norm_ semantics, then the Polyak step (:316-320) in the same launch
+  const int64_t step = *opt_count_io + 1;
+  const int nsq = launch_sumsq_partials(gq, 2 * nq, sq, st);
+  RLX_LAUNCH_CHECK();
+  rc = launch_clip_adam(qparams, gq, qm, qv, 2 * nq, sq, nsq, step, hp->lr_critic, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
+                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 3, st, nullptr, nullptr, qtarget, hp->tau, hp->weight_decay,
+                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  if (rc) return rc;
+  *opt_count_io += 1;
+  return RLX_OK;
+}
+
+int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* qdesc,
+                                  const float* qparams, const float* states, const float* critic_states, int64_t B, int64_t* opt_count_io,
+                                  const rlx_fasttd3_hparams* hp, float* metrics_out, void* stream) {
+  RLX_REQUIRE(ctx && pdesc && pparams && pm && pv && qdesc && qparams && states && opt_count_io && hp && metrics_out && B > 0, RLX_EINVAL,
+              "rlx_fasttd3_policy_update_f32: bad args");
+  int A, Oc;
+  int rc = td3_check_pair(*pdesc, *qdesc, *hp, &A, &Oc);
+  if (rc) return rc;
+  RLX_REQUIRE(critic_states || Oc == pdesc->in_dim, RLX_EINVAL,
+              "rlx_fasttd3_policy_update_f32: critic obs width != policy obs width needs critic_states");
+  const float* cs = critic_states ? critic_states : states;
+  hipStream_t st = (hipStream_t)stream;
+  bx_release_all(ctx);
+  const MlpLayout LP = make_layout(*pdesc), LQ = make_layout(*qdesc);
+  const int64_t np_ = LP.n_params, nq = LQ.n_params;
+  const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
+  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
+  const size_t np_b = td3_buf_floats(LP, B), nq_b = td3_buf_floats(LQ, B);
+  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA), n_hd = a64((size_t)B * A);
+  const int nblk = div_up(B, 4);
+  const size_t total = np_b + 2 * nq_b + 3 * n_x + n_hd + 4 * n_log + a64(nblk) + a64(np_) + a64((size_t)B * ldp) + 64;
+  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (!base || !sq) return RLX_ENOMEM;
+  float* cur = base;
+  TdBufs bp, b1, b2;
+  td3_carve(LP, B, cur, &bp);
+  td3_carve(LQ, B, cur, &b1);
+  td3_carve(LQ, B, cur, &b2);
+  float* xp = cur; cur += n_x;
+  float* dx1 = cur; cur += n_x;
+  float* dx2 = cur; cur += n_x;
+  float* dhead = cur; cur += n_hd;
+  float *l1 = cur, *l2 = cur + n_log, *d1 = cur + 2 * n_log, *d2 = cur + 3 * n_log;
+  cur += 4 * n_log;
+  float* part = cur; cur += a64(nblk);
+  float* gp = cur; cur += a64(np_);
+  float* xs = cur;                                              // policy observations at a 16-byte row pitch
+  const float inv_b = 1.0f / (float)B;
+  const uint32_t no_key[2] = {0, 0};
+  BxAllRelease bx_all{ctx};
+  {
+    const TdNet nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    rc = td3_images(ctx, nets, 3, B, st);
+    if (rc) return rc;
+  }
+  // policy on s, its action straight into the critics' input rows, both critics (one per stream), seeds
+  rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
+  if (!rc) rc = fs_concat(states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
+  if (!rc) rc = td3_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
+  if (!rc) rc = td3_head_act(LP, pparams, bp.H[LP.n_hidden - 1], B, TD_NOISE_NONE, nullptr, 0.f, 0.f, no_key, 0, nullptr, 0, B, xp, ldc, Oc,
+                             nullptr, 0, nullptr, nullptr, st);
+  FsFork fk(ctx, st);
+  if (!rc) rc = fk.begin();
+  if (!rc) rc = fk.fork();
+  if (!rc) rc = td3_fwd(ctx, LQ, qparams + nq, xp, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = td3_fwd(ctx, LQ, qparams, xp, ldc, b1, l1, B, fk.main());
+  if (!rc) rc = fk.join();
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_td3_policy_seed, dim3(nblk), dim3(256), 0, st, (const float*)l1, (const float*)l2, d1, d2, part, B, NA, hp->v_min,
+                     hp->v_max, hp->clipped_double_q, inv_b);
+  RLX_LAUNCH_CHECK();
+  {
+    GradScaleScope gscope(ctx, bx_grad_scale(B));
+    FsDefer defer(ctx);
+    rc = defer.begin(2 * td3_stage_floats(ctx, LQ, B, false) + td3_stage_floats(ctx, LP, B, true));
+    if (rc) return rc;
+    // the critics' input gradients on the action columns (no parameter gradients; one critic per stream), then the policy's backward
+    rc = fk.fork();
+    if (!rc) rc = td3_bwd(ctx, LQ, qparams + nq, xp, ldc, b2, d2, nullptr, dx2, ldc, B, fk.side(), Oc, A);
+    if (!rc) rc = td3_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
+    if (!rc) rc = fk.join();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_td3_tanh_bwd, dim3(td3_grid(B * A)), dim3(256), 0, st, (const float*)xp, (const float*)dx1, (const float*)dx2, ldc, Oc,
+                       dhead, B, A);
+    RLX_LAUNCH_CHECK();
+    rc = td3_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
+    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_td3_policy_loss, dim3(1), dim3(256), 0, st, (const float*)part, nblk, inv_b, metrics_out);
+  RLX_LAUNCH_CHECK();
+  const int64_t step = *opt_count_io + 1;
+  const int nsq = launch_sumsq_partials(gp, np_, sq, st);
+  RLX_LAUNCH_CHECK();
+  rc = launch_clip_adam(pparams, gp, pm, pv, np_, sq, nsq, step, hp->lr_policy, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
+                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 1, st, nullptr, nullptr, nullptr, 0.f, hp->weight_decay,
+                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  if (rc) return rc;
+  *opt_count_io += 1;
+  return RLX_OK;
+}
+
+}  // extern "C"

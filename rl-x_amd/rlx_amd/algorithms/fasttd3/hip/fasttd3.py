@@ -1,15 +1,19 @@
-"""`fastsac.hip`: the FastSAC training loop of rl_x/algorithms/fastsac/pytorch/fastsac.py:243-470 around the library's update
-steps (rl-x_amd/csrc/fastsac.hip).
+"""`fasttd3.hip`: the FastTD3 training loop of rl_x/algorithms/fasttd3/pytorch/fasttd3.py:228-519 around the library's update
+steps (rl-x_amd/csrc/fasttd3.hip).
 
-Per vector step (fastsac.py:247-268): act on the normalised observation (statistics frozen), env.step, ring add.  Once
-`learning_starts` steps are in the ring (:273-276): ONE sample of nr_policy_updates * nr_critic_updates * batch_size transitions
-(:285), the observation normaliser updated on the sampled states and then on the next states (:286-287), and for every policy
-update its critic updates -- each followed by the Polyak step, both inside rlx_fastsac_critic_update_f32 -- and then the policy
-step on the LAST critic slice's states (:300-329).
+Per vector step (fasttd3.py:260-282): act on the normalised observation (statistics frozen) with per-env exploration noise,
+env.step on the processed action, ring add of the UNclipped action, noise scales redrawn where an episode ended.  Once
+`learning_starts` steps are in the ring (:289): ONE sample of nr_policy_updates * nr_critic_updates * batch_size transitions
+(:300), the observation normaliser updated on the sampled states and then on the next states (:301-302), and for every policy
+update its critic updates -- each followed by the Polyak step, both inside rlx_fasttd3_critic_update_f32 -- and then the policy
+step on the LAST critic slice's states (:312-324).
 
-What differs from the reference, on purpose: random numbers (torch's CUDA generator there; the library's counter RNG here, for
-the action noise and the replay indices alike), fp32 instead of bf16 autocast, parameters initialised from numpy with
-torch.nn.Linear's defaults (uniform +-1/sqrt(fan_in); LayerNorm 1 / 0; the policy heads zero, policy.py:58-59)."""
+The replay ring, its sampling, the normaliser, the learning-rate schedule and evaluation are FastSAC's (the reference's two
+algorithms share them: fasttd3/pytorch/replay_buffer.py, observation_normalizer.py); both plugins take them from
+rlx_amd/algorithms/fast_offpolicy.py.  What differs from the reference, on purpose: random numbers (torch's CUDA generator
+there; the library's counter RNG here, for the noise scales, the action noise and the replay indices alike), fp32 instead of bf16 autocast, parameters
+initialised from numpy with torch.nn.Linear's defaults (uniform +-1/sqrt(fan_in); the policy head N(0, 0.01^2), bias 0,
+policy.py:45,50-53)."""
 import json
 import logging
 import os
@@ -18,37 +22,38 @@ import time
 import numpy as np
 
 from rlx_amd.algorithms.fast_offpolicy import FastOffPolicyLoop
-from rlx_amd.algorithms.fastsac.hip.general_properties import GeneralProperties
+from rlx_amd.algorithms.fasttd3.hip.general_properties import GeneralProperties
 from rlx_amd.environments.data_interface_type import DataInterfaceType
 from rlx_amd.plugin import MetricSink, adopt_checkpoint_config
 
 rlx_logger = logging.getLogger("rl_x")
 
-POLICY_HIDDEN = (512, 256, 128)      # policy.py:46-57
-CRITIC_HIDDEN = (768, 384, 192)      # q_network.py:27-38
-METRIC_NAMES = ("loss/q_loss", "loss/entropy_loss", "q/q_min", "q/q_max", "entropy/entropy", "gradients/critic_grad_norm",
-                "gradients/entropy_grad_norm", "entropy/alpha")
+POLICY_HIDDEN = (512, 256, 128)      # policy.py:38-47
+CRITIC_HIDDEN = (1024, 512, 256)     # q_network.py:28-36
+CRITIC_METRICS = ("loss/q_loss", "q/q_min", "q/q_max", "gradients/critic_grad_norm")
+POLICY_METRICS = ("loss/policy_loss", "gradients/policy_grad_norm")
 
 
-def _torch_linear_flat(rng, in_dim, hidden, out_dim, zero_head):
-    """torch.nn.Linear's default initialisation in the library's flat layout (W[in, out], b, LayerNorm scale, LayerNorm bias)."""
+def _torch_linear_flat(rng, in_dim, hidden, out_dim, head_std=None):
+    """torch.nn.Linear's default initialisation in the flat layout (W[in, out], b per layer; then the head).  head_std: the
+    policy head's layer_init (weights N(0, head_std^2), bias 0; policy.py:50-53)."""
     parts, d = [], in_dim
-    for h in hidden:
+    for li, h in enumerate(list(hidden) + [out_dim]):
         bound = 1.0 / np.sqrt(d)
-        parts += [rng.uniform(-bound, bound, (d, h)), rng.uniform(-bound, bound, h), np.ones(h), np.zeros(h)]
+        if li == len(hidden) and head_std is not None:
+            parts += [rng.normal(0.0, head_std, (d, h)), np.zeros(h)]
+        else:
+            parts += [rng.uniform(-bound, bound, (d, h)), rng.uniform(-bound, bound, h)]
         d = h
-    bound = 0.0 if zero_head else 1.0 / np.sqrt(d)
-    parts += [rng.uniform(-bound, bound, (d, out_dim)) if bound else np.zeros((d, out_dim)),
-              rng.uniform(-bound, bound, out_dim) if bound else np.zeros(out_dim)]
     return np.concatenate([p.reshape(-1) for p in parts]).astype(np.float32)
 
 
-class FastSAC(FastOffPolicyLoop):
-    _NAME = "fastsac.hip"
+class FastTD3(FastOffPolicyLoop):
+    _NAME = "fasttd3.hip"
 
     def __init__(self, config, train_env, eval_env, run_path, writer):
         import torch
-        from rlx_amd.hip import Ctx, FastSacHparams, lnmlp_desc
+        from rlx_amd.hip import Ctx, FastTd3Hparams, relu_mlp_desc
         from rlx_amd.hip import lib as hiplib
         self.torch, self.hiplib = torch, hiplib
         self.config, self.train_env, self.eval_env, self.writer = config, train_env, eval_env, writer
@@ -65,23 +70,25 @@ class FastSAC(FastOffPolicyLoop):
         self.logging_frequency, self.evaluation_frequency = int(alg.logging_frequency), int(alg.evaluation_frequency)
         self.save_frequency = int(alg.save_frequency)
         self.obs_norm = bool(alg.enable_observation_normalization)
+        self.noise_std_min, self.noise_std_max = float(alg.noise_std_min), float(alg.noise_std_max)
+        self.clip_and_rescale = bool(alg.action_clipping_and_rescaling)
         self.scheme = 1 if alg.threefry_partitionable else 0
-        if self.logging_frequency % self.nr_envs != 0:                                        # fastsac.py:60-61
+        if self.logging_frequency % self.nr_envs != 0:                                        # fasttd3.py:62-63
             raise ValueError("The logging frequency must be a multiple of the number of environments.")
-        if self.save_frequency != -1 and self.save_frequency % self.nr_envs != 0:             # fastsac.py:63-64
+        if self.save_frequency != -1 and self.save_frequency % self.nr_envs != 0:             # fasttd3.py:65-66
             raise ValueError("The save frequency must be a multiple of the number of environments.")
         if alg.device != "gpu":
-            raise ValueError("fastsac.hip runs on MI355X only: --algorithm.device must be 'gpu' (no CPU fallback)")
+            raise ValueError("fasttd3.hip runs on MI355X only: --algorithm.device must be 'gpu' (no CPU fallback)")
         if bool(alg.bf16_mixed_precision_training):
-            raise ValueError("fastsac.hip computes in fp32: set --algorithm.bf16_mixed_precision_training=False")
+            raise ValueError("fasttd3.hip computes in fp32: set --algorithm.bf16_mixed_precision_training=False")
         if float(alg.max_grad_norm) != -1.0 and float(alg.max_grad_norm) <= 0.0:
-            raise ValueError("fastsac.hip: max_grad_norm must be -1 (off, the reference's sentinel) or positive")
+            raise ValueError("fasttd3.hip: max_grad_norm must be -1 (off, the reference's sentinel) or positive")
         if train_env.general_properties.data_interface_type != DataInterfaceType.TORCH:
-            raise ValueError("fastsac.hip needs a TORCH data-interface environment")
+            raise ValueError("fasttd3.hip needs a TORCH data-interface environment")
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise ValueError("fastsac.hip is single-GPU (its normaliser statistics and gradients are not all-reduced)")
+                raise ValueError("fasttd3.hip is single-GPU (its normaliser statistics and gradients are not all-reduced)")
         except ImportError:
             pass
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -92,43 +99,35 @@ class FastSAC(FastOffPolicyLoop):
         A = int(np.prod(train_env.single_action_space.shape))
         self.obs_dim, self.act_dim = O, A
         from rlx_amd.algorithms.ppo.hip.ppo import PPO as _PPO
-        pidx, cidx = _PPO._observation_indices(train_env, O)            # policy.py:15, q_network.py:12
+        pidx, cidx = _PPO._observation_indices(train_env, O)            # policy.py:13, q_network.py:11
         self.obs_select = pidx is not None
         self.policy_obs_dim, self.critic_obs_dim = (len(pidx), len(cidx)) if self.obs_select else (O, O)
         if self.obs_select:
             self.pidx, self.cidx = torch.from_numpy(pidx).to(self.device), torch.from_numpy(cidx).to(self.device)
-        # action_scale = max(|low - center|, |high - center|) / scale (policy.py:36-43); spaces without center / scale: mid-point, 1
-        sp = train_env.single_action_space
-        low, high = (np.asarray(getattr(sp, k), np.float32).reshape(-1) for k in ("low", "high"))
-        center = np.asarray(getattr(sp, "center", 0.5 * (low + high)), np.float32).reshape(-1)
-        scale = np.asarray(getattr(sp, "scale", np.ones(A)), np.float32).reshape(-1)
-        self.action_scale = torch.from_numpy((np.maximum(np.abs(low - center), np.abs(high - center)) / scale).astype(np.float32)).to(self.device)
-        self.pdesc = lnmlp_desc(self.policy_obs_dim, POLICY_HIDDEN, 2 * A)
-        self.qdesc = lnmlp_desc(self.critic_obs_dim + A, CRITIC_HIDDEN, int(alg.nr_atoms))
+        sp = train_env.single_action_space                              # policy.py:29-30
+        self.act_low, self.act_high = (torch.from_numpy(np.asarray(getattr(sp, k), np.float32).reshape(-1).copy()).to(self.device)
+                                       for k in ("low", "high"))
+        self.pdesc = relu_mlp_desc(self.policy_obs_dim, POLICY_HIDDEN, A)
+        self.qdesc = relu_mlp_desc(self.critic_obs_dim + A, CRITIC_HIDDEN, int(alg.nr_atoms))
         rng = np.random.default_rng(self.seed)
-        self.pparams = torch.from_numpy(_torch_linear_flat(rng, self.policy_obs_dim, POLICY_HIDDEN, 2 * A, True)).to(self.device)
-        q = np.concatenate([_torch_linear_flat(rng, self.critic_obs_dim + A, CRITIC_HIDDEN, int(alg.nr_atoms), False) for _ in range(2)])
+        self.pparams = torch.from_numpy(_torch_linear_flat(rng, self.policy_obs_dim, POLICY_HIDDEN, A, head_std=0.01)).to(self.device)
+        q = np.concatenate([_torch_linear_flat(rng, self.critic_obs_dim + A, CRITIC_HIDDEN, int(alg.nr_atoms)) for _ in range(2)])
         self.qparams = torch.from_numpy(q).to(self.device)
-        self.qtarget = self.qparams.clone()                             # critic.py:19-20
-        te = alg.target_entropy
-        self.target_entropy = -float(A) if te == "auto" else float(te)  # entropy_coefficient.py:17-21
-        self.log_alpha = torch.full((1,), float(np.log(float(alg.alpha_init))), device=self.device)
+        self.qtarget = self.qparams.clone()                             # critic.py:18-19
         z = torch.zeros_like
         self.pm, self.pv, self.qm, self.qv = z(self.pparams), z(self.pparams), z(self.qparams), z(self.qparams)
-        self.am, self.av = torch.zeros(1, device=self.device), torch.zeros(1, device=self.device)
         self.critic_count = self.policy_count = 0
         self.key = hiplib.prng_key(self.seed)
-        if self.obs_norm:     # observation_normalizer.py:19-23
+        if self.obs_norm:     # observation_normalizer.py
             self.norm_mean, self.norm_var, self.norm_std = (torch.zeros(O, device=self.device), torch.ones(O, device=self.device),
                                                             torch.ones(O, device=self.device))
             self.norm_count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.hp = FastSacHparams()
-        for k in ("gamma", "tau", "v_min", "v_max", "log_std_min", "log_std_max", "weight_decay"):
+        self.hp = FastTd3Hparams()
+        for k in ("gamma", "tau", "v_min", "v_max", "weight_decay", "smoothing_epsilon", "smoothing_clip_value"):
             setattr(self.hp, k, float(alg[k]))
-        self.hp.target_entropy = self.target_entropy
-        self.hp.adam_b1, self.hp.adam_b2, self.hp.adam_eps = float(alg.adam_beta1), float(alg.adam_beta2), 1e-8
+        self.hp.adam_b1, self.hp.adam_b2, self.hp.adam_eps = 0.9, 0.999, 1e-8       # torch.optim.AdamW defaults (fasttd3.py:88-89)
         self.hp.nr_atoms, self.hp.clipped_double_q = int(alg.nr_atoms), int(bool(alg.clipped_double_q_learning))
-        self.hp.max_grad_norm = float(alg.max_grad_norm)         # -1: off; else torch clip_grad_norm_ semantics (fastsac.py:129-130, :218-219)
+        self.hp.max_grad_norm = float(alg.max_grad_norm)
         self.horizon = getattr(train_env, "horizon", 1000)
         if self.save_model:
             os.makedirs(self.save_path, exist_ok=True)
@@ -136,8 +135,7 @@ class FastSAC(FastOffPolicyLoop):
 
     # ------------------------------------------------------------------ pieces
     def _alloc(self):
-        """Training buffers: the replay ring, the sampled batch, metric accumulators.  (Acting buffers are per batch size:
-        _act_buffers -- test() / evaluate() need only those.)"""
+        """Training buffers: the replay ring, the sampled batch, the noise scales, metric accumulators."""
         t = self.torch
         N, O, A, cap = self.nr_envs, self.obs_dim, self.act_dim, self.capacity
         f = dict(device=self.device, dtype=t.float32)
@@ -150,34 +148,46 @@ class FastSAC(FastOffPolicyLoop):
         if self.obs_select:
             Op, Oc = self.policy_obs_dim, self.critic_obs_dim
             self.sel = (t.empty(T, Op, **f), t.empty(T, Op, **f), t.empty(T, Oc, **f), t.empty(T, Oc, **f))
-        self.metrics_c, self.metrics_p = t.zeros(8, **f), t.zeros(3, **f)
+        self.noise_scales = t.empty(N, **f)
+        self.metrics_c, self.metrics_p = t.zeros(4, **f), t.zeros(2, **f)
         # sums over the policy updates since the last log (the reference appends one metrics entry per policy update, each with
-        # that block's last critic metrics, and averages them all: fastsac.py:300-345)
-        self.sum_c, self.sum_p, self.n_met = t.zeros(8, **f), t.zeros(3, **f), 0
+        # that block's last critic metrics, and averages them all: fasttd3.py:326-337)
+        self.sum_c, self.sum_p, self.n_met = t.zeros(4, **f), t.zeros(2, **f), 0
 
     def _act_buffers(self, n):
-        """(normalised obs, policy columns, action) for a batch of n envs -- the eval env may have another nr_envs than the train env"""
+        """(normalised obs, policy columns, action, processed action) for a batch of n envs"""
         bufs = self.__dict__.setdefault("_act_bufs", {})
         if n not in bufs:
             t = self.torch
             f = dict(device=self.device, dtype=t.float32)
-            bufs[n] = (t.empty(n, self.obs_dim, **f), t.empty(n, self.policy_obs_dim, **f), t.empty(n, self.act_dim, **f))
+            bufs[n] = (t.empty(n, self.obs_dim, **f), t.empty(n, self.policy_obs_dim, **f), t.empty(n, self.act_dim, **f),
+                       t.empty(n, self.act_dim, **f))
         return bufs[n]
 
-    def act(self, state, deterministic=False):
-        """normalize(update=False) + policy.get_action (fastsac.py:252-254)"""
-        act_norm, act_pobs, action = self._act_buffers(int(state.shape[0]))
+    def act_pair(self, state, deterministic=False):
+        """normalize(update=False) + policy.get_action (fasttd3.py:262-264) -> (action for the ring, processed action for the env)"""
+        act_norm, act_pobs, action, processed = self._act_buffers(int(state.shape[0]))
         x = self.normalize(state.contiguous(), act_norm, False)
         x = self._columns(x, self.pidx if self.obs_select else None, act_pobs)
-        self.key = self.ctx.fastsac_act(self.pdesc, self.pparams, x, self.action_scale, self.key, action, self.hp,
-                                        deterministic=deterministic, scheme=self.scheme)
-        return action
+        low, high = (self.act_low, self.act_high) if self.clip_and_rescale else (None, None)
+        self.key = self.ctx.fasttd3_act(self.pdesc, self.pparams, x, None if deterministic else self.noise_scales, self.key, action,
+                                        processed, deterministic=deterministic, low=low, high=high, scheme=self.scheme)
+        return action, processed
+
+    def act(self, state, deterministic=False):
+        """the action the env gets (evaluation and test(): get_action(x) without noise)"""
+        return self.act_pair(state, deterministic)[1]
+
+    def redraw_noise_scales(self, dones=None):
+        """noise scales for every env (dones None, fasttd3.py:241) or for the envs whose episode ended (:274-278)"""
+        self.key = self.ctx.fasttd3_noise_scales(self.key, self.noise_scales, self.noise_std_min, self.noise_std_max, dones=dones,
+                                                 scheme=self.scheme)
 
     def optimize(self, step_index):
-        """fastsac.py:281-350 for one vector step"""
+        """fasttd3.py:296-341 for one vector step"""
         self.sample()
         s, s2 = self.total[0], self.total[1]
-        self.normalize(s, s, True)                     # total_normalized_states (update=True), then the next states (:286-287)
+        self.normalize(s, s, True)                     # total_normalized_states (update=True), then the next states (:301-302)
         self.normalize(s2, s2, True)
         if self.obs_select:
             sp, s2p, sc, s2c = self.sel
@@ -188,20 +198,20 @@ class FastSAC(FastOffPolicyLoop):
         else:
             sp, s2p, sc, s2c = s, s2, None, None
         lr = self.current_lr(step_index)
-        self.hp.lr_policy = self.hp.lr_critic = self.hp.lr_alpha = lr
+        self.hp.lr_policy = self.hp.lr_critic = lr
         B = self.batch_size
         for i in range(self.nr_policy_updates):
             for j in range(self.nr_critic_updates):
                 o = (i * self.nr_critic_updates + j) * B
                 rows = slice(o, o + B)
                 batch = (sp[rows], s2p[rows]) + tuple(x[rows] for x in self.total[2:])
-                self.key, self.critic_count = self.ctx.fastsac_critic_update(
-                    self.pdesc, self.pparams, self.qdesc, self.qparams, self.qm, self.qv, self.qtarget, self.log_alpha, self.am, self.av,
-                    batch, self.action_scale, self.key, self.critic_count, self.hp, self.metrics_c, self.scheme,
-                    critic_states=None if sc is None else sc[rows], critic_next_states=None if s2c is None else s2c[rows])
-            self.key, self.policy_count = self.ctx.fastsac_policy_update(
-                self.pdesc, self.pparams, self.pm, self.pv, self.qdesc, self.qparams, self.log_alpha, sp[rows], self.action_scale, self.key,
-                self.policy_count, self.hp, self.metrics_p, self.scheme, critic_states=None if sc is None else sc[rows])
+                self.key, self.critic_count = self.ctx.fasttd3_critic_update(
+                    self.pdesc, self.pparams, self.qdesc, self.qparams, self.qm, self.qv, self.qtarget, batch, self.key, self.critic_count,
+                    self.hp, self.metrics_c, self.scheme, critic_states=None if sc is None else sc[rows],
+                    critic_next_states=None if s2c is None else s2c[rows])
+            self.policy_count = self.ctx.fasttd3_policy_update(
+                self.pdesc, self.pparams, self.pm, self.pv, self.qdesc, self.qparams, sp[rows], self.policy_count, self.hp, self.metrics_p,
+                critic_states=None if sc is None else sc[rows])
             self.sum_c += self.metrics_c            # one entry per policy update (device adds, no synchronisation)
             self.sum_p += self.metrics_p
             self.n_met += 1
@@ -211,28 +221,30 @@ class FastSAC(FastOffPolicyLoop):
         checkpoint is written and before logging, so a poisoned state never replaces the last good file"""
         mc, mp = (self.sum_c / self.n_met).cpu().tolist(), (self.sum_p / self.n_met).cpu().tolist()
         if not all(np.isfinite(v) for v in mc + mp):
-            raise FloatingPointError("fastsac.hip: non-finite loss / gradient norm since the last log " + str(mc + mp) +
+            raise FloatingPointError("fasttd3.hip: non-finite loss / gradient norm since the last log " + str(mc + mp) +
                                      " (the optimizer steps of the affected updates were skipped on the device; no checkpoint was "
                                      "written over the last good one)")
         return mc, mp
 
-    # ------------------------------------------------------------------ training loop (fastsac.py:243-470)
+    # ------------------------------------------------------------------ training loop (fasttd3.py:228-446)
     def train(self):
-        t = self.torch
         self._alloc()
         env = self.train_env
         state, _ = env.reset()
         state = state.clone()
+        self.redraw_noise_scales()
         global_step = nr_episodes = opt_steps = 0
         last_log_time, last_log_step = time.time(), 0
         while global_step < self.total_timesteps:
-            action = self.act(state)
-            next_state, reward, terminated, truncated, info = env.step(action)
+            action, processed = self.act_pair(state)
+            next_state, reward, terminated, truncated, info = env.step(processed)
             done = terminated | truncated
-            self.replay_add(state, next_state, action, reward, done.float(), truncated.float())      # fastsac.py:262
+            donef = done.float()
+            self.replay_add(state, next_state, action, reward, donef, truncated.float())          # fasttd3.py:272
+            self.redraw_noise_scales(donef)                                                      # fasttd3.py:274-278
             state = next_state.clone()
             global_step += self.nr_envs
-            if global_step > self.learning_starts * self.nr_envs:                                   # fastsac.py:273
+            if global_step > self.learning_starts * self.nr_envs:                                # fasttd3.py:289
                 self.optimize(opt_steps)
                 opt_steps += 1
             if self.evaluation_frequency != -1 and global_step % self.evaluation_frequency == 0:
@@ -247,8 +259,8 @@ class FastSAC(FastOffPolicyLoop):
                 combined = {}
                 if self.n_met:
                     mc, mp = self._checked_means()                                              # one D2H per logging interval
-                    combined.update({METRIC_NAMES[i]: mc[i] for i in range(8)})
-                    combined.update({"loss/policy_loss": mp[0], "gradients/policy_grad_norm": mp[2]})
+                    combined.update(dict(zip(CRITIC_METRICS, mc)))
+                    combined.update(dict(zip(POLICY_METRICS, mp)))
                 if hasattr(env, "pop_episode_stats"):
                     n_done, mean_ret, mean_len = env.pop_episode_stats()
                     nr_episodes += n_done
@@ -266,10 +278,11 @@ class FastSAC(FastOffPolicyLoop):
                 self.sink.write(global_step, combined)
                 self.last_metrics = combined
 
-    _STATE = ("pparams", "pm", "pv", "qparams", "qm", "qv", "qtarget", "log_alpha", "am", "av")
+    _STATE = ("pparams", "pm", "pv", "qparams", "qm", "qv", "qtarget")
+
     def save(self):
         """Native checkpoint: flat parameter / AdamW-moment vectors, normaliser statistics, counters, the algorithm config (the
-        reference stores the modules' and optimisers' state_dicts, fastsac.py:472-496)."""
+        reference stores the modules' and optimisers' state_dicts, fasttd3.py:449-473)."""
         path = os.path.join(self.save_path, self.best_model_file_name)
         state = {k: getattr(self, k).cpu().numpy() for k in self._STATE + (self._NORM_STATE if self.obs_norm else ())}
         np.savez(path + ".tmp.npz", critic_count=self.critic_count, policy_count=self.policy_count, key=self.key,
@@ -279,8 +292,8 @@ class FastSAC(FastOffPolicyLoop):
     def load(config, train_env, eval_env, run_path, writer, explicitly_set_algorithm_params):
         ckpt = np.load(config.runner.load_model, allow_pickle=False)
         adopt_checkpoint_config(config, json.loads(str(ckpt["config_algorithm"])), explicitly_set_algorithm_params)
-        model = FastSAC(config, train_env, eval_env, run_path, writer)
-        for k in FastSAC._STATE + (FastSAC._NORM_STATE if model.obs_norm else ()):
+        model = FastTD3(config, train_env, eval_env, run_path, writer)
+        for k in FastTD3._STATE + (FastTD3._NORM_STATE if model.obs_norm else ()):
             getattr(model, k).copy_(model.torch.from_numpy(ckpt[k]).to(model.device))
         model.critic_count, model.policy_count = int(ckpt["critic_count"]), int(ckpt["policy_count"])
         model.key = ckpt["key"].astype(np.uint32)

@@ -63,6 +63,17 @@ class FastSacHparams(Structure):
         ("nr_atoms", c_int32), ("clipped_double_q", c_int32)]
 
 
+class FastTd3Hparams(Structure):
+    _fields_ = [(n, c_float) for n in ("gamma", "tau", "v_min", "v_max", "lr_policy", "lr_critic", "weight_decay", "adam_b1", "adam_b2",
+                                       "adam_eps", "max_grad_norm", "smoothing_epsilon", "smoothing_clip_value")] + [
+        ("nr_atoms", c_int32), ("clipped_double_q", c_int32)]
+
+
+def relu_mlp_desc(in_dim, hidden, out_dim):
+    """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
+    return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
+
+
 class LstmPolicyDesc(Structure):
     _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("enc_dim", c_int32), ("lstm_hidden", c_int32),
                 ("torso", c_int32 * 3), ("share_encoder", c_int32), ("cell", c_int32), ("combine", c_int32)]
@@ -206,6 +217,13 @@ _SIGNATURES = {
                                     c_int, POINTER(FastSacHparams), c_void_p]),
     "rlx_fastsac_critic_update_f32": (c_int, [c_void_p, POINTER(LnMlpDesc), c_void_p, POINTER(LnMlpDesc)] + [c_void_p] * 17 +
                                       [c_int64, _U32P, c_int, POINTER(c_int64), POINTER(FastSacHparams), c_void_p, c_void_p]),
+    "rlx_fasttd3_noise_scales_f32": (c_int, [c_void_p, _U32P, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p]),
+    "rlx_fasttd3_act_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _U32P, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "rlx_fasttd3_critic_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, _DESCP] + [c_void_p] * 13 +
+                                      [c_int64, _U32P, c_int, POINTER(c_int64), POINTER(FastTd3Hparams), c_void_p, c_void_p]),
+    "rlx_fasttd3_policy_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_int64,
+                                              POINTER(c_int64), POINTER(FastTd3Hparams), c_void_p, c_void_p]),
     "rlx_fastsac_policy_update_f32": (c_int, [c_void_p, POINTER(LnMlpDesc), c_void_p, c_void_p, c_void_p, POINTER(LnMlpDesc), c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _U32P, c_int, POINTER(c_int64),
                                               POINTER(FastSacHparams), c_void_p, c_void_p]),
@@ -863,6 +881,52 @@ class Ctx:
             _ptr(log_alpha, f), _ptr(states, f), _ptr(critic_states, f, True), _ptr(action_scale, f), int(states.shape[0]), k, scheme,
             ctypes.byref(cnt), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_fastsac_policy_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    # ---- FastTD3 (rl_x/algorithms/fasttd3/pytorch)
+    def fasttd3_noise_scales(self, key, scales, std_min, std_max, dones=None, scheme=THREEFRY_PARTITIONABLE):
+        """noise scales drawn for every env (dones None) or where dones is set; returns the new key"""
+        f = self.torch.float32
+        k = _key_arr(key)
+        _check(self.lib.rlx_fasttd3_noise_scales_f32(self.h, k, scheme, _ptr(scales, f), _ptr(dones, f, True), int(scales.numel()),
+                                                     float(std_min), float(std_max), _stream()), "rlx_fasttd3_noise_scales_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def fasttd3_act(self, pdesc, pparams, obs, noise_scales, key, action, processed, deterministic=False, low=None, high=None,
+                    scheme=THREEFRY_PARTITIONABLE, row_offset=0, n_global=None):
+        """Policy.get_action: (action for the ring, processed action for the env); clip-and-rescale when low / high are given.
+        Returns the new key."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        N = obs.shape[0]
+        _check(self.lib.rlx_fasttd3_act_f32(self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(obs, f), _ptr(noise_scales, f, True), k,
+                                            scheme, _ptr(action, f), _ptr(processed, f), N, int(bool(deterministic)), int(low is not None),
+                                            _ptr(low, f, True), _ptr(high, f, True), int(row_offset), int(n_global or N), _stream()),
+               "rlx_fasttd3_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def fasttd3_critic_update(self, pdesc, pparams, qdesc, qparams, qm, qv, qtarget, batch, key, opt_count, hp, metrics_out,
+                              scheme=THREEFRY_PARTITIONABLE, critic_states=None, critic_next_states=None):
+        """batch = (states, next_states, actions, rewards, dones, truncations, effective_n_steps).  -> (new key, new optimizer count)"""
+        f = self.torch.float32
+        k = _key_arr(key)
+        cnt = c_int64(int(opt_count))
+        s, s2, a, r, d, tr, ns = batch
+        _check(self.lib.rlx_fasttd3_critic_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), ctypes.byref(qdesc), _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f),
+            _ptr(s, f), _ptr(s2, f), _ptr(critic_states, f, True), _ptr(critic_next_states, f, True), _ptr(a, f), _ptr(r, f), _ptr(d, f),
+            _ptr(tr, f), _ptr(ns, f), int(s.shape[0]), k, scheme, ctypes.byref(cnt), ctypes.byref(hp), _ptr(metrics_out, f), _stream()),
+            "rlx_fasttd3_critic_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    def fasttd3_policy_update(self, pdesc, pparams, pm, pv, qdesc, qparams, states, opt_count, hp, metrics_out, critic_states=None):
+        """-> new optimizer count"""
+        f = self.torch.float32
+        cnt = c_int64(int(opt_count))
+        _check(self.lib.rlx_fasttd3_policy_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc), _ptr(qparams, f), _ptr(states, f),
+            _ptr(critic_states, f, True), int(states.shape[0]), ctypes.byref(cnt), ctypes.byref(hp), _ptr(metrics_out, f), _stream()),
+            "rlx_fasttd3_policy_update_f32")
+        return cnt.value
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
