@@ -705,6 +705,90 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pp
                                   const float* qparams, const float* states, const float* critic_states, int64_t B,
                                   int64_t* opt_count_io, const rlx_fasttd3_hparams* hp, float* metrics_out, void* stream);
 
+/* =================================== REPPO ===============================================
+ * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
+ * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust
+ * region.  nn.RMSNorm = weight only, eps = float32 epsilon 1.1920929e-07.  Hidden widths: multiples of 64, at most 768;
+ * act_dim <= 64; nr_bins 2..256.
+ * POLICY FLAT LAYOUT (policy.py:42-52): W1[policy_obs_dim, Hp], b1[Hp], rms1[Hp] | W2[Hp, Hp], b2, rms2 | head W[Hp, 2A], b[2A]
+ *   (columns [0, A) = loc, [A, 2A) = log_std) | log_entropy_coefficient | log_kl_coefficient.
+ * CRITIC FLAT LAYOUT (critic.py:33-55), Hc = critic_hidden: encoder W1[critic_obs_dim + A, Hc], b1, rms1 | W2[Hc, Hc], b2 (-> the
+ *   features F) | critic_head W3[Hc, Hc], b3, rms3 | W4[Hc, nr_bins], b4 | pred_head W5[Hc, Hc], b5, rms5 | W6[Hc, Hc + 1], b6
+ *   (column 0 = reward, 1.. = next features) | zero_distribution[nr_bins].  Both heads start with SiLU(F).
+ * Observations: the FULL normalised state rows [., O]; pidx / cidx: DEVICE int32 policy / critic column indices
+ * (policy_observation_indices / critic_observation_indices), or NULL when that network sees all O columns.
+ * Noise: threefry, key, subkey(s) = split(key) per call; rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) draws:
+ * eps_next = act / evaluate_next [N, A] and the policy step's new-action noise [B, A]; eps_cur = its old-policy noise [K, B, A]. */
+typedef struct rlx_reppo_desc {
+  int32_t policy_obs_dim, critic_obs_dim, act_dim;
+  int32_t policy_hidden, critic_hidden;  /* policy_hidden_dim, critic_hidden_dim (default_config.py: 512, 512) */
+  int32_t nr_bins;
+} rlx_reppo_desc;
+/* net 0: policy, 1: critic; -1 on a bad descriptor */
+int64_t rlx_reppo_param_count(const rlx_reppo_desc*, int net);
+
+typedef struct rlx_reppo_hparams { /* reppo/pytorch/default_config.py */
+  float gamma, gae_lambda, v_min, v_max;
+  float kl_bound;
+  float target_entropy;          /* act_dim * target_entropy_multiplier (reppo.py:63) */
+  float policy_min_std;
+  float auxiliary_loss_coefficient;
+  float max_grad_norm;           /* clip_grad_norm_ of both networks (reppo.py:134, :172); <= 0: none */
+  float adam_b1, adam_b2, adam_eps;  /* torch.optim.Adam defaults (reppo.py:97-98) */
+  int32_t nr_kl_samples;         /* 1..1024 */
+} rlx_reppo_hparams;
+
+/* REPPO's ObservationNormalizer (reppo/pytorch/observation_normalizer.py) -- NOT rlx_obs_norm_*: count is a DEVICE float32
+ * starting at 1e-4 and advanced in float32; update merges the batch mean / population variance of obs[N, O] into mean / var
+ * (:14-28); apply: out = (obs - mean) / sqrt(var + 1e-8) (:31-34, out may alias obs).                                         */
+int rlx_reppo_obs_norm_update_f32(rlx_ctx*, const float* obs, int64_t N, int O, float* mean, float* var, float* count, void* stream);
+int rlx_reppo_obs_norm_apply_f32(rlx_ctx*, const float* obs, int64_t N, int O, const float* mean, const float* var, float* out,
+                                 void* stream);
+/* rollout_act (reppo.py:187-192): policy on obs, Policy.sample_and_log_prob (policy.py:56-64): action = tanh(loc + (exp(log_std)
+ * + min_std) eps) [N, A] (what the batch stores), processed_action = low + 0.5 (clamp(action, -1, 1) + 1)(high - low) (what the env
+ * gets; low / high DEVICE float[A]).  deterministic: action = tanh(loc) (evaluation, test(); policy.py:77-78), key untouched.   */
+int rlx_reppo_act_f32(rlx_ctx*, const rlx_reppo_desc*, const float* pparams, const float* obs, int O, const int32_t* pidx,
+                      uint32_t key_io[2], int scheme, float* action, float* processed_action, const float* low, const float* high, int64_t N,
+                      int deterministic, const rlx_reppo_hparams* hp, void* stream);
+/* rollout_evaluate_next (reppo.py:195-204) on the normalised actual next state: a fresh policy sample a' with its log-prob, the
+ * critic encoder + critic_head on (s', a') (the pred_head is skipped: unused).  Writes next_features[N, critic_hidden] (F),
+ * next_value[N] = sum softmax(logits + 40 zero_distribution) centers, soft_reward[N] = r - gamma next_logp exp(log_entropy_coef). */
+int rlx_reppo_evaluate_next_f32(rlx_ctx*, const rlx_reppo_desc*, const float* pparams, const float* qparams, const float* next_obs, int O,
+                                const int32_t* pidx, const int32_t* cidx, const float* rewards, uint32_t key_io[2], int scheme,
+                                float* next_features, float* next_value, float* soft_reward, int64_t N, const rlx_reppo_hparams* hp,
+                                void* stream);
+/* compute_td_lambda_targets (reppo.py:207-219): reverse scan over T of [T, N] arrays from next_values[T - 1], truncation branch */
+int rlx_reppo_td_lambda_f32(rlx_ctx*, const float* soft_rewards, const float* next_values, const float* terminations,
+                            const float* truncations, int T, int N, float gamma, float gae_lambda, float* targets, void* stream);
+/* ONE critic_loss_fn call (reppo.py:119-136) on the batch rows `rows` (DEVICE int32[B]; NULL: rows 0..B-1) of the flat batch
+ * (states [., O], actions [., A], rewards, targets, terminations, truncations [.], next_features [., critic_hidden]): HL-Gauss
+ * cross-entropy masked by (1 - trunc) + auxiliary_loss_coefficient x the masked next-feature / reward prediction loss, backward,
+ * clip_grad_norm_(max_grad_norm), torch.optim.Adam step number `step` (>= 1) at learning rate lr.  metrics_out: DEVICE float[5] =
+ * {critic_update_loss, auxiliary_loss, q_mean, explained_variance, critic_grad_norm (before clipping)}.                      */
+int rlx_reppo_critic_step_f32(rlx_ctx*, const rlx_reppo_desc*, float* qparams, float* qm, float* qv, const float* states, int O,
+                              const int32_t* cidx, const float* actions, const float* rewards, const float* targets,
+                              const float* next_features, const float* terminations, const float* truncations, const int32_t* rows,
+                              int64_t B, int64_t step, float lr, const rlx_reppo_hparams* hp, float* metrics_out, void* stream);
+/* ONE policy_loss_fn call (reppo.py:140-184) with the critic's parameters frozen (differentiated through to the action):
+ * pathwise value of a fresh sample, the old policy's (old_pparams) nr_kl_samples samples and the new policy's log-prob at them
+ * (atanh of the clamped action), kl = mean_k(old_lp - new_lp); loss = where(kl < kl_bound, alpha logp - value, beta kl) +
+ * the two coefficient losses; clip_grad_norm_, Adam.  metrics_out: DEVICE float[9] = {policy_loss, entropy_coefficient_loss,
+ * kl_coefficient_loss, entropy, kl_divergence, entropy_coefficient, kl_coefficient, policy_q_mean, policy_grad_norm}.        */
+int rlx_reppo_policy_step_f32(rlx_ctx*, const rlx_reppo_desc*, float* pparams, float* pm, float* pv, const float* old_pparams,
+                              const float* qparams, const float* states, int O, const int32_t* pidx, const int32_t* cidx,
+                              const int32_t* rows, int64_t B, uint32_t key_io[2], int scheme, int64_t step, float lr,
+                              const rlx_reppo_hparams* hp, float* metrics_out, void* stream);
+/* The whole optimisation phase of one iteration (reppo.py:358-397): for every epoch e and minibatch m, the rows
+ * perm[e, m * mb : (m + 1) * mb] (perm: DEVICE int32[nr_epochs, batch], mb = batch / nr_minibatches), one critic step then one
+ * policy step on the updated critic, both at Adam step *opt_count_io + 1 (advanced per minibatch).  metrics_out: DEVICE
+ * float[nr_epochs * nr_minibatches, 14] = the critic step's 5 values then the policy step's 9 per minibatch (no host sync).  */
+int rlx_reppo_update_f32(rlx_ctx*, const rlx_reppo_desc*, float* pparams, float* pm, float* pv, const float* old_pparams,
+                         float* qparams, float* qm, float* qv, const float* states, int O, const int32_t* pidx, const int32_t* cidx,
+                         const float* actions, const float* rewards, const float* targets, const float* next_features,
+                         const float* terminations, const float* truncations, int64_t batch, const int32_t* perm, int nr_epochs,
+                         int nr_minibatches, uint32_t key_io[2], int scheme, int64_t* opt_count_io, float lr, const rlx_reppo_hparams* hp,
+                         float* metrics_out, void* stream);
+
 /* =================================== PPO + LSTM =======================================
  * Recurrent policy (rl_x/algorithms/ppo_lstm/flax_full_jit/policy.py:32-142, "concat" and "film" decoders):
  *   lstm_obs_encode / obs_encode: Dense(E)+LN+ELU on obs; OptimizedLSTMCell(H); LN+ELU on h;

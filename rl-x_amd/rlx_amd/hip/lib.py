@@ -69,6 +69,25 @@ class FastTd3Hparams(Structure):
         ("nr_atoms", c_int32), ("clipped_double_q", c_int32)]
 
 
+class ReppoDesc(Structure):
+    """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
+    _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
+                ("critic_hidden", c_int32), ("nr_bins", c_int32)]
+
+
+def reppo_desc(policy_obs_dim, critic_obs_dim, act_dim, policy_hidden, critic_hidden, nr_bins):
+    d = ReppoDesc()
+    d.policy_obs_dim, d.critic_obs_dim, d.act_dim = int(policy_obs_dim), int(critic_obs_dim), int(act_dim)
+    d.policy_hidden, d.critic_hidden, d.nr_bins = int(policy_hidden), int(critic_hidden), int(nr_bins)
+    return d
+
+
+class ReppoHparams(Structure):
+    _fields_ = [(n, c_float) for n in ("gamma", "gae_lambda", "v_min", "v_max", "kl_bound", "target_entropy", "policy_min_std",
+                                       "auxiliary_loss_coefficient", "max_grad_norm", "adam_b1", "adam_b2", "adam_eps")] + [
+        ("nr_kl_samples", c_int32)]
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -227,6 +246,21 @@ _SIGNATURES = {
     "rlx_fastsac_policy_update_f32": (c_int, [c_void_p, POINTER(LnMlpDesc), c_void_p, c_void_p, c_void_p, POINTER(LnMlpDesc), c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _U32P, c_int, POINTER(c_int64),
                                               POINTER(FastSacHparams), c_void_p, c_void_p]),
+    "rlx_reppo_param_count": (c_int64, [POINTER(ReppoDesc), c_int]),
+    "rlx_reppo_obs_norm_update_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_reppo_obs_norm_apply_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_reppo_act_f32": (c_int, [c_void_p, POINTER(ReppoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_int64, c_int, POINTER(ReppoHparams), c_void_p]),
+    "rlx_reppo_evaluate_next_f32": (c_int, [c_void_p, POINTER(ReppoDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                            _U32P, c_int, c_void_p, c_void_p, c_void_p, c_int64, POINTER(ReppoHparams), c_void_p]),
+    "rlx_reppo_td_lambda_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "rlx_reppo_critic_step_f32": (c_int, [c_void_p, POINTER(ReppoDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 8 +
+                                  [c_int64, c_int64, c_float, POINTER(ReppoHparams), c_void_p, c_void_p]),
+    "rlx_reppo_policy_step_f32": (c_int, [c_void_p, POINTER(ReppoDesc)] + [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                  _U32P, c_int, c_int64, c_float, POINTER(ReppoHparams), c_void_p, c_void_p]),
+    "rlx_reppo_update_f32": (c_int, [c_void_p, POINTER(ReppoDesc)] + [c_void_p] * 8 + [c_int] + [c_void_p] * 8 +
+                             [c_int64, c_void_p, c_int, c_int, _U32P, c_int, POINTER(c_int64), c_float, POINTER(ReppoHparams), c_void_p,
+                              c_void_p]),
     "rlx_dist_overflow_count": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "rlx_ppo_dist_prefetch": (c_int, [c_void_p, _U32P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rlx_ppo_update_dist_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p,
@@ -927,6 +961,86 @@ class Ctx:
             _ptr(critic_states, f, True), int(states.shape[0]), ctypes.byref(cnt), ctypes.byref(hp), _ptr(metrics_out, f), _stream()),
             "rlx_fasttd3_policy_update_f32")
         return cnt.value
+
+    # ---- REPPO (rl_x/algorithms/reppo/pytorch)
+    def reppo_param_count(self, desc, net):
+        """net 0: policy, 1: critic"""
+        return int(self.lib.rlx_reppo_param_count(ctypes.byref(desc), int(net)))
+
+    def reppo_obs_norm_update(self, obs, mean, var, count):
+        """REPPO's ObservationNormalizer.update: obs [N, O]; mean / var fp32 [O], count fp32 [1] (starts at 1e-4)"""
+        f = self.torch.float32
+        _check(self.lib.rlx_reppo_obs_norm_update_f32(self.h, _ptr(obs, f), int(obs.shape[0]), int(obs.shape[1]), _ptr(mean, f), _ptr(var, f),
+                                                      _ptr(count, f), _stream()), "rlx_reppo_obs_norm_update_f32")
+
+    def reppo_obs_norm_apply(self, obs, mean, var, out):
+        f = self.torch.float32
+        _check(self.lib.rlx_reppo_obs_norm_apply_f32(self.h, _ptr(obs, f), int(obs.shape[0]), int(obs.shape[1]), _ptr(mean, f), _ptr(var, f),
+                                                     _ptr(out, f), _stream()), "rlx_reppo_obs_norm_apply_f32")
+        return out
+
+    def reppo_act(self, desc, pparams, obs, key, action, processed, low, high, hp, deterministic=False, pidx=None,
+                  scheme=THREEFRY_PARTITIONABLE):
+        """rollout_act -> new key"""
+        f, k = self.torch.float32, _key_arr(key)
+        _check(self.lib.rlx_reppo_act_f32(self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(obs, f), int(obs.shape[1]),
+                                          _ptr(pidx, self.torch.int32, True), k, scheme, _ptr(action, f), _ptr(processed, f), _ptr(low, f),
+                                          _ptr(high, f), int(obs.shape[0]), int(bool(deterministic)), ctypes.byref(hp), _stream()),
+               "rlx_reppo_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def reppo_evaluate_next(self, desc, pparams, qparams, next_obs, rewards, key, next_features, next_value, soft_reward, hp, pidx=None,
+                            cidx=None, scheme=THREEFRY_PARTITIONABLE):
+        """rollout_evaluate_next -> new key"""
+        f, i32, k = self.torch.float32, self.torch.int32, _key_arr(key)
+        _check(self.lib.rlx_reppo_evaluate_next_f32(
+            self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(qparams, f), _ptr(next_obs, f), int(next_obs.shape[1]), _ptr(pidx, i32, True),
+            _ptr(cidx, i32, True), _ptr(rewards, f), k, scheme, _ptr(next_features, f), _ptr(next_value, f), _ptr(soft_reward, f),
+            int(next_obs.shape[0]), ctypes.byref(hp), _stream()), "rlx_reppo_evaluate_next_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def reppo_td_lambda(self, soft_rewards, next_values, terminations, truncations, gamma, gae_lambda, targets):
+        f = self.torch.float32
+        T, N = soft_rewards.shape
+        _check(self.lib.rlx_reppo_td_lambda_f32(self.h, _ptr(soft_rewards, f), _ptr(next_values, f), _ptr(terminations, f),
+                                                _ptr(truncations, f), int(T), int(N), float(gamma), float(gae_lambda), _ptr(targets, f),
+                                                _stream()), "rlx_reppo_td_lambda_f32")
+        return targets
+
+    def reppo_critic_step(self, desc, qparams, qm, qv, batch, step, lr, hp, metrics_out, rows=None, cidx=None):
+        """batch = (states, actions, rewards, targets, next_features, terminations, truncations); B = len(rows) or the batch's rows"""
+        f, i32 = self.torch.float32, self.torch.int32
+        s, a, r, tg, nf, te, tr = batch
+        B = int(rows.numel()) if rows is not None else int(s.shape[0])
+        _check(self.lib.rlx_reppo_critic_step_f32(
+            self.h, ctypes.byref(desc), _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(s, f), int(s.shape[1]), _ptr(cidx, i32, True),
+            _ptr(a, f), _ptr(r, f), _ptr(tg, f), _ptr(nf, f), _ptr(te, f), _ptr(tr, f), _ptr(rows, i32, True), B, int(step), float(lr),
+            ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_reppo_critic_step_f32")
+
+    def reppo_policy_step(self, desc, pparams, pm, pv, old_pparams, qparams, states, key, step, lr, hp, metrics_out, rows=None, pidx=None,
+                          cidx=None, scheme=THREEFRY_PARTITIONABLE):
+        """-> new key"""
+        f, i32, k = self.torch.float32, self.torch.int32, _key_arr(key)
+        B = int(rows.numel()) if rows is not None else int(states.shape[0])
+        _check(self.lib.rlx_reppo_policy_step_f32(
+            self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), _ptr(old_pparams, f), _ptr(qparams, f), _ptr(states, f),
+            int(states.shape[1]), _ptr(pidx, i32, True), _ptr(cidx, i32, True), _ptr(rows, i32, True), B, k, scheme, int(step), float(lr),
+            ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_reppo_policy_step_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def reppo_update(self, desc, pparams, pm, pv, old_pparams, qparams, qm, qv, batch, perm, nr_minibatches, key, opt_count, lr, hp,
+                     metrics_out, pidx=None, cidx=None, scheme=THREEFRY_PARTITIONABLE):
+        """batch = flat (states, actions, rewards, targets, next_features, terminations, truncations); perm int32 [nr_epochs, batch].
+        -> (new key, new optimizer count)"""
+        f, i32, k = self.torch.float32, self.torch.int32, _key_arr(key)
+        s, a, r, tg, nf, te, tr = batch
+        cnt = c_int64(int(opt_count))
+        _check(self.lib.rlx_reppo_update_f32(
+            self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), _ptr(old_pparams, f), _ptr(qparams, f), _ptr(qm, f),
+            _ptr(qv, f), _ptr(s, f), int(s.shape[1]), _ptr(pidx, i32, True), _ptr(cidx, i32, True), _ptr(a, f), _ptr(r, f), _ptr(tg, f),
+            _ptr(nf, f), _ptr(te, f), _ptr(tr, f), int(s.shape[0]), _ptr(perm, i32), int(perm.shape[0]), int(nr_minibatches), k, scheme,
+            ctypes.byref(cnt), float(lr), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_reppo_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current

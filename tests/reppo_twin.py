@@ -1,0 +1,249 @@
+"""Float64 CPU twin of rl-x_amd/csrc/reppo.hip (REPPO, rl_x/algorithms/reppo/pytorch), written from the library's flat parameter
+layouts (include/rlx_hip.h, rlx_reppo_desc): the networks, Policy.sample_and_log_prob / log_prob, critic_loss_fn, policy_loss_fn,
+rollout_act, rollout_evaluate_next, compute_td_lambda_targets, the observation normaliser, clip_grad_norm_ + Adam.  Gradients
+come from torch autograd in float64 on the CPU; nothing here touches the GPU or the library."""
+import math
+
+import numpy as np
+import torch
+
+RMS_EPS = float(np.finfo(np.float32).eps)       # nn.RMSNorm(eps=None) on float32 modules
+D = torch.float64
+
+
+def _lin(off, i, o, rms):
+    e = {"in": i, "out": o, "W": off, "b": off + i * o}
+    off += i * o + o
+    if rms:
+        e["g"] = off
+        off += o
+    return e, off
+
+
+def policy_layout(Op, A, Hp):
+    L, off = {}, 0
+    L["l0"], off = _lin(off, Op, Hp, True)
+    L["l1"], off = _lin(off, Hp, Hp, True)
+    L["head"], off = _lin(off, Hp, 2 * A, False)
+    L["coef"] = off
+    L["n"] = off + 2
+    return L
+
+
+def critic_layout(Oc, A, Hc, NB):
+    L, off = {}, 0
+    L["e0"], off = _lin(off, Oc + A, Hc, True)
+    L["e1"], off = _lin(off, Hc, Hc, False)
+    L["c0"], off = _lin(off, Hc, Hc, True)
+    L["c1"], off = _lin(off, Hc, NB, False)
+    L["p0"], off = _lin(off, Hc, Hc, True)
+    L["p1"], off = _lin(off, Hc, Hc + 1, False)
+    L["zd"] = off
+    L["n"] = off + NB
+    return L
+
+
+def zero_distribution(NB, v_min, v_max):
+    """critic.py:50-53, in float32 as the reference's module computes it"""
+    bw = (v_max - v_min) / (NB - 1)
+    support = torch.linspace(v_min - bw / 2, v_max + bw / 2, NB + 1, dtype=torch.float32)
+    cdf = torch.erf(support / (np.sqrt(2) * bw * 0.75))
+    return ((cdf[1:] - cdf[:-1]) / (cdf[-1] - cdf[0])).numpy()
+
+
+def make_params(seed, Op, Oc, A, Hp, Hc, NB, v_min, v_max, init_entropy_coefficient=0.01, init_kl_coefficient=0.01):
+    """torch defaults from a seeded numpy generator: Linear W, b ~ U(+-1/sqrt(fan_in)), RMSNorm weight 1, zero_distribution from
+    its erf formula, log(init coefficients) -> (policy flat, critic flat), float32"""
+    rng = np.random.default_rng(seed)
+
+    def fill(L, names, n):
+        flat = np.zeros(n)
+        for k in names:
+            e = L[k]
+            bound = 1.0 / np.sqrt(e["in"])
+            flat[e["W"]:e["W"] + e["in"] * e["out"]] = rng.uniform(-bound, bound, e["in"] * e["out"])
+            flat[e["b"]:e["b"] + e["out"]] = rng.uniform(-bound, bound, e["out"])
+            if "g" in e:
+                flat[e["g"]:e["g"] + e["out"]] = 1.0
+        return flat
+    LP, LQ = policy_layout(Op, A, Hp), critic_layout(Oc, A, Hc, NB)
+    p = fill(LP, ("l0", "l1", "head"), LP["n"])
+    p[LP["coef"]] = math.log(init_entropy_coefficient)
+    p[LP["coef"] + 1] = math.log(init_kl_coefficient)
+    q = fill(LQ, ("e0", "e1", "c0", "c1", "p0", "p1"), LQ["n"])
+    q[LQ["zd"]:] = zero_distribution(NB, v_min, v_max)
+    return p.astype(np.float32), q.astype(np.float32)
+
+
+def _t(x):
+    return x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+
+
+def _W(p, e):
+    return p[e["W"]:e["W"] + e["in"] * e["out"]].reshape(e["in"], e["out"])
+
+
+def _dense(p, e, x):
+    return x @ _W(p, e) + p[e["b"]:e["b"] + e["out"]]
+
+
+def _rms_silu(p, e, x):
+    z = _dense(p, e, x)
+    y = z * torch.rsqrt(z.pow(2).mean(-1, keepdim=True) + RMS_EPS) * p[e["g"]:e["g"] + e["out"]]
+    return torch.nn.functional.silu(y)
+
+
+def policy_fwd(p, L, x):
+    h = _rms_silu(p, L["l1"], _rms_silu(p, L["l0"], x))
+    out = _dense(p, L["head"], h)
+    A = out.shape[-1] // 2
+    return out[..., :A], out[..., A:]
+
+
+def critic_fwd(q, L, x, pred=True):
+    """-> features F, logits (+ 40 zero_distribution), pred [., H + 1] or None"""
+    F = _dense(q, L["e1"], _rms_silu(q, L["e0"], x))
+    S = torch.nn.functional.silu(F)
+    logits = _dense(q, L["c1"], _rms_silu(q, L["c0"], S)) + 40.0 * q[L["zd"]:L["n"]]
+    pr = _dense(q, L["p1"], _rms_silu(q, L["p0"], S)) if pred else None
+    return F, logits, pr
+
+
+def sample_and_log_prob(loc, log_std, noise, min_std):       # policy.py:56-64
+    std = log_std.exp() + min_std
+    base = loc + std * noise
+    action = torch.tanh(base)
+    glp = -0.5 * noise.pow(2) - 0.5 * math.log(2.0 * math.pi) - torch.log(std)
+    corr = 2.0 * (math.log(2.0) - base - torch.nn.functional.softplus(-2.0 * base))
+    return action, (glp - corr).sum(-1)
+
+
+def log_prob(loc, log_std, action, min_std):                 # policy.py:67-74
+    std = log_std.exp() + min_std
+    base = torch.atanh(torch.clamp(action, -1.0 + 1e-6, 1.0 - 1e-6))
+    glp = -0.5 * ((base - loc) / std).pow(2) - 0.5 * math.log(2.0 * math.pi) - torch.log(std)
+    corr = 2.0 * (math.log(2.0) - base - torch.nn.functional.softplus(-2.0 * base))
+    return (glp - corr).sum(-1)
+
+
+def centers(hp, NB):
+    return torch.linspace(hp["v_min"], hp["v_max"], NB, dtype=D)
+
+
+def act(p, LP, obs, noise, hp, low, high, deterministic=False):
+    """rollout_act (reppo.py:187-192) -> (action, processed action)"""
+    loc, ls = policy_fwd(_t(p), LP, _t(obs))
+    a = torch.tanh(loc) if deterministic else sample_and_log_prob(loc, ls, _t(noise), hp["policy_min_std"])[0]
+    low, high = _t(low), _t(high)
+    return a.numpy(), (low + 0.5 * (torch.clamp(a, -1.0, 1.0) + 1.0) * (high - low)).numpy()
+
+
+def evaluate_next(p, LP, q, LQ, next_obs_p, next_obs_c, reward, noise, hp):
+    """rollout_evaluate_next (reppo.py:195-204) -> (next_features, next_value, soft_reward)"""
+    p, q = _t(p), _t(q)
+    loc, ls = policy_fwd(p, LP, _t(next_obs_p))
+    a, lp = sample_and_log_prob(loc, ls, _t(noise), hp["policy_min_std"])
+    F, logits, _ = critic_fwd(q, LQ, torch.cat([_t(next_obs_c), a], -1), pred=False)
+    v = (torch.softmax(logits, -1) * centers(hp, logits.shape[-1])).sum(-1)
+    soft = _t(reward) - hp["gamma"] * lp * p[LP["coef"]].exp()
+    return F.numpy(), v.numpy(), soft.numpy()
+
+
+def td_lambda(soft_rewards, next_values, terms, truncs, gamma, lam):   # reppo.py:207-219
+    sr, nv, te, tr = (np.asarray(x, np.float64) for x in (soft_rewards, next_values, terms, truncs))
+    out = np.zeros_like(nv)
+    lr = nv[-1]
+    for t in range(nv.shape[0] - 1, -1, -1):
+        lsum = lam * lr + (1 - lam) * nv[t]
+        lr = sr[t] + gamma * (tr[t] * nv[t] + (1.0 - tr[t]) * (1.0 - te[t]) * lsum)
+        out[t] = lr
+    return out
+
+
+def obs_norm_update(mean, var, count, obs):
+    """observation_normalizer.py:14-28 in float32 arithmetic (count float32) -> (mean, var, count)"""
+    f = np.float32
+    x = torch.as_tensor(np.asarray(obs, np.float32))
+    bm, bv = x.mean(dim=0).numpy(), x.var(dim=0, unbiased=False).numpy()     # the reference's float32 reductions
+    bc = f(x.shape[0])
+    delta = (bm - mean).astype(f)
+    total = f(count + bc)
+    new_mean = (mean + (delta * bc) / total).astype(f)
+    m2 = ((var * count) + (bv * bc) + ((delta * delta) * count) * bc / total).astype(f)
+    return new_mean, (m2 / total).astype(f), total
+
+
+def clip_adam(params, grads, m, v, step, lr, max_norm, b1=0.9, b2=0.999, eps=1e-8):
+    """clip_grad_norm_ (g * min(1, c / (norm + 1e-6))) + torch.optim.Adam -> (params, m, v, norm before clipping)"""
+    norm = float(np.sqrt(np.sum(grads * grads)))
+    g = grads * min(1.0, max_norm / (norm + 1e-6)) if max_norm > 0 else grads
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+    params = params - (lr / bc1) * m / (np.sqrt(v) / math.sqrt(bc2) + eps)
+    return params, m, v, norm
+
+
+def critic_loss(q, LQ, obs_c, actions, targets, rewards, next_features, terms, truncs, hp):
+    """critic_loss_fn (reppo.py:119-130) -> (loss, critic_update_loss.mean, auxiliary_loss.mean, value.mean, explained variance)"""
+    NB = LQ["n"] - LQ["zd"]
+    _, logits, pred = critic_fwd(q, LQ, torch.cat([_t(obs_c), _t(actions)], -1))
+    targets, rewards, terms, truncs = _t(targets), _t(rewards), _t(terms), _t(truncs)
+    bw = (hp["v_max"] - hp["v_min"]) / (NB - 1)
+    support = torch.linspace(hp["v_min"] - bw / 2, hp["v_max"] + bw / 2, NB + 1, dtype=D)
+    cdf = torch.erf((support - torch.clamp(targets, hp["v_min"], hp["v_max"]).unsqueeze(-1)) / (math.sqrt(2) * bw * 0.75))
+    td = (cdf[..., 1:] - cdf[..., :-1]) / (cdf[..., -1:] - cdf[..., :1])
+    cul = -(td * torch.log_softmax(logits, -1)).sum(-1)
+    aux = torch.cat([(pred[..., 1:] - _t(next_features)).square(), (pred[..., :1] - rewards.unsqueeze(-1)).square()], -1).mean(-1)
+    cul = (1.0 - truncs) * cul
+    aux = (1.0 - truncs) * (1.0 - terms) * aux
+    loss = cul.mean() + hp["auxiliary_loss_coefficient"] * aux.mean()
+    value = (torch.softmax(logits, -1) * centers(hp, NB)).sum(-1)
+    ev = 1 - torch.var(targets - value, correction=0) / (torch.var(targets, correction=0) + 1e-8)
+    return loss, cul.mean(), aux.mean(), value.mean(), ev
+
+
+def critic_step(q, qm, qv, step, lr, LQ, batch, hp):
+    """one critic step -> (q, qm, qv, metrics[5], gradient)"""
+    qt = torch.tensor(np.asarray(q, np.float64), requires_grad=True)
+    loss, cul, aux, vm, ev = critic_loss(qt, LQ, *batch, hp)
+    loss.backward()
+    g = qt.grad.numpy().copy()
+    q2, m2, v2, norm = clip_adam(np.asarray(q, np.float64), g, qm, qv, step, lr, hp["max_grad_norm"])
+    return q2, m2, v2, np.array([float(cul), float(aux), float(vm), float(ev), norm]), g
+
+
+def policy_loss(p, LP, old_p, q, LQ, obs_p, obs_c, eps_new, eps_old, hp, f32_old_action=False):
+    """policy_loss_fn (reppo.py:140-168) -> (loss, metrics[8], kl per row).  f32_old_action: round the old policy's actions to
+    float32 before log_prob's atanh, as a float32 run does (near |a| = 1 that rounding dominates the KL terms' error)"""
+    mstd = hp["policy_min_std"]
+    loc, ls = policy_fwd(p, LP, _t(obs_p))
+    a, lp = sample_and_log_prob(loc, ls, _t(eps_new), mstd)
+    _, logits, _ = critic_fwd(_t(q), LQ, torch.cat([_t(obs_c), a], -1), pred=False)
+    value = (torch.softmax(logits, -1) * centers(hp, logits.shape[-1])).sum(-1)
+    with torch.no_grad():
+        oloc, ols = policy_fwd(_t(old_p), LP, _t(obs_p))
+    K = eps_old.shape[0]
+    oa, olp = sample_and_log_prob(oloc.expand(K, -1, -1), ols.expand(K, -1, -1), _t(eps_old), mstd)
+    if f32_old_action:
+        oa = oa.to(torch.float32).to(D)
+    nlp = log_prob(loc.expand(K, -1, -1), ls.expand(K, -1, -1), oa, mstd)
+    kl = (olp - nlp).mean(0)
+    alpha, beta = p[LP["coef"]].exp(), p[LP["coef"] + 1].exp()
+    clipped = torch.where(kl < hp["kl_bound"], lp * alpha.detach() - value, kl * beta.detach())
+    ent = -lp
+    ecl = alpha * (hp["target_entropy"] + ent).detach()
+    kcl = -beta * (kl.detach() - hp["kl_bound"])
+    loss = clipped.mean() + ecl.mean() + kcl.mean()
+    met = [clipped.mean(), ecl.mean(), kcl.mean(), ent.mean(), kl.mean(), alpha, beta, value.mean()]
+    return loss, np.array([float(x) for x in met]), kl.detach().numpy()
+
+
+def policy_step(p, pm, pv, old_p, q, step, lr, LP, LQ, obs_p, obs_c, eps_new, eps_old, hp, f32_old_action=False):
+    """one policy step -> (p, pm, pv, metrics[9], gradient, kl per row)"""
+    pt = torch.tensor(np.asarray(p, np.float64), requires_grad=True)
+    loss, met, kl = policy_loss(pt, LP, old_p, q, LQ, obs_p, obs_c, _t(eps_new), _t(eps_old), hp, f32_old_action)
+    loss.backward()
+    g = pt.grad.numpy().copy()
+    p2, m2, v2, norm = clip_adam(np.asarray(p, np.float64), g, pm, pv, step, lr, hp["max_grad_norm"])
+    return p2, m2, v2, np.append(met, norm), g, kl
