@@ -13,7 +13,10 @@ outputs only (batch, noise, scalars + seeded samples of gradients, updated param
 
 Cases: 0 every row inside the KL bound (old policy == policy); 1 an old policy that differs, kl_bound between two rows' KL
 values near the median (a mix of both branches of the `where`); 2 gradient clipping active (max_grad_norm far below both
-gradient norms).  Every case has terminations and truncations in its minibatch."""
+gradient norms); 3 policy hidden 128 != critic hidden 64, 151 bins over v +-100 (the reference's support), policy_min_std 0.05,
+auxiliary_loss_coefficient 0.5, targets beyond +-100 and on both edges (the clamp), an old policy that differs.  Every case has
+terminations and truncations in its minibatch.  Cases 0-2 store one `hidden` and use HP's settings; a case with overrides
+stores `policy_hidden`, `critic_hidden` and the CASE_KEYS it runs with."""
 import math
 import os
 import sys
@@ -29,13 +32,19 @@ from make_reference_golden import REF, _sampled, load_by_path, save, train_closu
 
 import reppo_twin as tw  # noqa: E402
 
-CASES = (  # (obs, act, hidden, nr_bins, batch, kl samples, param seed, old-policy seed, max_grad_norm)
-    (9, 3, 64, 21, 40, 4, 31, None, 0.5),
-    (7, 2, 64, 51, 48, 6, 32, 77, 0.5),
-    (9, 3, 64, 21, 40, 4, 33, 78, 0.002),
+CASES = (  # (obs, act, hidden, nr_bins, batch, kl samples, param seed, old-policy seed, max_grad_norm, overrides)
+    (9, 3, 64, 21, 40, 4, 31, None, 0.5, {}),
+    (7, 2, 64, 51, 48, 6, 32, 77, 0.5, {}),
+    (9, 3, 64, 21, 40, 4, 33, 78, 0.002, {}),
+    # hidden (policy, critic), the reference's bins and value range, a minimum std and an auxiliary coefficient != 1; targets
+    # beyond +-v_max and one on each edge (the clamp)
+    (9, 3, (128, 64), 151, 48, 5, 34, 79, 0.5, dict(v_min=-100.0, v_max=100.0, policy_min_std=0.05, auxiliary_loss_coefficient=0.5,
+                                                    wide_targets=True)),
 )
 HP = dict(gamma=0.99, gae_lambda=0.95, v_min=-10.0, v_max=10.0, learning_rate=3e-4, policy_min_std=0.0, auxiliary_loss_coefficient=1.0,
           init_entropy_coefficient=0.05, init_kl_coefficient=0.02, target_entropy_multiplier=0.5)
+# the settings a case may override; a case that overrides one also stores it (and both widths), the others keep their keys
+CASE_KEYS = ("v_min", "v_max", "policy_min_std", "auxiliary_loss_coefficient")
 
 
 def policy_linears(P):
@@ -96,20 +105,22 @@ def make_reppo():
     sp = types.SimpleNamespace
     rel = "rl_x/algorithms/reppo/pytorch/reppo.py"
     try:
-        for case, (O, A, H, NB, B, K, seed, old_seed, mgn) in enumerate(CASES):
+        for case, (O, A, H, NB, B, K, seed, old_seed, mgn, over) in enumerate(CASES):
             k = "c%d_" % case
+            Hp, Hc = H if isinstance(H, tuple) else (H, H)
+            hpc = dict(HP, **{n: over[n] for n in CASE_KEYS if n in over})
             g = torch.Generator().manual_seed(500 + case)
             r32 = lambda *sh: torch.randn(*sh, generator=g, dtype=torch.float64).to(torch.float32).to(dtype)
             low, high = -np.ones(A, np.float32), np.ones(A, np.float32)
             env = sp(single_action_space=sp(low=low, high=high, shape=(A,)), single_observation_space=sp(shape=(O,)))
-            P = pol.Policy(env, H, HP["policy_min_std"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"], np.arange(O), "cpu").to(dtype)
-            OP = pol.Policy(env, H, HP["policy_min_std"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"], np.arange(O), "cpu").to(dtype)
-            C = cri.Critic(env, H, NB, HP["v_min"], HP["v_max"], np.arange(O), "cpu").to(dtype)
+            P = pol.Policy(env, Hp, hpc["policy_min_std"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"], np.arange(O), "cpu").to(dtype)
+            OP = pol.Policy(env, Hp, hpc["policy_min_std"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"], np.arange(O), "cpu").to(dtype)
+            C = cri.Critic(env, Hc, NB, hpc["v_min"], hpc["v_max"], np.arange(O), "cpu").to(dtype)
             for m in list(P.modules()) + list(OP.modules()) + list(C.modules()):
                 if isinstance(m, nn.RMSNorm):
                     m.eps = tw.RMS_EPS
-            p, q = tw.make_params(seed, O, O, A, H, H, NB, HP["v_min"], HP["v_max"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"])
-            old_p = p if old_seed is None else tw.make_params(old_seed, O, O, A, H, H, NB, HP["v_min"], HP["v_max"])[0]
+            p, q = tw.make_params(seed, O, O, A, Hp, Hc, NB, hpc["v_min"], hpc["v_max"], HP["init_entropy_coefficient"], HP["init_kl_coefficient"])
+            old_p = p if old_seed is None else tw.make_params(old_seed, O, O, A, Hp, Hc, NB, hpc["v_min"], hpc["v_max"])[0]
             pb, ob, cb = policy_linears(P), policy_linears(OP), critic_linears(C)
             pe, oe, ce = [P.log_entropy_coefficient, P.log_kl_coefficient], [OP.log_entropy_coefficient, OP.log_kl_coefficient], [C.zero_distribution]
             load(pb, pe, p)
@@ -120,13 +131,17 @@ def make_reppo():
             states, next_states = r32(B, O), r32(B, O)
             actions = torch.tanh(r32(B, A)).to(torch.float32).to(dtype)
             rewards, targets = (r32(B) * 2.0).to(torch.float32).to(dtype), (r32(B) * 3.0).to(torch.float32).to(dtype)
-            next_features = (r32(B, H) * 0.5).to(torch.float32).to(dtype)
+            next_features = (r32(B, Hc) * 0.5).to(torch.float32).to(dtype)
             terms = (torch.rand(B, generator=g) < 0.2).to(dtype)
             truncs = (torch.rand(B, generator=g) < 0.15).to(dtype) * (1.0 - terms)
             eps_eval, eps_new, eps_old = r32(B, A), r32(B, A), r32(K, B, A)
-            hpc = dict(HP, nr_kl_samples=K, max_grad_norm=mgn, target_entropy=A * HP["target_entropy_multiplier"], kl_bound=0.1)
+            if over.get("wide_targets"):      # TD-lambda targets past the support: several beyond +-v_max, one on each edge
+                v = hpc["v_max"]
+                targets = (r32(B) * (0.6 * v)).to(torch.float32).to(dtype)
+                targets[:4] = torch.tensor([v, -v, 2.5 * v, -1.375 * v], dtype=dtype)
+            hpc.update(nr_kl_samples=K, max_grad_norm=mgn, target_entropy=A * HP["target_entropy_multiplier"], kl_bound=0.1)
             if old_seed is not None:          # kl_bound between two rows' KL values near the median, far from both
-                kl = tw.policy_loss(torch.tensor(p, dtype=dtype), tw.policy_layout(O, A, H), old_p, q, tw.critic_layout(O, A, H, NB),
+                kl = tw.policy_loss(torch.tensor(p, dtype=dtype), tw.policy_layout(O, A, Hp), old_p, q, tw.critic_layout(O, A, Hc, NB),
                                     states.numpy(), states.numpy(), eps_new, eps_old, hpc)[2]
                 s = np.sort(kl)
                 i = max(range(B // 4, 3 * B // 4), key=lambda j: s[j + 1] - s[j])
@@ -138,18 +153,23 @@ def make_reppo():
                 assert tuple(e.shape) == tuple(x.shape), (e.shape, x.shape)
                 return e.to(x.dtype)
             torch.randn_like = randn_like
-            bw = (HP["v_max"] - HP["v_min"]) / (NB - 1)
-            me = sp(policy=P, old_policy=OP, critic=C, gamma=HP["gamma"], v_min=HP["v_min"], v_max=HP["v_max"], kl_bound=hpc["kl_bound"],
-                    auxiliary_loss_coefficient=HP["auxiliary_loss_coefficient"], nr_kl_samples=K, target_entropy=hpc["target_entropy"],
+            v_min, v_max = hpc["v_min"], hpc["v_max"]
+            bw = (v_max - v_min) / (NB - 1)
+            me = sp(policy=P, old_policy=OP, critic=C, gamma=HP["gamma"], v_min=v_min, v_max=v_max, kl_bound=hpc["kl_bound"],
+                    auxiliary_loss_coefficient=hpc["auxiliary_loss_coefficient"], nr_kl_samples=K, target_entropy=hpc["target_entropy"],
                     max_grad_norm=mgn, bf16_mixed_precision_training=False)
             me.policy_optimizer = torch.optim.Adam(P.parameters(), lr=HP["learning_rate"], fused=False)
             me.critic_optimizer = torch.optim.Adam(C.parameters(), lr=HP["learning_rate"], fused=False)
             ns = {"torch": torch, "nn": nn, "math": math, "self": me, "autocast": torch.autocast,
-                  "hl_gauss_centers": torch.linspace(HP["v_min"], HP["v_max"], NB),
-                  "hl_gauss_support": torch.linspace(HP["v_min"] - bw / 2, HP["v_max"] + bw / 2, NB + 1), "hl_gauss_sigma": bw * 0.75}
+                  "hl_gauss_centers": torch.linspace(v_min, v_max, NB),
+                  "hl_gauss_support": torch.linspace(v_min - bw / 2, v_max + bw / 2, NB + 1), "hl_gauss_sigma": bw * 0.75}
             critic_fn, policy_fn, eval_next, td = train_closures(
                 rel, ["critic_loss_fn", "policy_loss_fn", "rollout_evaluate_next", "compute_td_lambda_targets"], ns)
-            out.update({k + "obs_dim": O, k + "act_dim": A, k + "hidden": H, k + "nr_bins": NB, k + "batch": B, k + "nr_kl_samples": K,
+            if over:
+                out.update({k + "policy_hidden": Hp, k + "critic_hidden": Hc}, **{k + n: hpc[n] for n in CASE_KEYS})
+            else:
+                out[k + "hidden"] = H
+            out.update({k + "obs_dim": O, k + "act_dim": A, k + "nr_bins": NB, k + "batch": B, k + "nr_kl_samples": K,
                         k + "param_seed": seed, k + "old_seed": -1 if old_seed is None else old_seed, k + "max_grad_norm": mgn,
                         k + "kl_bound": hpc["kl_bound"], k + "states": states, k + "next_states": next_states, k + "actions": actions,
                         k + "rewards": rewards, k + "targets": targets, k + "next_features": next_features, k + "terms": terms,

@@ -149,6 +149,27 @@ def evaluate_next(p, LP, q, LQ, next_obs_p, next_obs_c, reward, noise, hp):
     return F.numpy(), v.numpy(), soft.numpy()
 
 
+def fixture_case(z, c):
+    """case c of tests/golden/reppo_reference.npz -> dict: shapes (O, A, Hp, Hc, NB, B, K), hyperparameters hp, parameters p /
+    q / old_p and layouts LP / LQ.  Cases with one `hidden` run at HP_FIXTURE's settings; the others store both widths and
+    their own settings (tests/golden/make_reppo_golden.py, CASE_KEYS)"""
+    k = "c%d_" % c
+    g = lambda n: z[k + n]
+    has = lambda n: k + n in z.files
+    O, A, NB, B, K = (int(g(n)) for n in ("obs_dim", "act_dim", "nr_bins", "batch", "nr_kl_samples"))
+    Hp, Hc = (int(g("hidden")),) * 2 if has("hidden") else (int(g("policy_hidden")), int(g("critic_hidden")))
+    hp = dict(HP_FIXTURE, **{n: float(g(n)) for n in ("v_min", "v_max", "policy_min_std", "auxiliary_loss_coefficient") if has(n)})
+    hp.update(kl_bound=float(g("kl_bound")), max_grad_norm=float(g("max_grad_norm")), target_entropy=A * 0.5, nr_kl_samples=K)
+    p, q = make_params(int(g("param_seed")), O, O, A, Hp, Hc, NB, hp["v_min"], hp["v_max"], 0.05, 0.02)
+    old_p = p if int(g("old_seed")) < 0 else make_params(int(g("old_seed")), O, O, A, Hp, Hc, NB, hp["v_min"], hp["v_max"])[0]
+    return dict(O=O, A=A, Hp=Hp, Hc=Hc, NB=NB, B=B, K=K, hp=hp, p=p, q=q, old_p=old_p, LP=policy_layout(O, A, Hp),
+                LQ=critic_layout(O, A, Hc, NB))
+
+
+# the settings of the fixture's cases that do not store their own (make_reppo_golden.py HP)
+HP_FIXTURE = dict(gamma=0.99, gae_lambda=0.95, v_min=-10.0, v_max=10.0, policy_min_std=0.0, auxiliary_loss_coefficient=1.0)
+
+
 def td_lambda(soft_rewards, next_values, terms, truncs, gamma, lam):   # reppo.py:207-219
     sr, nv, te, tr = (np.asarray(x, np.float64) for x in (soft_rewards, next_values, terms, truncs))
     out = np.zeros_like(nv)

@@ -9,84 +9,11 @@ import pytest
 import torch
 
 import reppo_twin as tw
-from rlx_amd.hip import ReppoHparams, reppo_desc
+from reppo_cases import HP, Case, _close, _f32, _hp, _rel, _t, _with_noise, place_kl_bound, value_floor
+from rlx_amd.hip import reppo_desc
 from rlx_amd.hip import lib as L
 
 pytestmark = pytest.mark.gpu
-
-HP = dict(gamma=0.99, gae_lambda=0.95, v_min=-10.0, v_max=10.0, kl_bound=0.1, policy_min_std=0.0, auxiliary_loss_coefficient=1.0,
-          max_grad_norm=0.5, nr_kl_samples=4)
-
-
-def _t(a, dev, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype))).to(dev)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
-
-
-def _close(a, b, floor=1.0):
-    """1e-5 relative (L2), with an absolute floor per element: expected values sum_j p_j z_j over centers of order 10 cancel to
-    ~1e-6 at initialisation, where float32 leaves ~1e-7"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) <= 1e-5 * max(np.linalg.norm(b), floor * np.sqrt(b.size))
-
-
-def _hp(h):
-    hp = ReppoHparams()
-    for k in ("gamma", "gae_lambda", "v_min", "v_max", "kl_bound", "target_entropy", "policy_min_std", "auxiliary_loss_coefficient",
-              "max_grad_norm"):
-        setattr(hp, k, float(h[k]))
-    hp.adam_b1, hp.adam_b2, hp.adam_eps = 0.9, 0.999, 1e-8
-    hp.nr_kl_samples = int(h["nr_kl_samples"])
-    return hp
-
-
-def _f32(x):
-    return np.asarray(x, np.float32).astype(np.float64)
-
-
-class Case:
-    """shapes, parameters (float32-representable) and a batch; O full columns, the policy / critic see index subsets"""
-
-    def __init__(self, seed, B, O=13, A=3, Hp=64, Hc=64, NB=21, old_seed=None, obs_scale=1.0, **hp):
-        self.h = dict(HP, **hp)
-        self.h["target_entropy"] = A * 0.5
-        rng = np.random.default_rng(seed)
-        self.pidx = np.sort(rng.choice(O, O - 2, replace=False)).astype(np.int32)
-        self.cidx = np.arange(O, dtype=np.int32)[::-1].copy()
-        self.O, self.A, self.Hp, self.Hc, self.NB, self.B = O, A, Hp, Hc, NB, B
-        Op, Oc = len(self.pidx), len(self.cidx)
-        self.desc = reppo_desc(Op, Oc, A, Hp, Hc, NB)
-        self.LP, self.LQ = tw.policy_layout(Op, A, Hp), tw.critic_layout(Oc, A, Hc, NB)
-        self.p, self.q = tw.make_params(seed, Op, Oc, A, Hp, Hc, NB, self.h["v_min"], self.h["v_max"], 0.05, 0.02)
-        self.old_p = self.p if old_seed is None else tw.make_params(old_seed, Op, Oc, A, Hp, Hc, NB, self.h["v_min"], self.h["v_max"])[0]
-        r32 = lambda *sh: _f32(rng.standard_normal(sh))
-        self.states = _f32(r32(B, O) * obs_scale)
-        self.actions = _f32(np.tanh(r32(B, A)))
-        self.rewards = _f32(r32(B) * 2.0)
-        self.targets = _f32(r32(B) * 3.0)
-        self.next_features = rng.standard_normal((B, Hc), dtype=np.float32) * np.float32(0.5)
-        self.terms = (rng.random(B) < 0.2).astype(np.float64)
-        self.truncs = ((rng.random(B) < 0.15) & (self.terms == 0)).astype(np.float64)
-        self.eps_new = r32(B, A)
-        self.eps_old = r32(self.h["nr_kl_samples"], B, A)
-
-    def batch_twin(self):
-        return (self.states[:, self.cidx], self.actions, self.targets, self.rewards, self.next_features, self.terms, self.truncs)
-
-    def batch_dev(self, dev):
-        return tuple(_t(x, dev) for x in (self.states, self.actions, self.rewards, self.targets, self.next_features, self.terms, self.truncs))
-
-
-def _with_noise(ctx, eps_next, eps_cur, fn):
-    ctx.dbg_set_sac_noise(eps_next, eps_cur)
-    try:
-        return fn()
-    finally:
-        ctx.dbg_set_sac_noise(None, None)
 
 
 def test_param_counts_match_the_twin(ctx):
@@ -167,16 +94,7 @@ CASES = {  # name -> Case kwargs
 
 
 def _case(name):
-    c = Case(**CASES[name])
-    if c.old_p is not c.p:      # put the bound between two rows' KL values near the median, far from every row
-        kl = tw.policy_loss(torch.tensor(c.p, dtype=torch.float64), c.LP, c.old_p, c.q, c.LQ, c.states[:, c.pidx], c.states[:, c.cidx],
-                            tw._t(c.eps_new), tw._t(c.eps_old), c.h)[2]
-        s = np.sort(kl)
-        mid = len(s) // 2
-        i = max(range(mid - len(s) // 4, mid + len(s) // 4), key=lambda j: s[j + 1] - s[j])
-        c.h["kl_bound"] = float(np.float32(0.5 * (s[i] + s[i + 1])))
-        assert (s[i + 1] - s[i]) / 2 > 1e-4      # every row's KL at least 1e-4 from the bound: far beyond float32 error
-    return c
+    return place_kl_bound(Case(**CASES[name]))
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -312,28 +230,26 @@ def test_whole_update_equals_single_steps(ctx, dev, envs, steps, mbs, epochs):
         assert torch.isfinite(met).all()
 
 
-@pytest.mark.parametrize("c", [0, 1, 2])
+@pytest.mark.parametrize("c", [0, 1, 2, 3])
 def test_steps_match_the_reference_fixture(ctx, dev, c):
     """one critic step, then one policy step on the updated critic, against the outputs of the reference's own closures"""
     import os
     z = np.load(os.path.join(os.path.dirname(__file__), "golden", "reppo_reference.npz"))
     k = "c%d_" % c
     g = lambda n: z[k + n]
-    O, A, H, NB, K = (int(g(n)) for n in ("obs_dim", "act_dim", "hidden", "nr_bins", "nr_kl_samples"))
-    h = dict(HP, kl_bound=float(g("kl_bound")), max_grad_norm=float(g("max_grad_norm")), target_entropy=A * 0.5, nr_kl_samples=K)
+    fc = tw.fixture_case(z, c)
+    O, A, Hp, Hc, NB, B = (fc[n] for n in ("O", "A", "Hp", "Hc", "NB", "B"))
+    h, p, q, old_p = dict(HP, **fc["hp"]), fc["p"], fc["q"], fc["old_p"]
     hp = _hp(h)
-    p, q = tw.make_params(int(g("param_seed")), O, O, A, H, H, NB, -10.0, 10.0, 0.05, 0.02)
-    old_p = p if int(g("old_seed")) < 0 else tw.make_params(int(g("old_seed")), O, O, A, H, H, NB, -10.0, 10.0)[0]
-    desc = reppo_desc(O, O, A, H, H, NB)
-    B = int(g("batch"))
+    desc = reppo_desc(O, O, A, Hp, Hc, NB)
     P, Q, OP = _t(p, dev), _t(q, dev), _t(old_p, dev)
     z_ = lambda n: torch.zeros(n, device=dev)
     pm, pv, qm, qv = z_(p.size), z_(p.size), z_(q.size), z_(q.size)
     batch = tuple(_t(g(n), dev) for n in ("states", "actions", "rewards", "targets", "next_features", "terms", "truncs"))
-    nf, nv, sr = torch.empty(B, H, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
+    nf, nv, sr = torch.empty(B, Hc, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev)
     ee = _t(g("eps_eval"), dev)
     _with_noise(ctx, ee, None, lambda: ctx.reppo_evaluate_next(desc, P, Q, _t(g("next_states"), dev), batch[2], L.prng_key(0), nf, nv, sr, hp))
-    assert _rel(nf.cpu().numpy(), g("eval_next_features")) < 1e-5 and _close(nv.cpu().numpy(), g("eval_next_value"))
+    assert _rel(nf.cpu().numpy(), g("eval_next_features")) < 1e-5 and _close(nv.cpu().numpy(), g("eval_next_value"), value_floor(h))
     assert _rel(sr.cpu().numpy(), g("eval_soft_reward")) < 1e-5
     cm, pmet = z_(5), z_(9)
     ctx.reppo_critic_step(desc, Q, qm, qv, batch, 1, 3e-4, hp, cm)
@@ -352,12 +268,12 @@ def test_steps_match_the_reference_fixture(ctx, dev, c):
     # fixture's bases reach |3.6| .. |6.5|, where this conditioning exceeds 1e-5 of the KL: the KL-dependent scalars (clipped loss,
     # kl coefficient loss, kl) get that float32 bound on top of the 1e-5 bar.
     with torch.no_grad():
-        LP = tw.policy_layout(O, A, H)
+        LP, LQ = fc["LP"], fc["LQ"]
         oloc, ols = tw.policy_fwd(torch.tensor(old_p, dtype=torch.float64), LP, torch.tensor(g("states")))
         loc, ls = tw.policy_fwd(torch.tensor(p, dtype=torch.float64), LP, torch.tensor(g("states")))
-        oa = torch.tanh(oloc + ols.exp() * torch.tensor(g("eps_old")))
+        oa = torch.tanh(oloc + (ols.exp() + h["policy_min_std"]) * torch.tensor(g("eps_old")))
         b = torch.atanh(torch.clamp(oa, -1 + 1e-6, 1 - 1e-6))
-        std = ls.exp()
+        std = ls.exp() + h["policy_min_std"]
         sens = ((b - loc) / std).abs() / std + 2.0
         kl_f32 = float(((2.0 ** -24) / (1.0 - oa * oa) * sens).sum(-1).mean())
     beta = float(np.exp(p[LP["coef"] + 1]))
@@ -370,11 +286,10 @@ def test_steps_match_the_reference_fixture(ctx, dev, c):
     # agreement is pinned at 1e-12 on the CPU, tests/test_reppo_twin.py)
     idx = z[k + "gcritic_idx"]
     assert _rel(qm.cpu().numpy()[idx] / 0.1, z[k + "gcritic_val"]) < 1e-5
-    h["v_min"], h["v_max"], h["policy_min_std"] = -10.0, 10.0, 0.0
     zq = np.zeros(q.size)
-    rq = tw.critic_step(q, zq, zq, 1, 3e-4, tw.critic_layout(O, A, H, NB),
-                        tuple(g(n) for n in ("states", "actions", "targets", "rewards", "next_features", "terms", "truncs")), h)[0]
-    _, _, _, rmet, gp, _ = tw.policy_step(p, np.zeros(p.size), np.zeros(p.size), old_p, rq, 1, 3e-4, LP, tw.critic_layout(O, A, H, NB),
+    rq = tw.critic_step(q, zq, zq, 1, 3e-4, LQ, tuple(g(n) for n in ("states", "actions", "targets", "rewards", "next_features", "terms", "truncs")),
+                        h)[0]
+    _, _, _, rmet, gp, _ = tw.policy_step(p, np.zeros(p.size), np.zeros(p.size), old_p, rq, 1, 3e-4, LP, LQ,
                                           g("states"), g("states"), g("eps_new"), g("eps_old"), h, f32_old_action=True)
     gp_clipped = gp * min(1.0, h["max_grad_norm"] / (rmet[8] + 1e-6))
     assert _rel(pm.cpu().numpy() / 0.1, gp_clipped) < 1e-5

@@ -66,7 +66,9 @@ def test_obs_norm_count_is_float32():
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rl_x/algorithms/reppo/pytorch")), reason="needs the reference checkout")
-def test_networks_match_the_reference_modules():
+@pytest.mark.parametrize("Hp,Hc,NB,v", [(64, 64, 21, 10.0), (128, 64, 151, 100.0), (64, 192, 65, 100.0)],
+                         ids=["h64_v10", "hp128_hc64_v100", "hp64_hc192_v100"])
+def test_networks_match_the_reference_modules(Hp, Hc, NB, v):
     """the twin's network forward passes against the reference's Policy / Critic modules in float64 (the sampler, the losses and
     the normaliser are pinned by the fixture tests below)"""
     import sys
@@ -76,17 +78,17 @@ def test_networks_match_the_reference_modules():
     sys.path.insert(0, REF)
     pol = load_by_path("rl_x/algorithms/reppo/pytorch/policy.py", "ref_reppo_policy")
     cri = load_by_path("rl_x/algorithms/reppo/pytorch/critic.py", "ref_reppo_critic")
-    O, A, H, NB = 7, 2, 64, 21
+    O, A = 7, 2
     sp = types.SimpleNamespace
     env = sp(single_action_space=sp(low=-np.ones(A, np.float32), high=np.ones(A, np.float32), shape=(A,)),
              single_observation_space=sp(shape=(O,)))
-    P = pol.Policy(env, H, 0.0, 0.05, 0.02, np.arange(O), "cpu").double()
-    C = cri.Critic(env, H, NB, -10.0, 10.0, np.arange(O), "cpu").double()
+    P = pol.Policy(env, Hp, 0.0, 0.05, 0.02, np.arange(O), "cpu").double()
+    C = cri.Critic(env, Hc, NB, -v, v, np.arange(O), "cpu").double()
     for m in list(P.modules()) + list(C.modules()):
         if isinstance(m, torch.nn.RMSNorm):
             m.eps = tw.RMS_EPS
-    p, q = tw.make_params(3, O, O, A, H, H, NB, -10.0, 10.0, 0.05, 0.02)
-    LP, LQ = tw.policy_layout(O, A, H), tw.critic_layout(O, A, H, NB)
+    p, q = tw.make_params(3, O, O, A, Hp, Hc, NB, -v, v, 0.05, 0.02)
+    LP, LQ = tw.policy_layout(O, A, Hp), tw.critic_layout(O, A, Hc, NB)
     t = lambda a: torch.from_numpy(np.asarray(a, np.float64))
 
     def load(seq_lins, L, names, flat):
@@ -101,7 +103,7 @@ def test_networks_match_the_reference_modules():
         P.log_entropy_coefficient.copy_(t(p[LP["coef"]:LP["coef"] + 1]))
         P.log_kl_coefficient.copy_(t(p[LP["coef"] + 1:]))
         C.zero_distribution.copy_(t(q[LQ["zd"]:]))
-    assert np.array_equal(np.asarray(C.zero_distribution.detach().numpy(), np.float32), tw.zero_distribution(NB, -10.0, 10.0))
+    assert np.array_equal(np.asarray(C.zero_distribution.detach().numpy(), np.float32), tw.zero_distribution(NB, -v, v))
     rng = np.random.default_rng(4)
     x, e = t(rng.standard_normal((9, O))), t(rng.standard_normal((9, A)))
     with torch.no_grad():
@@ -119,14 +121,6 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "reppo_reference.npz"
 LR = 3e-4
 
 
-def _hp(z, c):
-    k = "c%d_" % c
-    A = int(z[k + "act_dim"])
-    return dict(gamma=0.99, gae_lambda=0.95, v_min=-10.0, v_max=10.0, policy_min_std=0.0, auxiliary_loss_coefficient=1.0,
-                kl_bound=float(z[k + "kl_bound"]), max_grad_norm=float(z[k + "max_grad_norm"]), target_entropy=A * 0.5,
-                nr_kl_samples=int(z[k + "nr_kl_samples"]))
-
-
 def _check_sampled(z, name, full, tol=1e-12):
     idx = z[name + "_idx"]
     assert abs(np.linalg.norm(full) - z[name + "_norm"]) <= tol * z[name + "_norm"], name
@@ -142,19 +136,16 @@ def test_fixture_is_inputs_and_outputs_only():
     z = np.load(GOLDEN)
     assert str(z["source"]).startswith("reference:rl_x/algorithms/reppo/pytorch")
     assert not os.path.basename(GOLDEN).startswith("reference_")
-    assert int(z["n_cases"]) == 3
+    assert int(z["n_cases"]) == 4
 
 
-@pytest.mark.parametrize("c", [0, 1, 2])
+@pytest.mark.parametrize("c", [0, 1, 2, 3])
 def test_twin_reproduces_the_reference_fixture(c):
     z = np.load(GOLDEN)
     k = "c%d_" % c
     g = lambda n: z[k + n]
-    O, A, H, NB = (int(g(n)) for n in ("obs_dim", "act_dim", "hidden", "nr_bins"))
-    hp = _hp(z, c)
-    p, q = tw.make_params(int(g("param_seed")), O, O, A, H, H, NB, -10.0, 10.0, 0.05, 0.02)
-    old_p = p if int(g("old_seed")) < 0 else tw.make_params(int(g("old_seed")), O, O, A, H, H, NB, -10.0, 10.0)[0]
-    LP, LQ = tw.policy_layout(O, A, H), tw.critic_layout(O, A, H, NB)
+    fc = tw.fixture_case(z, c)
+    hp, p, q, old_p, LP, LQ = (fc[n] for n in ("hp", "p", "q", "old_p", "LP", "LQ"))
     s, s2 = g("states"), g("next_states")
     F, v, sr = tw.evaluate_next(p, LP, q, LQ, s2, s2, g("rewards"), g("eps_eval"), hp)
     assert _rel(F, g("eval_next_features")) < 1e-12 and _rel(v, g("eval_next_value")) < 1e-12 and _rel(sr, g("eval_soft_reward")) < 1e-12
@@ -180,6 +171,11 @@ def test_twin_reproduces_the_reference_fixture(c):
         assert np.min(np.abs(kl - hp["kl_bound"])) > 1e-4          # every row far from the bound next to float32 error
     if c == 2:
         assert g("critic_metrics")[4] > hp["max_grad_norm"] and g("policy_metrics")[8] > hp["max_grad_norm"]
+    if c == 3:      # the regimes this case is there for
+        assert (fc["Hp"], fc["Hc"], fc["NB"], hp["v_max"]) == (128, 64, 151, 100.0) and -hp["v_min"] == hp["v_max"]
+        assert hp["policy_min_std"] > 0 and hp["auxiliary_loss_coefficient"] != 1.0
+        t = g("targets")
+        assert (t > hp["v_max"]).sum() >= 2 and (t < hp["v_min"]).sum() >= 2 and (t == hp["v_max"]).any() and (t == hp["v_min"]).any()
     assert _rel(tw.td_lambda(g("td_soft_rewards"), g("td_next_values"), g("td_terms"), g("td_truncs"), 0.99, 0.95), g("td_targets")) < 1e-12
 
 
