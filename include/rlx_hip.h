@@ -789,6 +789,59 @@ int rlx_reppo_update_f32(rlx_ctx*, const rlx_reppo_desc*, float* pparams, float*
                          int nr_minibatches, uint32_t key_io[2], int scheme, int64_t* opt_count_io, float lr, const rlx_reppo_hparams* hp,
                          float* metrics_out, void* stream);
 
+/* =================================== MPO =================================================
+ * Maximum a posteriori policy optimisation (rl_x/algorithms/mpo/pytorch): a C51-style critic whose target is the triangular
+ * projection of the target critic's distributions at S target-policy samples per next state, a non-parametric E-step over S
+ * samples per state, a decoupled Gaussian M-step with per-dimension KL terms, and Adam on the dual variables.
+ * Hidden widths: a multiple of 64, at most 512 (every layer has the same width); act_dim 1..64; nr_atoms 2..128;
+ * action_sampling_number 1..64; any batch B >= 1.  torch.nn.LayerNorm eps 1e-5.
+ * POLICY FLAT LAYOUT (policy.py:39-49), H = hidden: W1[policy_obs_dim, H], b1[H], ln_g[H], ln_b[H] | W2[H, H], b2 | W3[H, H], b3 |
+ *   head W[H, 2A], b[2A] (columns [0, A) = the `mean` Linear, [A, 2A) = the `std` Linear before the softplus).
+ * CRITIC FLAT LAYOUT (q_network.py:28-37): W1[critic_obs_dim + A, H] (rows [0, critic_obs_dim) = observation, then action), b1,
+ *   ln_g, ln_b | W2, b2 | W3, b3 | head W[H, nr_atoms], b[nr_atoms].
+ * DUALS (dual_variables.py:7-10): log_eta | log_alpha_mean[A] | log_alpha_stddev[A] | log_penalty_temperature  (2A + 2 floats).
+ * Observations: the FULL normalised state rows [., O]; pidx / cidx: DEVICE int32 policy / critic column indices, or NULL.
+ * Noise: threefry, key, subkey(s) = split(key) per call; rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) draws:
+ * eps_next = act [N, A] / the critic step's samples [S, B, A]; eps_cur = the actor step's samples [S, 2B, A].                   */
+typedef struct rlx_mpo_desc {
+  int32_t policy_obs_dim, critic_obs_dim, act_dim;
+  int32_t hidden;                /* nr_hidden_units (default_config.py: 256) */
+  int32_t nr_atoms;
+} rlx_mpo_desc;
+/* net 0: policy, 1: critic, 2: duals; -1 on a bad descriptor */
+int64_t rlx_mpo_param_count(const rlx_mpo_desc*, int net);
+
+typedef struct rlx_mpo_hparams { /* mpo/pytorch/default_config.py */
+  float gamma, v_min, v_max;
+  float max_grad_norm;           /* clip_grad_norm_ of all three optimisers (mpo.py:155, :235, :241); <= 0: none */
+  float epsilon_non_parametric, epsilon_parametric_mu, epsilon_parametric_sigma, epsilon_penalty;
+  float policy_init_scale, policy_min_scale;
+  float float_epsilon, min_log_temperature, min_log_alpha;
+  float adam_b1, adam_b2, adam_eps;  /* torch.optim.Adam defaults (mpo.py:101-103) */
+  int32_t action_sampling_number;    /* S: 1..64 */
+  int32_t action_clipping, action_rescaling;
+} rlx_mpo_hparams;
+
+/* Policy.sample_action / get_deterministic_action (policy.py:89-97) on obs [N, O]: action = mean + std eps [N, A] (what the ring
+ * stores), processed_action = scale_to_env(action): clamp to [-1, 1] (action_clipping), then low + 0.5 (p + 1)(high - low)
+ * (action_rescaling; low / high DEVICE float[A]).  deterministic: action = mean, key untouched.                                */
+int rlx_mpo_act_f32(rlx_ctx*, const rlx_mpo_desc*, const float* pparams, const float* obs, int O, const int32_t* pidx,
+                    uint32_t key_io[2], int scheme, float* action, float* processed_action, const float* low, const float* high, int64_t N,
+                    int deterministic, const rlx_mpo_hparams* hp, void* stream);
+/* ONE `update` (mpo.py:124-267) on the batch states, next_states [B, O], actions [B, A], rewards, dones, truncations,
+ * effective_n_steps [B]: the critic step (S target-policy samples per next state through the target critic, triangular projection,
+ * cross-entropy, clip_grad_norm_, Adam at agent_lr), the actor step on [states; next_states] (E-step weights, M-step losses, clip, Adam
+ * at agent_lr) and the dual step (Adam at dual_lr, clip, clamps).  The target networks are only read.  All three optimisers take
+ * Adam step number `step` (>= 1).  metrics_out: DEVICE float[17] in the order of mpo.py:389-407 = {critic_loss, actor_loss,
+ * dual_loss, loss_eta, loss_alpha, current_q_mean, eta, penalty_temperature, alpha_mean, alpha_std, mean_kl_mean, mean_kl_std,
+ * actor_grad_norm, critic_grad_norm, dual_grad_norm, std_min_mean, std_max_mean}.  No host synchronisation.                    */
+int rlx_mpo_update_f32(rlx_ctx*, const rlx_mpo_desc*, float* pparams, float* pm, float* pv, const float* target_pparams,
+                       float* qparams, float* qm, float* qv, const float* target_qparams, float* duals, float* dm, float* dv,
+                       const float* states, const float* next_states, int O, const int32_t* pidx, const int32_t* cidx,
+                       const float* actions, const float* rewards, const float* dones, const float* truncations,
+                       const float* effective_n_steps, int64_t B, uint32_t key_io[2], int scheme, int64_t step, float agent_lr,
+                       float dual_lr, const rlx_mpo_hparams* hp, float* metrics_out, void* stream);
+
 /* =================================== PPO + LSTM =======================================
  * Recurrent policy (rl_x/algorithms/ppo_lstm/flax_full_jit/policy.py:32-142, "concat" and "film" decoders):
  *   lstm_obs_encode / obs_encode: Dense(E)+LN+ELU on obs; OptimizedLSTMCell(H); LN+ELU on h;

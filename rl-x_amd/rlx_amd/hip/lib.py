@@ -88,6 +88,26 @@ class ReppoHparams(Structure):
         ("nr_kl_samples", c_int32)]
 
 
+class MpoDesc(Structure):
+    """rlx_mpo_desc: MPO's LayerNorm-tanh-ELU policy and critic (include/rlx_hip.h: flat layouts)."""
+    _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("hidden", c_int32),
+                ("nr_atoms", c_int32)]
+
+
+def mpo_desc(policy_obs_dim, critic_obs_dim, act_dim, hidden, nr_atoms):
+    d = MpoDesc()
+    d.policy_obs_dim, d.critic_obs_dim, d.act_dim = int(policy_obs_dim), int(critic_obs_dim), int(act_dim)
+    d.hidden, d.nr_atoms = int(hidden), int(nr_atoms)
+    return d
+
+
+class MpoHparams(Structure):
+    _fields_ = [(n, c_float) for n in ("gamma", "v_min", "v_max", "max_grad_norm", "epsilon_non_parametric", "epsilon_parametric_mu",
+                                       "epsilon_parametric_sigma", "epsilon_penalty", "policy_init_scale", "policy_min_scale",
+                                       "float_epsilon", "min_log_temperature", "min_log_alpha", "adam_b1", "adam_b2", "adam_eps")] + [
+        ("action_sampling_number", c_int32), ("action_clipping", c_int32), ("action_rescaling", c_int32)]
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -261,6 +281,11 @@ _SIGNATURES = {
     "rlx_reppo_update_f32": (c_int, [c_void_p, POINTER(ReppoDesc)] + [c_void_p] * 8 + [c_int] + [c_void_p] * 8 +
                              [c_int64, c_void_p, c_int, c_int, _U32P, c_int, POINTER(c_int64), c_float, POINTER(ReppoHparams), c_void_p,
                               c_void_p]),
+    "rlx_mpo_param_count": (c_int64, [POINTER(MpoDesc), c_int]),
+    "rlx_mpo_act_f32": (c_int, [c_void_p, POINTER(MpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_int, POINTER(MpoHparams), c_void_p]),
+    "rlx_mpo_update_f32": (c_int, [c_void_p, POINTER(MpoDesc)] + [c_void_p] * 13 + [c_int, c_void_p, c_void_p] + [c_void_p] * 5 +
+                           [c_int64, _U32P, c_int, c_int64, c_float, c_float, POINTER(MpoHparams), c_void_p, c_void_p]),
     "rlx_dist_overflow_count": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "rlx_ppo_dist_prefetch": (c_int, [c_void_p, _U32P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rlx_ppo_update_dist_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p,
@@ -1041,6 +1066,33 @@ class Ctx:
             _ptr(nf, f), _ptr(te, f), _ptr(tr, f), int(s.shape[0]), _ptr(perm, i32), int(perm.shape[0]), int(nr_minibatches), k, scheme,
             ctypes.byref(cnt), float(lr), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_reppo_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    # ---- MPO (rl_x/algorithms/mpo/pytorch)
+    def mpo_param_count(self, desc, net):
+        """net 0: policy, 1: critic, 2: duals"""
+        return int(self.lib.rlx_mpo_param_count(ctypes.byref(desc), int(net)))
+
+    def mpo_act(self, desc, pparams, obs, key, action, processed, hp, low=None, high=None, deterministic=False, pidx=None,
+                scheme=THREEFRY_PARTITIONABLE):
+        """Policy.sample_action / get_deterministic_action -> new key"""
+        f, k = self.torch.float32, _key_arr(key)
+        _check(self.lib.rlx_mpo_act_f32(self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(obs, f), int(obs.shape[1]),
+                                        _ptr(pidx, self.torch.int32, True), k, scheme, _ptr(action, f), _ptr(processed, f),
+                                        _ptr(low, f, True), _ptr(high, f, True), int(obs.shape[0]), int(bool(deterministic)),
+                                        ctypes.byref(hp), _stream()), "rlx_mpo_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def mpo_update(self, desc, nets, batch, key, step, agent_lr, dual_lr, hp, metrics_out, pidx=None, cidx=None,
+                   scheme=THREEFRY_PARTITIONABLE):
+        """nets = (pparams, pm, pv, target_pparams, qparams, qm, qv, target_qparams, duals, dm, dv);
+        batch = (states, next_states, actions, rewards, dones, truncations, effective_n_steps) -> new key"""
+        f, i32, k = self.torch.float32, self.torch.int32, _key_arr(key)
+        s, s2, a, r, d, tr, n = batch
+        _check(self.lib.rlx_mpo_update_f32(
+            self.h, ctypes.byref(desc), *(_ptr(x, f) for x in nets), _ptr(s, f), _ptr(s2, f), int(s.shape[1]), _ptr(pidx, i32, True),
+            _ptr(cidx, i32, True), _ptr(a, f), _ptr(r, f), _ptr(d, f), _ptr(tr, f), _ptr(n, f), int(s.shape[0]), k, scheme, int(step),
+            float(agent_lr), float(dual_lr), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_mpo_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
