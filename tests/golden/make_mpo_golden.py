@@ -17,7 +17,11 @@ Cases (each batch has terminations, truncations and effective n-steps 1..4):
   2 action_clipping = False;                                      3 policy_init_scale 3 (samples leave [-1, 1]), max_grad_norm
     small enough that all three clips act;                        4 duals at their edges: log_eta 25 (softplus' linear branch),
     log_alpha_stddev -17.99995 with target == online policy (the step pushes it below -18: the clamp acts);
-  5 policy / critic observation index sets of different widths (6 and 10 of 12 columns)."""
+  5 policy / critic observation index sets of different widths (6 and 10 of 12 columns);
+  6 past the other cases' shapes: obs 10, act 5, hidden 128, 101 atoms (odd, past one wave), B 13, S 7, an asymmetric support
+    [-20, 60] with rewards past both edges, and TWO consecutive `update` calls: the three Adam optimisers carry their state from
+    the first into the second (step 2, non-zero moments), fresh noise per call, the same batch.  The second call's outputs are
+    stored under c6_u2_* (the sampled networks at the first call's positions: values and norms only)."""
 import os
 import sys
 import types
@@ -40,6 +44,8 @@ CASES = (
     (8, 3, 64, 51, 16, 6, 44, 84, dict(policy_init_scale=3.0, max_grad_norm=1e-3)),
     (8, 3, 64, 51, 16, 6, 45, None, dict(init_log_eta=25.0, init_log_alpha_stddev=-17.99995)),
     (12, 2, 64, 51, 12, 4, 46, 86, dict(pidx=(0, 2, 3, 5, 8, 11), cidx=(1, 2, 3, 4, 5, 6, 7, 9, 10, 11))),
+    (10, 5, 128, 101, 13, 7, 47, 87, dict(v_min=-20.0, v_max=60.0, reward_scale=20.0, reward_edges=(75.0, -35.0, 60.5, -20.5),
+                                          n_updates=2)),
 )
 # the settings a case may override (every case stores all of them)
 CASE_KEYS = ("v_min", "v_max", "action_clipping", "policy_init_scale", "max_grad_norm", "init_log_eta", "init_log_alpha_stddev")
@@ -147,6 +153,11 @@ def make_mpo():
             truncs = (torch.rand(B, generator=g) < 0.5).to(dtype) * dones       # a truncation is also a done (replay_buffer.py)
             nsteps = torch.randint(1, 5, (B,), generator=g).to(dtype)
             dones[:2], truncs[:2], nsteps[:4] = torch.tensor([1.0, 1.0]), torch.tensor([0.0, 1.0]), torch.tensor([1.0, 2.0, 3.0, 4.0])
+            if "reward_edges" in over:          # rows 4.. (not done): targets past both edges of the support
+                e = over["reward_edges"]
+                rewards[4:4 + len(e)] = torch.tensor(e)
+                dones[4:4 + len(e)] = 0.0
+                truncs[4:4 + len(e)] = 0.0
             eps_c, eps_a, eps_act = r32(S, B, A), r32(S, 2 * B, A), r32(B, A)
             queue = []
 
@@ -188,23 +199,34 @@ def make_mpo():
                 a_s, pa_s = P.sample_action(states)
                 pa_d = P.get_deterministic_action(states)
             out.update({k + "act_mean": mean, k + "act_std": std, k + "act_sample": a_s, k + "act_sample_proc": pa_s, k + "act_det_proc": pa_d})
-            # --- one update (mpo.py:124-267)
-            queue.extend([eps_c, eps_a])
-            met = update(states, next_states, actions, rewards, dones, truncs, nsteps)
-            assert not queue
-            # the closure returns them in the order of mpo.py:249-267; stored in the order of the logged dict (mpo.py:389-407)
-            met = [float(x.detach()) for x in met]
-            out[k + "metrics"] = np.array([met[i] for i in (0, 1, 2, 8, 9, 3, 4, 5, 6, 7, 10, 11, 12, 13, 14, 15, 16)])
-            pm_, qm_ = policy_modules(P), critic_modules(Q)
-            for name, mods, opt, sd in (("p", pm_, me.actor_optimizer, 500), ("q", qm_, me.critic_optimizer, 600)):
-                out.update(_sampled(k + name + "_after", flat(mods, lambda t: t), sd + case))
-                out.update(_sampled(k + name + "m_after", adam_flat(opt, mods, "exp_avg"), sd + 10 + case))
-                out.update(_sampled(k + name + "v_after", adam_flat(opt, mods, "exp_avg_sq"), sd + 20 + case))
-            dl = [duals.log_eta, duals.log_alpha_mean, duals.log_alpha_stddev, duals.log_penalty_temperature]
-            st = me.dual_optimizer.state
-            out[k + "duals_after"] = torch.cat([x.detach().reshape(-1) for x in dl]).numpy()
-            for key in ("exp_avg", "exp_avg_sq"):
-                out[k + "duals_" + key] = torch.cat([(st[x][key] if x in st else torch.zeros_like(x)).reshape(-1) for x in dl]).numpy()
+            # --- one update (mpo.py:124-267); a second one with fresh noise when the case asks for it
+            for call in range(over.get("n_updates", 1)):
+                u = k if call == 0 else k + "u2_"
+                if call == 0:
+                    ec, ea = eps_c, eps_a
+                else:
+                    ec, ea = r32(S, B, A), r32(S, 2 * B, A)
+                    out.update({u + "eps_c": ec, u + "eps_a": ea})
+                queue.extend([ec, ea])
+                met = update(states, next_states, actions, rewards, dones, truncs, nsteps)
+                assert not queue
+                # the closure returns them in the order of mpo.py:249-267; stored in the order of the logged dict (mpo.py:389-407)
+                met = [float(x.detach()) for x in met]
+                out[u + "metrics"] = np.array([met[i] for i in (0, 1, 2, 8, 9, 3, 4, 5, 6, 7, 10, 11, 12, 13, 14, 15, 16)])
+                pm_, qm_ = policy_modules(P), critic_modules(Q)
+                for name, mods, opt, sd in (("p", pm_, me.actor_optimizer, 500), ("q", qm_, me.critic_optimizer, 600)):
+                    for n_, vec, sd_ in ((name + "_after", flat(mods, lambda t: t), sd + case),
+                                         (name + "m_after", adam_flat(opt, mods, "exp_avg"), sd + 10 + case),
+                                         (name + "v_after", adam_flat(opt, mods, "exp_avg_sq"), sd + 20 + case)):
+                        smp = _sampled(u + n_, vec, sd_)
+                        if call:        # the same positions as the first call's: the indices are stored once
+                            assert np.array_equal(smp.pop(u + n_ + "_idx"), out[k + n_ + "_idx"])
+                        out.update(smp)
+                dl = [duals.log_eta, duals.log_alpha_mean, duals.log_alpha_stddev, duals.log_penalty_temperature]
+                st = me.dual_optimizer.state
+                out[u + "duals_after"] = torch.cat([x.detach().reshape(-1) for x in dl]).numpy()
+                for key in ("exp_avg", "exp_avg_sq"):
+                    out[u + "duals_" + key] = torch.cat([(st[x][key] if x in st else torch.zeros_like(x)).reshape(-1) for x in dl]).numpy()
             torch.randn, torch.randn_like = raw_randn, raw_randn_like
     finally:
         torch.randn, torch.randn_like = raw_randn, raw_randn_like

@@ -8,7 +8,13 @@ import torch.nn.functional as F
 
 D = torch.float64
 SOFTPLUS0 = float(np.float32(np.log(2.0)))        # float(F.softplus(torch.zeros(1))) of the float32 module (policy.py:51)
-LOG_2PI = float(torch.log(torch.tensor(2.0 * np.pi, dtype=torch.float32)))    # mpo.py:115, a float32 tensor
+# mpo.py:114-115 compute log(S) and log(2 pi) as float32 tensors.  The twin rounds numpy's float64 log to float32 instead of
+# calling torch's float32 log, which is one ulp off for some arguments on some CPU builds (log 7 on one of ours).
+LOG_2PI = float(np.float32(np.log(2.0 * np.pi)))
+
+
+def log_f32(x):
+    return float(np.float32(np.log(float(x))))
 METRICS = ("loss/critic_loss", "loss/actor_loss", "loss/dual_loss", "loss/loss_eta", "loss/loss_alpha", "q/current_q_mean", "dual/eta",
            "dual/penalty_temperature", "dual/alpha_mean", "dual/alpha_std", "kl/mean_kl_mean", "kl/mean_kl_std",
            "gradients/actor_grad_norm", "gradients/critic_grad_norm", "gradients/dual_grad_norm", "policy/std_min_mean",
@@ -130,7 +136,7 @@ def update(st, LP, LQ, batch, eps_c, eps_a, hp, step, pidx=None, cidx=None):
     S, B, A, NA = hp["action_sampling_number"], s.shape[0], LP["out"] // 2, LQ["out"]
     clip, feps = bool(hp["action_clipping"]), hp["float_epsilon"]
     z = torch.linspace(hp["v_min"], hp["v_max"], NA, dtype=D)
-    log_s = float(torch.log(torch.tensor(S, dtype=torch.float32)))
+    log_s = log_f32(S)
     tp, tq = _t(st["tp"]), _t(st["tq"])
     # ---- critic step (mpo.py:125-156)
     with torch.no_grad():

@@ -1,66 +1,20 @@
 """GPU: MPO (mpo.hip) against the reference fixture (tests/golden/mpo_reference.npz) and the float64 twin (tests/mpo_twin.py): acting
 and one whole update per fixture case, the twin at the reference defaults (obs 48, act 12, B 256 and 4096, S 20, hidden 256, 51
 atoms), bit-identical repeats, the refusals just outside the envelope, an ill-conditioned temperature, and the plugin end to end.
-Tolerances: 1e-5 relative (L2 per vector); second Adam moments 5e-5 (float32's 1 - b2); the expected-q metric with a floor of
-max|v| / 10 (its value is a difference of atoms that large)."""
+A fixture case with a second `update` call is also checked at step 2, started from the twin's state after the first call.
+Tolerances (tests/mpo_cases.py): 1e-5 relative (L2 per vector); second Adam moments 5e-5 (float32's 1 - b2); the expected-q
+metric with a floor of max|v| / 10 (its value is a difference of atoms that large)."""
 import numpy as np
 import pytest
 import torch
 
 import mpo_cases
 import mpo_twin as tw
-from rlx_amd.hip import MpoHparams, mpo_desc
+from mpo_cases import Run, _check_metrics, _hp, _rel, _t
+from rlx_amd.hip import mpo_desc
 from rlx_amd.hip import lib as L
 
 pytestmark = pytest.mark.gpu
-
-
-def _t(x, dev, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype))).to(dev)
-
-
-def _rel(got, exp):
-    return np.linalg.norm(np.asarray(got, np.float64) - exp) / max(np.linalg.norm(exp), 1e-30)
-
-
-def _hp(h):
-    hp = MpoHparams()
-    for k in ("gamma", "v_min", "v_max", "max_grad_norm", "epsilon_non_parametric", "epsilon_parametric_mu", "epsilon_parametric_sigma",
-              "epsilon_penalty", "policy_init_scale", "policy_min_scale", "float_epsilon", "min_log_temperature", "min_log_alpha"):
-        setattr(hp, k, float(h[k]))
-    hp.adam_b1, hp.adam_b2, hp.adam_eps = 0.9, 0.999, 1e-8
-    hp.action_sampling_number, hp.action_clipping, hp.action_rescaling = int(h["action_sampling_number"]), int(bool(h["action_clipping"])), int(bool(h["action_rescaling"]))
-    return hp
-
-
-class Run:
-    """one rlx_mpo_update_f32 call on device copies of a twin state"""
-
-    def __init__(self, ctx, dev, desc, st, batch, hp_dict, eps=None, pidx=None, cidx=None, key=(0, 7), step=1):
-        self.nets = tuple(_t(st[k], dev) for k in ("p", "pm", "pv", "tp", "q", "qm", "qv", "tq", "d", "dm", "dv"))
-        self.met = torch.zeros(17, device=dev)
-        hp = _hp(hp_dict)
-        b = tuple(_t(x, dev) for x in batch)
-        pi = None if pidx is None else _t(pidx, dev, np.int32)
-        ci = None if cidx is None else _t(cidx, dev, np.int32)
-        self.eps = None if eps is None else (_t(eps[0], dev), _t(eps[1], dev))     # kept alive: the library holds the pointers
-        if eps is not None:
-            ctx.dbg_set_sac_noise(*self.eps)
-        try:
-            self.key = ctx.mpo_update(desc, self.nets, b, np.array(key, np.uint32), step, hp_dict["agent_learning_rate"],
-                                      hp_dict["dual_learning_rate"], hp, self.met, pidx=pi, cidx=ci)
-        finally:
-            ctx.dbg_set_sac_noise(None, None)
-        torch.cuda.synchronize()
-        self.out = dict(zip(("p", "pm", "pv", "tp", "q", "qm", "qv", "tq", "d", "dm", "dv"), (x.cpu().numpy().astype(np.float64) for x in self.nets)))
-        self.metrics = self.met.cpu().numpy().astype(np.float64)
-
-
-def _check_metrics(got, ref, vmax):
-    floor = np.ones(17)
-    floor[5] = max(vmax / 10.0, 1.0)
-    bad = [(i, tw.METRICS[i], got[i], ref[i]) for i in range(17) if abs(got[i] - ref[i]) > 1e-5 * max(abs(ref[i]), floor[i])]
-    assert not bad, bad
 
 
 @pytest.mark.parametrize("c", range(mpo_cases.n_cases()))
@@ -107,6 +61,27 @@ def test_update_matches_the_reference(ctx, dev, c):
     A = fc.A
     assert r.out["d"][1:1 + A].tobytes() == fc.state["d"][1:1 + A].astype(np.float32).astype(np.float64).tobytes()   # no gradient
     assert np.array_equal(r.out["tp"], fc.state["tp"]) and np.array_equal(r.out["tq"], fc.state["tq"])             # read only
+
+
+@pytest.mark.parametrize("c", mpo_cases.two_call_cases())
+def test_second_update_matches_the_reference(ctx, dev, c):
+    """the fixture's second `update` (step 2, the reference's Adam moments and duals carried over), teacher-forced: the library
+    starts from the twin's state after the first call, so the bars measure the kernels, not two steps of drift"""
+    fc = mpo_cases.load(c)
+    sc = fc.second
+    desc = mpo_desc(fc.Op, fc.Oc, fc.A, fc.H, fc.NA)
+    pidx, cidx = fc.indices()
+    st1, _, _ = tw.update(fc.state, fc.LP, fc.LQ, fc.batch, fc.eps_c, fc.eps_a, fc.h, 1, pidx, cidx)
+    assert np.any(st1["pm"] != 0) and np.any(st1["qv"] != 0) and np.any(st1["dm"] != 0)
+    r = Run(ctx, dev, desc, st1, fc.batch, fc.h, (sc.eps_c, sc.eps_a), pidx, cidx, step=2)
+    _check_metrics(r.metrics, sc.metrics, max(abs(fc.h["v_min"]), abs(fc.h["v_max"])))
+    for name, key, tol in (("p_after", "p", 1e-5), ("pm_after", "pm", 1e-5), ("pv_after", "pv", 5e-5), ("q_after", "q", 1e-5),
+                           ("qm_after", "qm", 1e-5), ("qv_after", "qv", 5e-5)):
+        idx, val, _ = sc.sampled(name)
+        assert _rel(r.out[key][idx], val) < tol, (name, _rel(r.out[key][idx], val))
+    assert _rel(r.out["d"], sc.duals) < 1e-5
+    assert _rel(r.out["dm"], sc.dm) < 1e-5 and _rel(r.out["dv"], sc.dv) < 5e-5
+    mpo_cases.check_dual_step(r.out["d"], sc.duals, st1["d"])        # step 2's bias corrections
 
 
 def _defaults_case(B, seed, A=12, O=48):

@@ -1,5 +1,6 @@
 """CPU: the float64 MPO twin (tests/mpo_twin.py) against the reference fixture (tests/golden/mpo_reference.npz, outputs of the
-reference's own modules and `update` closure), the reference quirks the fixture pins, and the plugin's registration."""
+reference's own modules and `update` closure; one case runs two consecutive calls), the reference quirks the fixture pins, and the
+plugin's registration."""
 import os
 
 import numpy as np
@@ -51,7 +52,7 @@ def test_twin_reproduces_the_reference_fixture(c):
     _, pd = tw.act(fc.state["p"], fc.LP, fc.batch[0][:, fc.pidx], None, fc.h, fc.low, fc.high, deterministic=True)
     assert _rel(pd, z[k + "act_det_proc"]) < 1e-12
     # one update
-    pidx, cidx = (fc.pidx, fc.cidx) if fc.full_obs else (None, None)
+    pidx, cidx = fc.indices()
     new, met, _ = tw.update(fc.state, fc.LP, fc.LQ, fc.batch, fc.eps_c, fc.eps_a, fc.h, 1, pidx, cidx)
     ref = z[k + "metrics"]
     assert np.all(np.abs(met - ref) <= 1e-12 * np.maximum(np.abs(ref), 1.0)), (met, ref)
@@ -61,6 +62,28 @@ def test_twin_reproduces_the_reference_fixture(c):
         assert abs(np.linalg.norm(new[key]) - norm) <= 1e-12 * max(norm, 1e-30), name
     assert _rel(new["d"], z[k + "duals_after"]) < 1e-12
     assert _rel(new["dm"], z[k + "duals_exp_avg"]) < 1e-12 and _rel(new["dv"], z[k + "duals_exp_avg_sq"]) < 1e-12
+
+
+@pytest.mark.parametrize("c", mpo_cases.two_call_cases())
+def test_twin_reproduces_the_second_update(c):
+    """the fixture's second `update` call (step 2; the reference's three Adam optimisers carry their moments over, the duals
+    their values): the twin from its own state after the first call"""
+    fc = mpo_cases.load(c)
+    sc = fc.second
+    pidx, cidx = fc.indices()
+    st1, _, _ = tw.update(fc.state, fc.LP, fc.LQ, fc.batch, fc.eps_c, fc.eps_a, fc.h, 1, pidx, cidx)
+    new, met, _ = tw.update(st1, fc.LP, fc.LQ, fc.batch, sc.eps_c, sc.eps_a, fc.h, 2, pidx, cidx)
+    assert np.all(np.abs(met - sc.metrics) <= 1e-12 * np.maximum(np.abs(sc.metrics), 1.0)), (met, sc.metrics)
+    for name, key in (("p_after", "p"), ("pm_after", "pm"), ("pv_after", "pv"), ("q_after", "q"), ("qm_after", "qm"), ("qv_after", "qv")):
+        idx, val, norm = sc.sampled(name)
+        assert _rel(new[key][idx], val) < 1e-12, name
+        assert abs(np.linalg.norm(new[key]) - norm) <= 1e-12 * max(norm, 1e-30), name
+        assert not np.array_equal(val, fc.sampled(name)[1]), name                      # the second call moved it
+    assert _rel(new["d"], sc.duals) < 1e-12
+    assert _rel(new["dm"], sc.dm) < 1e-12 and _rel(new["dv"], sc.dv) < 1e-12
+    # step 2 is not step 1 again: the twin at step 1 from the same state misses the fixture
+    wrong, _, _ = tw.update(st1, fc.LP, fc.LQ, fc.batch, sc.eps_c, sc.eps_a, fc.h, 1, pidx, cidx)
+    assert _rel(wrong["d"], sc.duals) > 1e-9 and _rel(wrong["p"][sc.sampled("p_after")[0]], sc.sampled("p_after")[1]) > 1e-9
 
 
 @pytest.mark.parametrize("c", range(mpo_cases.n_cases()))
@@ -96,6 +119,13 @@ def test_edge_cases_are_exercised():
     assert r.max() > c1.h["v_max"] and r.min() < c1.h["v_min"]                            # targets past both edges
     c5 = mpo_cases.load(5)
     assert c5.Op != c5.Oc and c5.Op < c5.O
+    c6 = mpo_cases.load(6)         # past the other cases' shapes, an asymmetric support, two calls
+    assert (c6.H, c6.NA, c6.A, c6.B, c6.S) == (128, 101, 5, 13, 7) and c6.NA > 64 and c6.B % 4 != 0
+    assert c6.h["v_min"] == -20.0 and c6.h["v_max"] == 60.0
+    r, d = c6.batch[3], c6.batch[4]
+    assert (r > c6.h["v_max"]).any() and (r < c6.h["v_min"]).any() and (d[r > c6.h["v_max"]] == 0).all()
+    assert c6.second is not None and mpo_cases.two_call_cases() == [6]
+    assert all(mpo_cases.load(c).second is None for c in range(6))
     for c in range(mpo_cases.n_cases()):
         fc = mpo_cases.load(c)
         d, tr, n = fc.batch[4], fc.batch[5], fc.batch[6]
