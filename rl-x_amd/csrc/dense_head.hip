@@ -1,0 +1,232 @@
+// dense_head.hip -- the kernels every network pass of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip shares (net_pass.h declares
+// their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat
+// and the N(0, 1) noise block.
+#include "net_pass.h"
+
+namespace rlx {
+
+// Dense heads (nr_atoms = 101 or 2 * act_dim outputs: widths the float4-tiled GEMM stages do not take -- their contraction and
+// leading dimensions have to be multiples of four).  K <= 768 inputs, any N; small next to the trunk, so plain kernels.
+// out[M, N] = H[M, K] @ W[K, N] + b: a workgroup of 128 threads per 8 rows x 128 columns, thread <-> output column.  The H values
+// of a row are the same for every lane: their addresses are wave-uniform, so they arrive through the scalar cache as SGPR operands
+// of the FMAs -- no LDS, no barrier, eight W loads in flight per thread.  (With H in LDS the kernel was LDS-issue bound: eight
+// broadcast reads per k and wave; 22 -> 34 us when the W tiles went through LDS as well.)  One ascending fmaf chain per output.
+__global__ __launch_bounds__(128) void k_fs_head_fwd(const float* __restrict__ H, const float* __restrict__ W, const float* __restrict__ b,
+                                                     float* __restrict__ out, int64_t M, int K, int N) {
+  const int64_t r0 = (int64_t)blockIdx.x * 8;
+  const int n = blockIdx.y * 128 + threadIdx.x;
+  const int nc = n < N ? n : N - 1;                      // (idle lanes compute a copy of the last column)
+  const float* hr[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) hr[r] = H + (r0 + r < M ? r0 + r : M - 1) * K;
+  float acc[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+  int k = 0;
+  for (; k + 8 <= K; k += 8) {
+    float w[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) w[u] = W[(int64_t)(k + u) * N + nc];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc[r] = fmaf(hr[r][k + u], w[u], acc[r]);
+    }
+  }
+  for (; k < K; ++k) {
+    const float w = W[(int64_t)k * N + nc];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = fmaf(hr[r][k], w, acc[r]);
+  }
+  if (n < N) {
+    const float bv = b[n];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      if (r0 + r < M) out[(r0 + r) * N + n] = acc[r] + bv;
+  }
+}
+// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k.  RELU_MASK (FastTD3): H_dH
+// holds the ReLU output H on entry and dH * (H > 0) on exit (each entry is read by the thread that overwrites it).
+template <bool RELU_MASK>
+__global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d, const float* __restrict__ W, float* __restrict__ dH,
+                                                    int64_t M, int K, int N) {
+  extern __shared__ float s_d[];   // [8][N]
+  const int64_t r0 = (int64_t)blockIdx.x * 8;
+  {
+    const int64_t left = (M - r0) * N;
+    lds_stage<256, float>(s_d, d + r0 * N, 8 * N, left < 8 * N ? (int)left : 8 * N, 0.f);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += 256) {
+    float acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+    const float* wr = W + (int64_t)k * N;
+    for (int n = 0; n < N; ++n) {
+      const float w = wr[n];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) acc[r] = fmaf(s_d[r * N + n], w, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+      if (r0 + r < M) {
+        if (RELU_MASK) acc[r] = dH[(r0 + r) * K + k] > 0.f ? acc[r] : 0.f;
+        dH[(r0 + r) * K + k] = acc[r];
+      }
+  }
+}
+// partial[s][K * N + N]: dW = H^T d and db = column sums of d over the rows [s * rows, (s + 1) * rows) -- summed in row order;
+// the slabs are added in slab order by the reduction kernel.  blockIdx.y = slab, thread <-> (k, n) pairs.
+__global__ __launch_bounds__(256) void k_fs_head_dw(const float* __restrict__ H, const float* __restrict__ d, float* __restrict__ partial,
+                                                    int64_t M, int K, int N, int rows, int64_t PS, int boff) {
+  const int64_t r0 = (int64_t)blockIdx.y * rows;
+  const int64_t r1 = r0 + rows < M ? r0 + rows : M;
+  float* out = partial + (int64_t)blockIdx.y * PS;
+  const int total = K * N + N;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
+    float acc = 0.f;
+    if (e < K * N) {
+      const int k = e / N, n = e - k * N;
+      for (int64_t r = r0; r < r1; ++r) acc = fmaf(H[r * K + k], d[r * N + n], acc);
+    } else {
+      const int n = e - K * N;
+      for (int64_t r = r0; r < r1; ++r) acc += d[r * N + n];
+    }
+    out[e < K * N ? e : boff + (e - K * N)] = acc;
+  }
+}
+
+// The same partials from a register tile: workgroup = slab, thread = 8 k x NJ n outputs (k = 8 tk .. 8 tk + 7, n = tn + TN j),
+// 16-row chunks of H and d staged in LDS; every output is one ascending fmaf chain over the slab's rows like above.  (The
+// per-output loop above re-reads H and d from L2 for every output: 134 us at [8192, 192] x [8192, 101]; this one 10.)
+// Slab layout: [K * N] dW, then db at float `boff` (both 16-byte aligned when the caller pads: vector path of the reduction).
+template <int NJ>
+__global__ __launch_bounds__(256) void k_fs_head_dw_tiled(const float* __restrict__ H, const float* __restrict__ d,
+                                                          float* __restrict__ partial, int64_t M, int K, int N, int rows, int TK, int TN,
+                                                          int64_t PS, int boff) {
+  extern __shared__ __attribute__((aligned(16))) float s_hd[];
+  constexpr int RC = 16;
+  float* Hs = s_hd;              // [RC][K]
+  float* Ds = s_hd + RC * K;     // [RC][N]
+  const int tk = threadIdx.x / TN, tn = threadIdx.x - tk * TN;
+  const bool on = tk < TK;
+  float acc[8][NJ], bsum[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    bsum[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i][j] = 0.f;
+  }
+  const int64_t r0 = (int64_t)blockIdx.x * rows;
+  const int64_t r1 = r0 + rows < M ? r0 + rows : M;
+  for (int64_t c0 = r0; c0 < r1; c0 += RC) {
+    const int nr = (int)(r1 - c0 < RC ? r1 - c0 : RC);
+    __syncthreads();
+    lds_stage<256, float>(Hs, H + c0 * K, RC * K, nr * K, 0.f);
+    lds_stage<256, float>(Ds, d + c0 * N, RC * N, nr * N, 0.f);
+    __syncthreads();
+    if (on) {
+#pragma unroll 2
+      for (int r = 0; r < RC; ++r) {
+        const float4 h0 = *reinterpret_cast<const float4*>(Hs + r * K + 8 * tk);
+        const float4 h1 = *reinterpret_cast<const float4*>(Hs + r * K + 8 * tk + 4);
+        const float hv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int n = tn + TN * j;
+          const float dv = n < N ? Ds[r * N + n] : 0.f;
+          bsum[j] += dv;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[i][j] = fmaf(hv[i], dv, acc[i][j]);
+        }
+      }
+    }
+  }
+  if (!on) return;
+  float* out = partial + (int64_t)blockIdx.x * PS;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int n = tn + TN * j;
+    if (n >= N) continue;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[(int64_t)(8 * tk + i) * N + n] = acc[i][j];
+    if (tk == 0) out[boff + n] = bsum[j];
+  }
+}
+
+// [obs | action] rows of a critic input (row stride ld; the action columns may be filled later by k_fs_sample)
+__global__ __launch_bounds__(256) void k_fs_concat(const float* __restrict__ obs, int Oc, const float* __restrict__ act, int A,
+                                                   float* __restrict__ out, int ld, int64_t M) {
+  const int64_t n = M * ld;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / ld;
+    const int c = (int)(i - r * ld);
+    out[i] = c < Oc ? obs[r * Oc + c] : (act && c < Oc + A ? act[r * A + (c - Oc)] : 0.f);
+  }
+}
+
+// N(0, 1) draws of an [n] block: normal(bits(key, i of n))
+__global__ __launch_bounds__(256) void k_normal_noise(float* __restrict__ out, int64_t n, uint32_t k0, uint32_t k1, int scheme) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = normal_from_bits(random_bits_at(k0, k1, (uint64_t)i, (uint64_t)n, scheme));
+}
+
+int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st) {
+  hipLaunchKernelGGL(k_fs_head_fwd, dim3(div_up(M, 8), div_up(N, 128)), dim3(128), 0, st, H, W, b, out, M, K, N);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
+                bool relu_mask) {
+  if (gW) {
+    const int boff = (K * N + 3) & ~3;
+    const int64_t PS = boff + ((N + 3) & ~3);
+    const int TK = K / 8, TN = TK > 0 && TK <= 256 ? 256 / TK : 0;
+    const int nj = TN ? div_up(N, TN) : 99;
+    const bool tiled = K % 8 == 0 && nj <= 12 && (size_t)16 * (K + N) * sizeof(float) <= 48 * 1024;
+    const int rows = tiled ? (M >= 8192 ? 32 : 64) : 128, S = div_up(M, rows);   // (>= 256 slabs: one per CU)
+    float* part = stage_alloc(ctx, (size_t)S * PS);
+    if (!part) return RLX_ENOMEM;
+    if (tiled) {
+      const size_t lds = (size_t)16 * (K + N) * sizeof(float);
+#define FS_DW_TILED(NJ) hipLaunchKernelGGL(k_fs_head_dw_tiled<NJ>, dim3(S), dim3(256), lds, st, (const float*)H_dH, d, part, M, K, N, rows, TK, TN, PS, boff)
+      if (nj <= 2) FS_DW_TILED(2);
+      else if (nj <= 4) FS_DW_TILED(4);
+      else if (nj <= 8) FS_DW_TILED(8);
+      else FS_DW_TILED(12);
+#undef FS_DW_TILED
+    } else {
+      int gx = div_up(K * N + N, 256);
+      if (gx > 64) gx = 64;
+      hipLaunchKernelGGL(k_fs_head_dw, dim3(gx, S), dim3(256), 0, st, (const float*)H_dH, d, part, M, K, N, rows, PS, boff);
+    }
+    RLX_LAUNCH_CHECK();
+    ReduceTable tab;
+    tab.n = 0;
+    tab.seg[tab.n++] = ReduceSeg{part, gW, (int64_t)K * N, PS, S, 0, 1.f, 0.f, 1};
+    tab.seg[tab.n++] = ReduceSeg{part + boff, gb, (int64_t)N, PS, S, 0, 1.f, 0.f, 1};
+    const int rc = stage_reduce(ctx, tab, nullptr, nullptr, st);
+    if (rc) return rc;
+  }
+  if (relu_mask) hipLaunchKernelGGL(k_fs_head_dx<true>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
+  else hipLaunchKernelGGL(k_fs_head_dx<false>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st) {
+  int grid = div_up(M * ld, 256);
+  if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(k_fs_concat, dim3(grid), dim3(256), 0, st, obs, Oc, act, A, out, ld, M);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int scheme, hipStream_t st) {
+  hipLaunchKernelGGL(k_normal_noise, dim3(elem_grid(n)), dim3(256), 0, st, out, n, k0, k1, scheme);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+}  // namespace rlx

@@ -3,24 +3,17 @@
 //
 // Networks (policy.py:46-57, q_network.py:27-38): every hidden layer is Dense -> LayerNorm (torch: eps 1e-5) -> SiLU, then a
 // Dense head -- rlx_lnmlp_desc.  They are composed from the library's GEMM stages (launch_gemm_fwd / stage_dx / stage_dw: the
-// exact-fp32 MFMA engine for the forward and input-gradient products -- no weight images are registered here --, the
-// split-operand weight-gradient kernel for batches >= 4096 rows) and the row-wise LayerNorm + activation kernels of ln_kernels.h
-// (k_ln_act_wide: widths up to 768, eps argument, SiLU' from the recomputed pre-activation).  CPU twin: oracle/fastsac.py,
+// exact-fp32 MFMA engine below 4096 rows, the split-operand engine from there on -- trunk_images, net_pass.h), the dense-head
+// kernels of dense_head.hip and the row-wise LayerNorm + activation kernels of ln_kernels.h (k_ln_act_wide: widths up to 768,
+// eps argument, SiLU' from the recomputed pre-activation).  Arena, grids, key splitting and the backward tails shared with
+// fasttd3.hip, reppo.hip and mpo.hip are in net_pass.h.  CPU twin: oracle/fastsac.py,
 // pinned by outputs of the reference's own modules and closures (tests/golden/reference_fastsac.npz).
 //
 // Noise: the reference draws with torch's CUDA generator (Normal.rsample), which no other implementation reproduces; the
 // library uses its counter RNG (threefry, the key split per call like rlx_sac_*), and rlx_dbg_set_sac_noise injects a given
 // eps for parity tests.
-#include "gemm_bx.h"
 #include "ln_kernels.h"
-#include "mlp.h"
-#include "fs_sched.h"
-
-extern "C" int rlx_c51_critic_loss_f32(rlx_ctx* ctx, const float* q1_logits, const float* q2_logits, const float* q1_next_logits,
-                                       const float* q2_next_logits, const float* rewards, const float* dones,
-                                       const float* truncations, const float* effective_n_steps, const float* next_log_probs,
-                                       const float* log_alpha, int64_t B, int nr_atoms, float gamma, float v_min, float v_max,
-                                       int clipped_double_q, float* d_q1_logits, float* d_q2_logits, float* out4, void* stream);
+#include "net_pass.h"
 
 namespace rlx {
 
@@ -66,57 +59,14 @@ static LnLayout ln_layout(const rlx_lnmlp_desc& d) {
 
 struct LnBufs { float* Z[4]; float* H[4]; };   // [M, out_l]: pre-LayerNorm values, activations (the backward reuses H_l for dH_l / dZ_l)
 
-static size_t ln_buf_floats(const LnLayout& L, int64_t M) {
-  size_t n = 0;
-  for (int l = 0; l < L.n_hidden; ++l) n += 2 * (((size_t)M * L.layer[l].out + 63) & ~size_t(63));
-  return n;
-}
-static void ln_carve(const LnLayout& L, int64_t M, float*& cur, LnBufs* b) {
+static void ln_carve(const LnLayout& L, int64_t M, Arena& a, LnBufs* b) {
   for (int l = 0; l < L.n_hidden; ++l) {
-    const size_t n = ((size_t)M * L.layer[l].out + 63) & ~size_t(63);
-    b->Z[l] = cur; cur += n;
-    b->H[l] = cur; cur += n;
+    b->Z[l] = a.take((size_t)M * L.layer[l].out);
+    b->H[l] = a.take((size_t)M * L.layer[l].out);
   }
 }
 
-static inline int ln_rows_grid(const rlx_ctx* ctx, int64_t M) {
-  int grid = div_up(M, 4);
-  if (grid > ctx->num_cus * 8) grid = ctx->num_cus * 8;
-  return grid;
-}
-
-static inline int ln_bwd_rows_grid(const rlx_ctx* ctx, int64_t M) {   // 16 rows per workgroup: fewer partial slabs (sac.hip: ln_bwd_grid)
-  int grid = div_up(M, 16);
-  if (grid > ctx->num_cus * 4) grid = ctx->num_cus * 4;
-  return grid < 1 ? 1 : grid;
-}
-
-int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
-int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st);
-int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
-                bool relu_mask = false);
-
-// Split-operand weight images for the trunk GEMMs of a pass with >= 4096 rows (gemm_bx.h): launch_gemm_fwd / stage_dx pick them up
-// by weight pointer.  nets[i]: parameter vector, layout, whether the pass needs the transposed images (input gradients).
-struct FsNet { const float* p; const LnLayout* L; bool bwd; };
-static int fs_images(rlx_ctx* ctx, const FsNet* nets, int n, int64_t M, hipStream_t st) {
-  if (M < 4096 || !ctx->gemm_bx) return RLX_OK;
-  BxMat mats[BX_MAX_JOBS];
-  int k = 0;
-  for (int i = 0; i < n; ++i)
-    for (int l = 0; l < nets[i].L->n_hidden; ++l) {
-      const LnLayer& o = nets[i].L->layer[l];
-      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
-      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
-    }
-  if (!k) return RLX_OK;
-  const int rc = bx_prepare_mats(ctx, mats, k, st);
-  if (rc) return rc;
-  // the second critic's passes run on the side stream under scratch bank 1 (FsFork): the same images serve both banks
-  for (int i = 0; i < ctx->bx_n[0]; ++i) ctx->bx_img[1][i] = ctx->bx_img[0][i];
-  ctx->bx_n[1] = ctx->bx_n[0];
-  return RLX_OK;
-}
+using FsNet = NetRef<LnLayout>;   // parameter vector, layout, whether the pass needs the transposed images (input gradients)
 
 // forward through all hidden layers and the head; x: [M, in] with row stride ldx (a multiple of four, zero padded)
 static int ln_fwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* x, int ldx, const LnBufs& b, float* head_out, int64_t M,
@@ -127,7 +77,7 @@ static int ln_fwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* 
     const LnLayer& o = L.layer[l];
     int rc = launch_gemm_fwd(ctx, h, p + o.W, p + o.b, b.Z[l], M, o.out, o.in, RLX_ACT_NONE, st, ld, nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ln_act_wide<false>, dim3(ln_rows_grid(ctx, M)), dim3(256), 0, st, (const float*)b.Z[l], b.H[l], p + o.g, p + o.be,
+    hipLaunchKernelGGL(k_ln_act_wide<false>, dim3(rows_grid(ctx, M)), dim3(256), 0, st, (const float*)b.Z[l], b.H[l], p + o.g, p + o.be,
                        (float*)nullptr, M, o.out, RLX_ACT_SILU, FS_LN_EPS);
     RLX_LAUNCH_CHECK();
     h = b.H[l];
@@ -138,11 +88,10 @@ static int ln_fwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* 
 
 // floats the partial-sum buffers of one ln_bwd take from the deferred-reduction arena (stage_alloc rounds each to 64)
 static size_t ln_bwd_stage_floats(const rlx_ctx* ctx, const LnLayout& L, int64_t M, bool grads) {
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
   size_t n = 0;
-  if (grads) n += a64((size_t)div_up(M, 32) * (((size_t)L.head_in * L.head_out + 3 & ~size_t(3)) + ((L.head_out + 3) & ~3)));
+  if (grads) n += head_stage_floats(L.head_in, L.head_out, M);
   for (int l = 0; l < L.n_hidden; ++l) {
-    n += a64((size_t)ln_bwd_rows_grid(ctx, M) * 2 * L.layer[l].out);
+    n += a64((size_t)bwd_rows_grid(ctx, M) * 2 * L.layer[l].out);
     if (grads) n += a64(stage_dw_floats(ctx, M, L.layer[l].in, L.layer[l].out));
   }
   return n;
@@ -161,192 +110,27 @@ static int ln_bwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* 
   if (rc) return rc;
   for (int l = last; l >= 0; --l) {
     const LnLayer& o = L.layer[l];
-    const int grid = ln_bwd_rows_grid(ctx, M);
+    const int grid = bwd_rows_grid(ctx, M);
     float* part = stage_alloc(ctx, (size_t)grid * 2 * o.out);
     if (!part) return RLX_ENOMEM;
     hipLaunchKernelGGL(k_ln_act_wide<true>, dim3(grid), dim3(256), (size_t)8 * o.out * sizeof(float), st, (const float*)b.Z[l], b.H[l],
                        p + o.g, p + o.be, part, M, o.out, RLX_ACT_SILU, FS_LN_EPS);
     RLX_LAUNCH_CHECK();
     if (grads) {
-      ReduceTable tab;
-      tab.n = 0;
-      tab.seg[tab.n++] = ReduceSeg{part, grads + o.g, (int64_t)o.out, (int64_t)2 * o.out, grid, 0, 1.f, 0.f, 1};
-      tab.seg[tab.n++] = ReduceSeg{part + o.out, grads + o.be, (int64_t)o.out, (int64_t)2 * o.out, grid, 0, 1.f, 0.f, 1};
-      rc = stage_reduce(ctx, tab, nullptr, nullptr, st);
+      rc = norm_bwd_reduce(ctx, part, grid, o.out, grads + o.g, grads + o.be, st);
       if (rc) return rc;
       rc = stage_dw(ctx, l == 0 ? x : b.H[l - 1], l == 0 ? ldx : o.in, b.H[l], M, o.in, o.out, grads + o.W, grads + o.b, nullptr, nullptr, st);
       if (rc) return rc;
     }
     if (l > 0) rc = stage_dx(ctx, b.H[l], p + o.W, b.H[l - 1], M, o.out, o.in, o.in, RLX_ACT_NONE, 0, st, nullptr);
-    else if (dx && dx_nc > 0 && dx_cols_ok(o.out, dx_nc))
-      rc = launch_dx_cols(b.H[0], p + o.W + (int64_t)dx_c0 * o.out, dx + dx_c0, M, o.out, dx_nc, lddx, st);
-    else if (dx) rc = stage_dx(ctx, b.H[0], p + o.W, dx, M, o.out, o.in, lddx, RLX_ACT_NONE, 0, st, nullptr);
+    else if (dx) rc = first_layer_dx(ctx, b.H[0], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
     if (rc) return rc;
   }
   return RLX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-// Dense heads (nr_atoms = 101 or 2 * act_dim outputs: widths the float4-tiled GEMM stages do not take -- their contraction and
-// leading dimensions have to be multiples of four).  K <= 768 inputs, any N; small next to the trunk, so plain kernels.
-// out[M, N] = H[M, K] @ W[K, N] + b: a workgroup of 128 threads per 8 rows x 128 columns, thread <-> output column.  The H values
-// of a row are the same for every lane: their addresses are wave-uniform, so they arrive through the scalar cache as SGPR operands
-// of the FMAs -- no LDS, no barrier, eight W loads in flight per thread.  (With H in LDS the kernel was LDS-issue bound: eight
-// broadcast reads per k and wave; 22 -> 34 us when the W tiles went through LDS as well.)  One ascending fmaf chain per output.
-__global__ __launch_bounds__(128) void k_fs_head_fwd(const float* __restrict__ H, const float* __restrict__ W, const float* __restrict__ b,
-                                                     float* __restrict__ out, int64_t M, int K, int N) {
-  const int64_t r0 = (int64_t)blockIdx.x * 8;
-  const int n = blockIdx.y * 128 + threadIdx.x;
-  const int nc = n < N ? n : N - 1;                      // (idle lanes compute a copy of the last column)
-  const float* hr[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) hr[r] = H + (r0 + r < M ? r0 + r : M - 1) * K;
-  float acc[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) acc[r] = 0.f;
-  int k = 0;
-  for (; k + 8 <= K; k += 8) {
-    float w[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) w[u] = W[(int64_t)(k + u) * N + nc];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[r] = fmaf(hr[r][k + u], w[u], acc[r]);
-    }
-  }
-  for (; k < K; ++k) {
-    const float w = W[(int64_t)k * N + nc];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) acc[r] = fmaf(hr[r][k], w, acc[r]);
-  }
-  if (n < N) {
-    const float bv = b[n];
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      if (r0 + r < M) out[(r0 + r) * N + n] = acc[r] + bv;
-  }
-}
-// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k.  RELU_MASK (FastTD3): H_dH
-// holds the ReLU output H on entry and dH * (H > 0) on exit (each entry is read by the thread that overwrites it).
-template <bool RELU_MASK>
-__global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d, const float* __restrict__ W, float* __restrict__ dH,
-                                                    int64_t M, int K, int N) {
-  extern __shared__ float s_d[];   // [8][N]
-  const int64_t r0 = (int64_t)blockIdx.x * 8;
-  {
-    const int64_t left = (M - r0) * N;
-    lds_stage<256, float>(s_d, d + r0 * N, 8 * N, left < 8 * N ? (int)left : 8 * N, 0.f);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < K; k += 256) {
-    float acc[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) acc[r] = 0.f;
-    const float* wr = W + (int64_t)k * N;
-    for (int n = 0; n < N; ++n) {
-      const float w = wr[n];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) acc[r] = fmaf(s_d[r * N + n], w, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      if (r0 + r < M) {
-        if (RELU_MASK) acc[r] = dH[(r0 + r) * K + k] > 0.f ? acc[r] : 0.f;
-        dH[(r0 + r) * K + k] = acc[r];
-      }
-  }
-}
-// partial[s][K * N + N]: dW = H^T d and db = column sums of d over the rows [s * rows, (s + 1) * rows) -- summed in row order;
-// the slabs are added in slab order by the reduction kernel.  blockIdx.y = slab, thread <-> (k, n) pairs.
-__global__ __launch_bounds__(256) void k_fs_head_dw(const float* __restrict__ H, const float* __restrict__ d, float* __restrict__ partial,
-                                                    int64_t M, int K, int N, int rows, int64_t PS, int boff) {
-  const int64_t r0 = (int64_t)blockIdx.y * rows;
-  const int64_t r1 = r0 + rows < M ? r0 + rows : M;
-  float* out = partial + (int64_t)blockIdx.y * PS;
-  const int total = K * N + N;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
-    float acc = 0.f;
-    if (e < K * N) {
-      const int k = e / N, n = e - k * N;
-      for (int64_t r = r0; r < r1; ++r) acc = fmaf(H[r * K + k], d[r * N + n], acc);
-    } else {
-      const int n = e - K * N;
-      for (int64_t r = r0; r < r1; ++r) acc += d[r * N + n];
-    }
-    out[e < K * N ? e : boff + (e - K * N)] = acc;
-  }
-}
-
-// The same partials from a register tile: workgroup = slab, thread = 8 k x NJ n outputs (k = 8 tk .. 8 tk + 7, n = tn + TN j),
-// 16-row chunks of H and d staged in LDS; every output is one ascending fmaf chain over the slab's rows like above.  (The
-// per-output loop above re-reads H and d from L2 for every output: 134 us at [8192, 192] x [8192, 101]; this one 10.)
-// Slab layout: [K * N] dW, then db at float `boff` (both 16-byte aligned when the caller pads: vector path of the reduction).
-template <int NJ>
-__global__ __launch_bounds__(256) void k_fs_head_dw_tiled(const float* __restrict__ H, const float* __restrict__ d,
-                                                          float* __restrict__ partial, int64_t M, int K, int N, int rows, int TK, int TN,
-                                                          int64_t PS, int boff) {
-  extern __shared__ __attribute__((aligned(16))) float s_hd[];
-  constexpr int RC = 16;
-  float* Hs = s_hd;              // [RC][K]
-  float* Ds = s_hd + RC * K;     // [RC][N]
-  const int tk = threadIdx.x / TN, tn = threadIdx.x - tk * TN;
-  const bool on = tk < TK;
-  float acc[8][NJ], bsum[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    bsum[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i][j] = 0.f;
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * rows;
-  const int64_t r1 = r0 + rows < M ? r0 + rows : M;
-  for (int64_t c0 = r0; c0 < r1; c0 += RC) {
-    const int nr = (int)(r1 - c0 < RC ? r1 - c0 : RC);
-    __syncthreads();
-    lds_stage<256, float>(Hs, H + c0 * K, RC * K, nr * K, 0.f);
-    lds_stage<256, float>(Ds, d + c0 * N, RC * N, nr * N, 0.f);
-    __syncthreads();
-    if (on) {
-#pragma unroll 2
-      for (int r = 0; r < RC; ++r) {
-        const float4 h0 = *reinterpret_cast<const float4*>(Hs + r * K + 8 * tk);
-        const float4 h1 = *reinterpret_cast<const float4*>(Hs + r * K + 8 * tk + 4);
-        const float hv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int n = tn + TN * j;
-          const float dv = n < N ? Ds[r * N + n] : 0.f;
-          bsum[j] += dv;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) acc[i][j] = fmaf(hv[i], dv, acc[i][j]);
-        }
-      }
-    }
-  }
-  if (!on) return;
-  float* out = partial + (int64_t)blockIdx.x * PS;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int n = tn + TN * j;
-    if (n >= N) continue;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[(int64_t)(8 * tk + i) * N + n] = acc[i][j];
-    if (tk == 0) out[boff + n] = bsum[j];
-  }
-}
-
-// [obs | action] rows of a critic input (row stride ld; the action columns may be filled later by k_fs_sample)
-__global__ __launch_bounds__(256) void k_fs_concat(const float* __restrict__ obs, int Oc, const float* __restrict__ act, int A,
-                                                   float* __restrict__ out, int ld, int64_t M) {
-  const int64_t n = M * ld;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / ld;
-    const int c = (int)(i - r * ld);
-    out[i] = c < Oc ? obs[r * Oc + c] : (act && c < Oc + A ? act[r * A + (c - Oc)] : 0.f);
-  }
-}
-
+// (the dense heads and the [obs | action] concat: dense_head.hip)
 // policy.get_action_and_log_prob (policy.py:75-90) from the head output [M, 2A] = [mean | raw log-std]: one thread per
 // (row, action dim); the log-prob terms of a row are added in index order by one lane.  act_out: row stride ld, first column c0.
 __global__ __launch_bounds__(256) void k_fs_sample(const float* __restrict__ head, const float* __restrict__ scale, uint32_t k0,
@@ -521,50 +305,6 @@ __global__ __launch_bounds__(256) void k_fs_policy_metrics(const float* __restri
   }
 }
 
-int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st) {
-  hipLaunchKernelGGL(k_fs_head_fwd, dim3(div_up(M, 8), div_up(N, 128)), dim3(128), 0, st, H, W, b, out, M, K, N);
-  RLX_LAUNCH_CHECK();
-  return RLX_OK;
-}
-
-int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
-                bool relu_mask) {
-  if (gW) {
-    const int boff = (K * N + 3) & ~3;
-    const int64_t PS = boff + ((N + 3) & ~3);
-    const int TK = K / 8, TN = TK > 0 && TK <= 256 ? 256 / TK : 0;
-    const int nj = TN ? div_up(N, TN) : 99;
-    const bool tiled = K % 8 == 0 && nj <= 12 && (size_t)16 * (K + N) * sizeof(float) <= 48 * 1024;
-    const int rows = tiled ? (M >= 8192 ? 32 : 64) : 128, S = div_up(M, rows);   // (>= 256 slabs: one per CU)
-    float* part = stage_alloc(ctx, (size_t)S * PS);
-    if (!part) return RLX_ENOMEM;
-    if (tiled) {
-      const size_t lds = (size_t)16 * (K + N) * sizeof(float);
-#define FS_DW_TILED(NJ) hipLaunchKernelGGL(k_fs_head_dw_tiled<NJ>, dim3(S), dim3(256), lds, st, (const float*)H_dH, d, part, M, K, N, rows, TK, TN, PS, boff)
-      if (nj <= 2) FS_DW_TILED(2);
-      else if (nj <= 4) FS_DW_TILED(4);
-      else if (nj <= 8) FS_DW_TILED(8);
-      else FS_DW_TILED(12);
-#undef FS_DW_TILED
-    } else {
-      int gx = div_up(K * N + N, 256);
-      if (gx > 64) gx = 64;
-      hipLaunchKernelGGL(k_fs_head_dw, dim3(gx, S), dim3(256), 0, st, (const float*)H_dH, d, part, M, K, N, rows, PS, boff);
-    }
-    RLX_LAUNCH_CHECK();
-    ReduceTable tab;
-    tab.n = 0;
-    tab.seg[tab.n++] = ReduceSeg{part, gW, (int64_t)K * N, PS, S, 0, 1.f, 0.f, 1};
-    tab.seg[tab.n++] = ReduceSeg{part + boff, gb, (int64_t)N, PS, S, 0, 1.f, 0.f, 1};
-    const int rc = stage_reduce(ctx, tab, nullptr, nullptr, st);
-    if (rc) return rc;
-  }
-  if (relu_mask) hipLaunchKernelGGL(k_fs_head_dx<true>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
-  else hipLaunchKernelGGL(k_fs_head_dx<false>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
-  RLX_LAUNCH_CHECK();
-  return RLX_OK;
-}
-
 static int fs_sample(const float* head, const float* scale, const uint32_t ks[2], int scheme, const float* inject, float* act_out, int ld,
                      int c0, float* logp, int64_t M, int A, const rlx_fastsac_hparams& hp, int deterministic, int64_t row_off,
                      int64_t M_global, hipStream_t st) {
@@ -572,14 +312,6 @@ static int fs_sample(const float* head, const float* scale, const uint32_t ks[2]
   const int rpb = 256 / A;
   hipLaunchKernelGGL(k_fs_sample, dim3(div_up(M, rpb)), dim3(256), (size_t)rpb * A * sizeof(float), st, head, scale, ks[0], ks[1], scheme,
                      inject, act_out, ld, c0, logp, M, A, hp.log_std_min, hp.log_std_max, deterministic, row_off, M_global);
-  RLX_LAUNCH_CHECK();
-  return RLX_OK;
-}
-
-int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st) {
-  int grid = div_up(M * ld, 256);
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(k_fs_concat, dim3(grid), dim3(256), 0, st, obs, Oc, act, A, out, ld, M);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }
@@ -677,16 +409,18 @@ int rlx_lnmlp_fwd_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* d, const float* params
   bx_release_all(ctx);
   const LnLayout L = ln_layout(*d);
   const int ldp = (d->in_dim + 3) & ~3;
-  float* base = (float*)scratch(ctx, SL_SAC, (ln_buf_floats(L, M) + (size_t)M * ldp + 64) * sizeof(float));
-  if (!base) return RLX_ENOMEM;
   LnBufs b;
-  float* cur = base;
-  ln_carve(L, M, cur, &b);
+  float* xp;                         // the rows at a 16-byte pitch, when the caller's are not
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    ln_carve(L, M, a, &b);
+    xp = a.take((size_t)M * ldp);
+  });
+  if (rc) return rc;
   if (ldx % 4 != 0 || ldx < ldp) {   // the GEMM stages read 16-byte pieces: rows at a pitch that is a multiple of four, zero padded
     RLX_REQUIRE(ldx == d->in_dim, RLX_EUNSUP, "rlx_lnmlp_fwd_f32: a row stride that is not a multiple of 4 must equal in_dim");
-    rc = fs_concat(x, d->in_dim, nullptr, 0, cur, ldp, M, (hipStream_t)stream);
+    rc = fs_concat(x, d->in_dim, nullptr, 0, xp, ldp, M, (hipStream_t)stream);
     if (rc) return rc;
-    x = cur;
+    x = xp;
     ldx = ldp;
   }
   return ln_fwd(ctx, L, params, x, ldx, b, out, M, (hipStream_t)stream);
@@ -724,25 +458,21 @@ int rlx_fastsac_act_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, const float* 
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
   const LnLayout L = ln_layout(*pdesc);
-  const size_t nb = ln_buf_floats(L, N);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  float* base = (float*)scratch(ctx, SL_SAC, (nb + (size_t)N * 2 * A + (size_t)N * ldp + 128) * sizeof(float));
-  if (!base) return RLX_ENOMEM;
   LnBufs b;
-  float* cur = base;
-  ln_carve(L, N, cur, &b);
-  float* head = cur;
-  float* xs = head + (((size_t)N * 2 * A + 63) & ~size_t(63));
+  float *head, *xs;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    ln_carve(L, N, a, &b);
+    head = a.take((size_t)N * 2 * A);
+    xs = a.take((size_t)N * ldp);
+  });
+  if (rc) return rc;
   rc = fs_concat(obs, pdesc->in_dim, nullptr, 0, xs, ldp, N, st);
   if (!rc) rc = ln_fwd(ctx, L, pparams, xs, ldp, b, head, N, st);
   if (rc) return rc;
-  uint32_t ks[4] = {key_io[0], key_io[1], 0, 0};
-  if (!deterministic) {
-    split_host(key_io, ks, 2, scheme);      // key, subkey = split(key)
-    key_io[0] = ks[0];
-    key_io[1] = ks[1];
-  }
-  return fs_sample(head, action_scale, ks + 2, scheme, ctx->dbg_sac_eps[0], action, A, 0, nullptr, N, A, *hp, deterministic, row_offset,
+  uint32_t sub[2] = {0, 0};
+  if (!deterministic) next_key(key_io, sub, 1, scheme);      // key, subkey = split(key)
+  return fs_sample(head, action_scale, sub, scheme, ctx->dbg_sac_eps[0], action, A, 0, nullptr, N, A, *hp, deterministic, row_offset,
                    N_global, st);
 }
 
@@ -770,38 +500,31 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   const int64_t nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3;
   // ---- arena: policy activations, one set for the two target passes (inference), two sets for the online critics
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
-  const size_t np_b = ln_buf_floats(LP, B), nq_b = ln_buf_floats(LQ, B);
-  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  const size_t total = np_b + 3 * nq_b + 2 * n_x + a64((size_t)B * 2 * A) + 6 * n_log + a64(B) + a64(2 * nq) + a64((size_t)B * ldp) + 256;
-  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
-  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
-  if (!base || !sq) return RLX_ENOMEM;
-  float* cur = base;
   LnBufs bp, bt, b1, b2;
-  ln_carve(LP, B, cur, &bp);
-  ln_carve(LQ, B, cur, &bt);
-  ln_carve(LQ, B, cur, &b1);
-  ln_carve(LQ, B, cur, &b2);
-  float* xc = cur; cur += n_x;
-  float* xn = cur; cur += n_x;
-  float* head = cur; cur += a64((size_t)B * 2 * A);
-  float *lt1 = cur, *lt2 = cur + n_log, *l1 = cur + 2 * n_log, *l2 = cur + 3 * n_log, *d1 = cur + 4 * n_log, *d2 = cur + 5 * n_log;
-  cur += 6 * n_log;
-  float* lpn = cur; cur += a64(B);
-  float* gq = cur; cur += a64(2 * nq);
-  float* xs = cur; cur += a64((size_t)B * ldp);                 // policy observations at a 16-byte row pitch
-  float* c51o = cur;                                            // 4 floats
-  // key, subkey = split(key)
-  uint32_t ks[4];
-  split_host(key_io, ks, 2, scheme);
-  key_io[0] = ks[0];
-  key_io[1] = ks[1];
-  struct BxAll { rlx_ctx* c; ~BxAll() { bx_release_all(c); } } bx_all{ctx};
+  float *xc, *xn, *head, *lt1, *lt2, *l1, *l2, *d1, *d2, *lpn, *gq, *xs, *c51o;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    ln_carve(LP, B, a, &bp);
+    ln_carve(LQ, B, a, &bt);
+    ln_carve(LQ, B, a, &b1);
+    ln_carve(LQ, B, a, &b2);
+    xc = a.take((size_t)B * ldc);
+    xn = a.take((size_t)B * ldc);
+    head = a.take((size_t)B * 2 * A);
+    for (float** l : {&lt1, &lt2, &l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
+    lpn = a.take(B);
+    gq = a.take(2 * nq);
+    xs = a.take((size_t)B * ldp);                               // policy observations at a 16-byte row pitch
+    c51o = a.take(4);
+  });
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (rc || !sq) return RLX_ENOMEM;
+  uint32_t ks[2];
+  next_key(key_io, ks, 1, scheme);                              // key, subkey = split(key)
+  BxReleaseAll bx_all{ctx};
   {
     const FsNet nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
-    rc = fs_images(ctx, nets, 5, B, st);
+    rc = trunk_images(ctx, nets, 5, B, st);
     if (rc) return rc;
   }
   // Two streams: the policy on s' + both target critics on (s', a') on the caller's stream, both online critics on (s, a) on the
@@ -819,7 +542,7 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   if (!rc) rc = fs_concat(cn, Oc, nullptr, A, xn, ldc, B, fk.main());
   if (!rc) rc = fs_concat(next_states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
   if (!rc) rc = ln_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
-  if (!rc) rc = fs_sample(head, action_scale, ks + 2, scheme, ctx->dbg_sac_eps[0], xn, ldc, Oc, lpn, B, A, *hp, 0, 0, B, st);
+  if (!rc) rc = fs_sample(head, action_scale, ks, scheme, ctx->dbg_sac_eps[0], xn, ldc, Oc, lpn, B, A, *hp, 0, 0, B, st);
   if (!rc) rc = ln_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
   if (!rc) rc = ln_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
   if (!rc) rc = fk.join();
@@ -872,47 +595,39 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
   const LnLayout LP = ln_layout(*pdesc), LQ = ln_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3;
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
-  const size_t np_b = ln_buf_floats(LP, B), nq_b = ln_buf_floats(LQ, B);
-  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA), n_hd = a64((size_t)B * 2 * A);
   const int nblk = div_up(B, 4);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  const size_t total = np_b + 2 * nq_b + 3 * n_x + 2 * n_hd + 4 * n_log + a64(B) + a64(nblk) + a64(np_) + a64((size_t)B * ldp) + 256;
-  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
-  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
-  if (!base || !sq) return RLX_ENOMEM;
-  float* cur = base;
   LnBufs bp, b1, b2;
-  ln_carve(LP, B, cur, &bp);
-  ln_carve(LQ, B, cur, &b1);
-  ln_carve(LQ, B, cur, &b2);
-  float* xp = cur; cur += n_x;
-  float* dx1 = cur; cur += n_x;
-  float* dx2 = cur; cur += n_x;
-  float* head = cur; cur += n_hd;
-  float* dhead = cur; cur += n_hd;
-  float *l1 = cur, *l2 = cur + n_log, *d1 = cur + 2 * n_log, *d2 = cur + 3 * n_log;
-  cur += 4 * n_log;
-  float* lp = cur; cur += a64(B);
-  float* part = cur; cur += a64(nblk);
-  float* gp = cur; cur += a64(np_);
-  float* xs = cur;                                              // policy observations at a 16-byte row pitch
-  uint32_t ks[4];
-  split_host(key_io, ks, 2, scheme);
-  key_io[0] = ks[0];
-  key_io[1] = ks[1];
+  float *xp, *dx1, *dx2, *head, *dhead, *l1, *l2, *d1, *d2, *lp, *part, *gp, *xs;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    ln_carve(LP, B, a, &bp);
+    ln_carve(LQ, B, a, &b1);
+    ln_carve(LQ, B, a, &b2);
+    for (float** x : {&xp, &dx1, &dx2}) *x = a.take((size_t)B * ldc);
+    head = a.take((size_t)B * 2 * A);
+    dhead = a.take((size_t)B * 2 * A);
+    for (float** l : {&l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
+    lp = a.take(B);
+    part = a.take(nblk);
+    gp = a.take(np_);
+    xs = a.take((size_t)B * ldp);                               // policy observations at a 16-byte row pitch
+  });
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (rc || !sq) return RLX_ENOMEM;
+  uint32_t ks[2];
+  next_key(key_io, ks, 1, scheme);                              // key, subkey = split(key)
   const float inv_b = 1.0f / (float)B;
-  struct BxAll { rlx_ctx* c; ~BxAll() { bx_release_all(c); } } bx_all{ctx};
+  BxReleaseAll bx_all{ctx};
   {
     const FsNet nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
-    rc = fs_images(ctx, nets, 3, B, st);
+    rc = trunk_images(ctx, nets, 3, B, st);
     if (rc) return rc;
   }
   // policy on s, sampled action into the critics' input rows, both critics, seeds
   rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
   if (!rc) rc = fs_concat(states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
   if (!rc) rc = ln_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
-  if (!rc) rc = fs_sample(head, action_scale, ks + 2, scheme, ctx->dbg_sac_eps[1], xp, ldc, Oc, lp, B, A, *hp, 0, 0, B, st);
+  if (!rc) rc = fs_sample(head, action_scale, ks, scheme, ctx->dbg_sac_eps[1], xp, ldc, Oc, lp, B, A, *hp, 0, 0, B, st);
   FsFork fk(ctx, st);
   if (!rc) rc = fk.begin();
   if (!rc) rc = fk.fork();
@@ -936,7 +651,7 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
     if (rc) return rc;
     int grid = div_up(B * A, 256);
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(k_fs_policy_grad, dim3(grid), dim3(256), 0, st, (const float*)head, action_scale, ctx->dbg_sac_eps[1], ks[2], ks[3],
+    hipLaunchKernelGGL(k_fs_policy_grad, dim3(grid), dim3(256), 0, st, (const float*)head, action_scale, ctx->dbg_sac_eps[1], ks[0], ks[1],
                        scheme, (const float*)dx1, (const float*)dx2, ldc, Oc, log_alpha, dhead, B, A, hp->log_std_min, hp->log_std_max, inv_b,
                        (int64_t)0, B);
     RLX_LAUNCH_CHECK();

@@ -6,8 +6,9 @@
 // ln_first = 0, has_logstd = 0 (flat layout: per layer W[in, out] row-major, b[out]; then the head), hidden widths multiples of
 // 64 up to 1024 (td3_check: the PPO / SAC check mlp_check_desc stays as it is).  The trunks are the library's GEMM stages with
 // the fused bias + ReLU epilogue (launch_gemm_fwd) and the ReLU' input-gradient epilogue (stage_dx), the split-operand engine
-// for passes of >= 4096 rows (td3_images), stage_dw for the weight gradients; the heads are fastsac.hip's k_fs_head_* kernels
-// (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head kernel k_td3_head_act below.
+// for passes of >= 4096 rows (trunk_images, net_pass.h), stage_dw for the weight gradients; the heads are dense_head.hip's
+// k_fs_head_* kernels (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head kernel k_td3_head_act
+// below.  Arena, grids, key splitting and the first layer's input gradient: net_pass.h, shared with fastsac.hip.
 //
 // fp16 window: the split-operand engine holds |weight| < 1023, |activation| < 4094, per-sample gradient < 8190.
 // ReLU activations are not bounded by a LayerNorm; a value outside the window turns the affected products into inf / NaN, the
@@ -18,23 +19,9 @@
 // like rlx_fastsac_*), and rlx_dbg_set_sac_noise(eps_next, .) injects the given N(0, 1) draws of the exploration noise
 // (rlx_fasttd3_act_f32, [N, A]) and of the smoothing noise (rlx_fasttd3_critic_update_f32, [B, A]) for parity tests.
 // CPU twin: tests/fasttd3_twin.py, pinned by outputs of the reference's own modules and closures (tests/golden/fasttd3_reference.npz).
-#include "gemm_bx.h"
-#include "mlp.h"
-#include "fs_sched.h"
-
-extern "C" int rlx_c51_critic_loss_f32(rlx_ctx* ctx, const float* q1_logits, const float* q2_logits, const float* q1_next_logits,
-                                       const float* q2_next_logits, const float* rewards, const float* dones,
-                                       const float* truncations, const float* effective_n_steps, const float* next_log_probs,
-                                       const float* log_alpha, int64_t B, int nr_atoms, float gamma, float v_min, float v_max,
-                                       int clipped_double_q, float* d_q1_logits, float* d_q2_logits, float* out4, void* stream);
+#include "net_pass.h"
 
 namespace rlx {
-
-// fastsac.hip
-int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
-int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st);
-int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
-                bool relu_mask);
 
 static int td3_check(const rlx_mlp_desc& d) {
   RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL,
@@ -49,37 +36,11 @@ static int td3_check(const rlx_mlp_desc& d) {
 
 struct TdBufs { float* H[3]; };   // [M, out_l] ReLU outputs (the backward overwrites H_l with dZ_l)
 
-static size_t td3_buf_floats(const MlpLayout& L, int64_t M) {
-  size_t n = 0;
-  for (int l = 0; l < L.n_hidden; ++l) n += ((size_t)M * L.layer[l].out + 63) & ~size_t(63);
-  return n;
-}
-static void td3_carve(const MlpLayout& L, int64_t M, float*& cur, TdBufs* b) {
-  for (int l = 0; l < L.n_hidden; ++l) {
-    b->H[l] = cur;
-    cur += ((size_t)M * L.layer[l].out + 63) & ~size_t(63);
-  }
+static void td3_carve(const MlpLayout& L, int64_t M, Arena& a, TdBufs* b) {
+  for (int l = 0; l < L.n_hidden; ++l) b->H[l] = a.take((size_t)M * L.layer[l].out);
 }
 
-// split-operand weight images of the trunk GEMMs of a pass with >= 4096 rows (as fastsac.hip: fs_images)
-struct TdNet { const float* p; const MlpLayout* L; bool bwd; };
-static int td3_images(rlx_ctx* ctx, const TdNet* nets, int n, int64_t M, hipStream_t st) {
-  if (M < 4096 || !ctx->gemm_bx) return RLX_OK;
-  BxMat mats[BX_MAX_JOBS];
-  int k = 0;
-  for (int i = 0; i < n; ++i)
-    for (int l = 0; l < nets[i].L->n_hidden; ++l) {
-      const LayerOff& o = nets[i].L->layer[l];
-      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
-      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
-    }
-  if (!k) return RLX_OK;
-  const int rc = bx_prepare_mats(ctx, mats, k, st);
-  if (rc) return rc;
-  for (int i = 0; i < ctx->bx_n[0]; ++i) ctx->bx_img[1][i] = ctx->bx_img[0][i];   // the side stream's bank sees the same images
-  ctx->bx_n[1] = ctx->bx_n[0];
-  return RLX_OK;
-}
+using TdNet = NetRef<MlpLayout>;   // parameter vector, layout, whether the pass needs the transposed images (input gradients)
 
 // trunk forward (Dense + bias + ReLU fused in the GEMM epilogue), then the head when head_out != NULL; x: [M, in], row stride
 // ldx (a multiple of four, zero padded)
@@ -102,9 +63,7 @@ static int td3_fwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float
 // div_up(M, 32) of them)
 static size_t td3_stage_floats(const rlx_ctx* ctx, const MlpLayout& L, int64_t M, bool grads) {
   if (!grads) return 0;
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
-  const size_t K = L.head.in, N = L.head.out;
-  size_t n = a64((size_t)div_up(M, 32) * (((K * N + 3) & ~size_t(3)) + ((N + 3) & ~size_t(3))));
+  size_t n = head_stage_floats(L.head.in, L.head.out, M);
   for (int l = 0; l < L.n_hidden; ++l) n += a64(stage_dw_floats(ctx, M, L.layer[l].in, L.layer[l].out));
   return n;
 }
@@ -125,9 +84,7 @@ static int td3_bwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float
       if (rc) return rc;
     }
     if (l > 0) rc = stage_dx(ctx, b.H[l], p + o.W, b.H[l - 1], M, o.out, o.in, o.in, RLX_ACT_RELU, 1, st);
-    else if (dx && dx_nc > 0 && dx_cols_ok(o.out, dx_nc))
-      rc = launch_dx_cols(b.H[0], p + o.W + (int64_t)dx_c0 * o.out, dx + dx_c0, M, o.out, dx_nc, lddx, st);
-    else if (dx) rc = stage_dx(ctx, b.H[0], p + o.W, dx, M, o.out, o.in, lddx, RLX_ACT_NONE, 0, st);
+    else if (dx) rc = first_layer_dx(ctx, b.H[0], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
     if (rc) return rc;
   }
   return RLX_OK;
@@ -265,16 +222,11 @@ __global__ __launch_bounds__(256) void k_td3_policy_loss(const float* __restrict
   if (threadIdx.x == 0) metrics[0] = ((s_buf[0] + s_buf[1]) + (s_buf[2] + s_buf[3])) * inv_b;
 }
 
-static inline int td3_grid(int64_t n) {
-  int g = div_up(n, 256);
-  return g > 4096 ? 4096 : (g < 1 ? 1 : g);
-}
-
 static int td3_head_act(const MlpLayout& L, const float* p, const float* H, int64_t M, int mode, const float* noise_scale, float smooth_eps,
                         float smooth_clip, const uint32_t ks[2], int scheme, const float* inject, int64_t row_off, int64_t M_global, float* act,
                         int ld, int c0, float* proc, int clip_rescale, const float* low, const float* high, hipStream_t st) {
   const int A = L.head.out;
-  hipLaunchKernelGGL(k_td3_head_act, dim3(td3_grid(M * A)), dim3(256), 0, st, H, p + L.head.W, p + L.head.b, M, L.head.in, A, mode, noise_scale,
+  hipLaunchKernelGGL(k_td3_head_act, dim3(elem_grid(M * A)), dim3(256), 0, st, H, p + L.head.W, p + L.head.b, M, L.head.in, A, mode, noise_scale,
                      smooth_eps, smooth_clip, ks[0], ks[1], scheme, inject, row_off, M_global, act, ld, c0, proc, clip_rescale, low, high);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
@@ -295,8 +247,6 @@ static int td3_check_pair(const rlx_mlp_desc& pd, const rlx_mlp_desc& qd, const 
   return RLX_OK;
 }
 
-struct BxAllRelease { rlx_ctx* c; ~BxAllRelease() { bx_release_all(c); } };
-
 }  // namespace rlx
 
 using namespace rlx;
@@ -306,11 +256,9 @@ extern "C" {
 int rlx_fasttd3_noise_scales_f32(rlx_ctx* ctx, uint32_t key_io[2], int scheme, float* noise_scales, const float* dones, int N,
                                  float noise_std_min, float noise_std_max, void* stream) {
   RLX_REQUIRE(ctx && key_io && noise_scales && N > 0, RLX_EINVAL, "rlx_fasttd3_noise_scales_f32: bad args");
-  uint32_t ks[4];
-  split_host(key_io, ks, 2, scheme);      // key, subkey = split(key)
-  key_io[0] = ks[0];
-  key_io[1] = ks[1];
-  hipLaunchKernelGGL(k_td3_noise_scales, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, noise_scales, dones, N, ks[2], ks[3], scheme,
+  uint32_t ks[2];
+  next_key(key_io, ks, 1, scheme);      // key, subkey = split(key)
+  hipLaunchKernelGGL(k_td3_noise_scales, dim3(div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, noise_scales, dones, N, ks[0], ks[1], scheme,
                      noise_std_min, noise_std_max);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
@@ -329,22 +277,19 @@ int rlx_fasttd3_act_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pp
   bx_release_all(ctx);
   const MlpLayout L = make_layout(*pdesc);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  float* base = (float*)scratch(ctx, SL_SAC, (td3_buf_floats(L, N) + (size_t)N * ldp + 64) * sizeof(float));
-  if (!base) return RLX_ENOMEM;
   TdBufs b;
-  float* cur = base;
-  td3_carve(L, N, cur, &b);
-  float* xs = cur;
+  float* xs;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    td3_carve(L, N, a, &b);
+    xs = a.take((size_t)N * ldp);
+  });
+  if (rc) return rc;
   rc = fs_concat(obs, pdesc->in_dim, nullptr, 0, xs, ldp, N, st);
   if (!rc) rc = td3_fwd(ctx, L, pparams, xs, ldp, b, nullptr, N, st);
   if (rc) return rc;
-  uint32_t ks[4] = {key_io[0], key_io[1], 0, 0};
-  if (!deterministic) {
-    split_host(key_io, ks, 2, scheme);
-    key_io[0] = ks[0];
-    key_io[1] = ks[1];
-  }
-  return td3_head_act(L, pparams, b.H[L.n_hidden - 1], N, deterministic ? TD_NOISE_NONE : TD_NOISE_EXPLORE, noise_scales, 0.f, 0.f, ks + 2,
+  uint32_t ks[2] = {0, 0};
+  if (!deterministic) next_key(key_io, ks, 1, scheme);
+  return td3_head_act(L, pparams, b.H[L.n_hidden - 1], N, deterministic ? TD_NOISE_NONE : TD_NOISE_EXPLORE, noise_scales, 0.f, 0.f, ks,
                       scheme, ctx->dbg_sac_eps[0], row_offset, N_global, action, pdesc->out_dim, 0, processed_action, clip_and_rescale, low,
                       high, st);
 }
@@ -371,35 +316,29 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   const int64_t nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
   // ---- arena: policy trunk, one set for the two target passes (inference, one after the other), two sets for the online critics
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
-  const size_t np_b = td3_buf_floats(LP, B), nq_b = td3_buf_floats(LQ, B);
-  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA);
-  const size_t total = np_b + 3 * nq_b + 2 * n_x + 6 * n_log + a64(B) + a64(2 * nq) + a64((size_t)B * ldp) + 128;
-  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
-  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
-  if (!base || !sq) return RLX_ENOMEM;
-  float* cur = base;
   TdBufs bp, bt, b1, b2;
-  td3_carve(LP, B, cur, &bp);
-  td3_carve(LQ, B, cur, &bt);
-  td3_carve(LQ, B, cur, &b1);
-  td3_carve(LQ, B, cur, &b2);
-  float* xc = cur; cur += n_x;
-  float* xn = cur; cur += n_x;
-  float *lt1 = cur, *lt2 = cur + n_log, *l1 = cur + 2 * n_log, *l2 = cur + 3 * n_log, *d1 = cur + 4 * n_log, *d2 = cur + 5 * n_log;
-  cur += 6 * n_log;
-  float* zeros = cur; cur += a64(B);                            // next_log_probs of the C51 target: 0 (no entropy term)
-  float* gq = cur; cur += a64(2 * nq);
-  float* xs = cur; cur += a64((size_t)B * ldp);                 // policy observations of s' at a 16-byte row pitch
-  float* ninf = cur;                                            // log_alpha of the C51 target: -inf (alpha = 0)
-  uint32_t ks[4];
-  split_host(key_io, ks, 2, scheme);
-  key_io[0] = ks[0];
-  key_io[1] = ks[1];
-  BxAllRelease bx_all{ctx};
+  float *xc, *xn, *lt1, *lt2, *l1, *l2, *d1, *d2, *zeros, *gq, *xs, *ninf;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    td3_carve(LP, B, a, &bp);
+    td3_carve(LQ, B, a, &bt);
+    td3_carve(LQ, B, a, &b1);
+    td3_carve(LQ, B, a, &b2);
+    xc = a.take((size_t)B * ldc);
+    xn = a.take((size_t)B * ldc);
+    for (float** l : {&lt1, &lt2, &l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
+    zeros = a.take(B);                                          // next_log_probs of the C51 target: 0 (no entropy term)
+    gq = a.take(2 * nq);
+    xs = a.take((size_t)B * ldp);                               // policy observations of s' at a 16-byte row pitch
+    ninf = a.take(1);                                           // log_alpha of the C51 target: -inf (alpha = 0)
+  });
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (rc || !sq) return RLX_ENOMEM;
+  uint32_t ks[2];
+  next_key(key_io, ks, 1, scheme);
+  BxReleaseAll bx_all{ctx};
   {
     const TdNet nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
-    rc = td3_images(ctx, nets, 5, B, st);
+    rc = trunk_images(ctx, nets, 5, B, st);
     if (rc) return rc;
   }
   // Two streams: the online critics on (s, a) on the side stream; the policy on s', the smoothed next action and both target
@@ -414,7 +353,7 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   if (!rc) rc = fs_concat(next_states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
   if (!rc) rc = td3_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
   if (!rc) rc = td3_head_act(LP, pparams, bp.H[LP.n_hidden - 1], B, TD_NOISE_SMOOTH, nullptr, hp->smoothing_epsilon, hp->smoothing_clip_value,
-                             ks + 2, scheme, ctx->dbg_sac_eps[0], 0, B, xn, ldc, Oc, nullptr, 0, nullptr, nullptr, st);
+                             ks, scheme, ctx->dbg_sac_eps[0], 0, B, xn, ldc, Oc, nullptr, 0, nullptr, nullptr, st);
   if (!rc) rc = td3_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
   if (!rc) rc = td3_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
   if (rc) return rc;
@@ -464,34 +403,28 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
   const MlpLayout LP = make_layout(*pdesc), LQ = make_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
-  auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
-  const size_t np_b = td3_buf_floats(LP, B), nq_b = td3_buf_floats(LQ, B);
-  const size_t n_x = a64((size_t)B * ldc), n_log = a64((size_t)B * NA), n_hd = a64((size_t)B * A);
   const int nblk = div_up(B, 4);
-  const size_t total = np_b + 2 * nq_b + 3 * n_x + n_hd + 4 * n_log + a64(nblk) + a64(np_) + a64((size_t)B * ldp) + 64;
-  float* base = (float*)scratch(ctx, SL_SAC, total * sizeof(float));
-  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
-  if (!base || !sq) return RLX_ENOMEM;
-  float* cur = base;
   TdBufs bp, b1, b2;
-  td3_carve(LP, B, cur, &bp);
-  td3_carve(LQ, B, cur, &b1);
-  td3_carve(LQ, B, cur, &b2);
-  float* xp = cur; cur += n_x;
-  float* dx1 = cur; cur += n_x;
-  float* dx2 = cur; cur += n_x;
-  float* dhead = cur; cur += n_hd;
-  float *l1 = cur, *l2 = cur + n_log, *d1 = cur + 2 * n_log, *d2 = cur + 3 * n_log;
-  cur += 4 * n_log;
-  float* part = cur; cur += a64(nblk);
-  float* gp = cur; cur += a64(np_);
-  float* xs = cur;                                              // policy observations at a 16-byte row pitch
+  float *xp, *dx1, *dx2, *dhead, *l1, *l2, *d1, *d2, *part, *gp, *xs;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    td3_carve(LP, B, a, &bp);
+    td3_carve(LQ, B, a, &b1);
+    td3_carve(LQ, B, a, &b2);
+    for (float** x : {&xp, &dx1, &dx2}) *x = a.take((size_t)B * ldc);
+    dhead = a.take((size_t)B * A);
+    for (float** l : {&l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
+    part = a.take(nblk);
+    gp = a.take(np_);
+    xs = a.take((size_t)B * ldp);                               // policy observations at a 16-byte row pitch
+  });
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (rc || !sq) return RLX_ENOMEM;
   const float inv_b = 1.0f / (float)B;
   const uint32_t no_key[2] = {0, 0};
-  BxAllRelease bx_all{ctx};
+  BxReleaseAll bx_all{ctx};
   {
     const TdNet nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
-    rc = td3_images(ctx, nets, 3, B, st);
+    rc = trunk_images(ctx, nets, 3, B, st);
     if (rc) return rc;
   }
   // policy on s, its action straight into the critics' input rows, both critics (one per stream), seeds
@@ -521,7 +454,7 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
     if (!rc) rc = td3_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
     if (!rc) rc = fk.join();
     if (rc) return rc;
-    hipLaunchKernelGGL(k_td3_tanh_bwd, dim3(td3_grid(B * A)), dim3(256), 0, st, (const float*)xp, (const float*)dx1, (const float*)dx2, ldc, Oc,
+    hipLaunchKernelGGL(k_td3_tanh_bwd, dim3(elem_grid(B * A)), dim3(256), 0, st, (const float*)xp, (const float*)dx1, (const float*)dx2, ldc, Oc,
                        dhead, B, A);
     RLX_LAUNCH_CHECK();
     rc = td3_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);

@@ -1,6 +1,6 @@
-// fs_sched.h -- the stream fork / join and the deferred parameter-gradient reduction of the distributional off-policy updates
-// (fastsac.hip, fasttd3.hip): both run a critic pair whose two halves go to two streams and whose backward passes gather all
-// their slab partials into one reduction launch.
+// fs_sched.h -- the stream fork / join of the distributional off-policy updates (fastsac.hip, fasttd3.hip: a critic pair whose two
+// halves go to two streams) and the deferred parameter-gradient reduction (those two, reppo.hip and mpo.hip: the backward passes
+// of a step gather all their slab partials into one reduction launch).  Included through net_pass.h.
 #pragma once
 #include "mlp.h"
 

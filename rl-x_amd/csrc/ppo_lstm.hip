@@ -16,6 +16,7 @@
 #include "lstm_kernels.h"
 #include "ppo_internal.h"
 #include "gemm_bx.h"
+#include "net_pass.h"
 
 namespace rlx {
 
@@ -565,7 +566,6 @@ static int lstm_minibatch(rlx_ctx* ctx, const rlx_lstm_policy_desc& d, const Lst
     int lgrid = div_up(M, 4);
     if (lgrid > ctx->num_cus * 4) lgrid = ctx->num_cus * 4;
     const int64_t E = L.E, H = L.H;
-    auto a64 = [](size_t n) { return (n + 63) & ~size_t(63); };
     size_t need = stage_dw_floats(ctx, M, L.D2, L.D3) + stage_dw_floats(ctx, M, L.D1, L.D2) + a64((size_t)lgrid * 2 * L.D1) +
                   stage_dw_floats(ctx, M, L.K1, L.D1) + a64((size_t)lgrid * 2 * H) +
                   (L.film ? stage_dw_floats(ctx, M, (int)H, (int)(2 * E)) : 0) +

@@ -17,6 +17,7 @@
 #include "dist.h"
 #include "ln_kernels.h"
 #include "sac_sample.h"
+#include "net_pass.h"
 
 namespace rlx {
 
@@ -1167,7 +1168,7 @@ int rlx_sac_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
     }
     // split-fp16 weight images of all five networks for the GEMMs of this update (batches >= 4096 rows; the parameters do
     // not change before the optimizer steps at the end): one launch, in front of the fork
-    struct BxAll { rlx_ctx* c; ~BxAll() { bx_release_all(c); } } bx_all{ctx};
+    BxReleaseAll bx_all{ctx};
     bool emit_images = false;
     if (B >= 4096) {
       const bool pw = pdesc->in_dim > 32, qw = true;   // critics always run their first layer on the GEMM kernels

@@ -4,9 +4,9 @@
 Two updates per case, injected noise: step 1 from zero moments, then step 2 started from the twin's state after step 1
 (teacher-forced: the bars measure the kernels, not two steps of drift).  All 11 state vectors and the 17 metrics are compared.
 The paths each case is there for, worked out from the host selection code (k_mpo_sample_l1<4> for H <= 256 else <8> with
-NJ = H / 64; fs_head_bwd's NJ / untiled choice; stage_dw's split-operand engine for M >= 4096 rows (bx_dw_usable); mp_images
-for T = 3 S B >= 4096 target rows; mp_fwd's LayerNorm grid cap num_cus 8 workgroups of 4 rows, mp_bwd_rows_grid's num_cus 4
-of 16 rows, mp_grid's 4096 blocks of 256 elements); R = 2B stacked rows:
+NJ = H / 64; fs_head_bwd's NJ / untiled choice; stage_dw's split-operand engine for M >= 4096 rows (bx_dw_usable); net_images
+for T = 3 S B >= 4096 target rows; rows_grid's cap (mp_fwd's LayerNorm) of num_cus 8 workgroups of 4 rows, bwd_rows_grid's num_cus 4
+of 16 rows, elem_grid's 4096 blocks of 256 elements -- net_pass.h); R = 2B stacked rows:
 
 | case      | O / Op / Oc   | A  | H   | NA  | B             | S  | also                      | paths                                        |
 |-----------|---------------|----|-----|-----|---------------|----|---------------------------|----------------------------------------------|
@@ -38,7 +38,7 @@ Also: mid-training states at the default size (step 37, non-zero moments in all 
 initial values, alpha ~ 1000, a target policy with sigma ~ 0.02-0.05 and one with sigma ~ 0.006-0.009): the twin measures the
 actor's trunk gradients scaled as the split engine would scale them (bx_grad_scale) against fp16's range -- 3.8x headroom at
 sigma 0.028, none at sigma 0.007, where the split engine returned a NaN gradient norm; acting at A 1 and A 64 with H 512 past
-mp_grid's cap, with and without action_rescaling, sampled and deterministic; and the refusals for every field of rlx_mpo_desc /
+elem_grid's cap, with and without action_rescaling, sampled and deterministic; and the refusals for every field of rlx_mpo_desc /
 rlx_mpo_hparams / the call arguments that were not yet tested, each before any device work."""
 import re
 
@@ -128,7 +128,7 @@ NAMES = ["wide", "act64", "narrow", "tiles", "many_rows"]
 
 
 def _head_nj(K, N):
-    """fastsac.hip fs_head_bwd: the tiled kernel's NJ (2 / 4 / 8 / 12), 0 = the untiled kernel"""
+    """dense_head.hip fs_head_bwd: the tiled kernel's NJ (2 / 4 / 8 / 12), 0 = the untiled kernel"""
     TK = K // 8
     TN = 256 // TK if 0 < TK <= 256 else 0
     nj = -(-N // TN) if TN else 99
@@ -303,7 +303,7 @@ def test_mid_training_state_at_the_default_size(ctx, dev, name):
 # ----------------------------------------------------------------------------------------------------------------------- acting
 def _act_cases():
     return {"a1": dict(seed=91, N=300, O=7, A=1, H=64, Op=None),
-            "a64": dict(seed=92, N=16385, O=40, A=64, H=512, Op=29)}       # N A > mp_grid's 4096 x 256: grid-stride
+            "a64": dict(seed=92, N=16385, O=40, A=64, H=512, Op=29)}       # N A > elem_grid's 4096 x 256: grid-stride
 
 
 @pytest.mark.parametrize("rescale", [False, True])

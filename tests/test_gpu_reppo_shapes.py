@@ -2,8 +2,8 @@
 (tests/reppo_twin.py), at the bars of test_gpu_reppo.py (tests/reppo_cases.py).
 
 Critic step (two, so the second sees non-zero Adam moments) and policy step per case, injected noise.  The paths each case is
-there for, worked out from the host selection code (fs_head_bwd's NJ / untiled choice, rp_critic_bwd's dx_cols_ok,
-rp_rows_grid / rp_bwd_rows_grid, k_rp_sample's 256 / A rows per workgroup):
+there for, worked out from the host selection code (fs_head_bwd's NJ / untiled choice, rp_critic_bwd's dx_cols_ok (first_layer_dx),
+rows_grid / bwd_rows_grid of net_pass.h, k_rp_sample's 256 / A rows per workgroup):
 
 | case      | Hp / Hc   | A  | NB  | K  | B             | also                               | paths                                       |
 |-----------|-----------|----|-----|----|---------------|------------------------------------|---------------------------------------------|
@@ -173,7 +173,7 @@ def _act_cases():
     return {"a1": dict(N=300, A=1, Hp=64, Hc=64, NB=21),
             "a64": dict(N=301, A=64, Hp=64, Hc=128, NB=65),
             "h768": dict(N=257, A=6, Hp=768, Hc=768, NB=256, v_min=-100.0, v_max=100.0),
-            "rows": dict(N=32 * _num_cus() + 29, A=3, Hp=64, Hc=64, NB=51)}   # above rp_rows_grid's cap: a second grid-stride pass
+            "rows": dict(N=32 * _num_cus() + 29, A=3, Hp=64, Hc=64, NB=51)}   # above rows_grid's cap: a second grid-stride pass
 
 
 @pytest.mark.parametrize("name", ["a1", "a64", "h768", "rows"])
