@@ -1,6 +1,7 @@
 // dense_head.hip -- the kernels every network pass of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip shares (net_pass.h declares
-// their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat
-// and the N(0, 1) noise block.
+// their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat,
+// the N(0, 1) noise block, and the row norm + activation kernels of a Block with their one launcher (norm_act).
+#include "ln_kernels.h"
 #include "net_pass.h"
 
 namespace rlx {
@@ -171,6 +172,76 @@ __global__ __launch_bounds__(256) void k_normal_noise(float* __restrict__ out, i
     out[i] = normal_from_bits(random_bits_at(k0, k1, (uint64_t)i, (uint64_t)n, scheme));
 }
 
+// torch.nn.RMSNorm(D) (weight only) + activation over [M, D], D % 64 == 0, D <= 768: one wave per row.
+//   fwd: Y = act((Z * rsqrt(mean(Z^2) + eps)) * g)          (Z kept for the backward)
+//   bwd: dY (in place) -> dZ = r (dxh - xh mean(dxh xh)),  dxh = dY act'(y) g;  per-block partial dg -> partials[grid][D]
+// SiLU' comes from the recomputed pre-activation (ln_kernels.h does the same for the LayerNorm blocks).
+template <bool BWD, int ACT>
+__global__ __launch_bounds__(256) void k_rms_act(const float* __restrict__ Z, float* __restrict__ Y, const float* __restrict__ g,
+                                                 float* __restrict__ partials, int64_t M, int D, float eps) {
+  constexpr int NJMAX = 12;
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // bwd: [4][D]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int NJ = D >> 6;
+  float gam[NJMAX], dg[NJMAX];
+#pragma unroll
+  for (int j = 0; j < NJMAX; ++j) {
+    gam[j] = j < NJ ? g[lane + 64 * j] : 0.f;
+    dg[j] = 0.f;
+  }
+  const float invD = 1.0f / (float)D;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + w; row < M; row += (int64_t)gridDim.x * 4) {
+    float z[NJMAX], dy[NJMAX];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j) {
+      z[j] = j < NJ ? Z[row * D + lane + 64 * j] : 0.f;
+      if (BWD) dy[j] = j < NJ ? Y[row * D + lane + 64 * j] : 0.f;
+      ss += z[j] * z[j];
+    }
+    ss = wave_sum(ss);
+    const float r = rsqrtf(ss * invD + eps);
+    if (!BWD) {
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) {
+          const float y = (z[j] * r) * gam[j];
+          Y[row * D + lane + 64 * j] = ACT == RLX_ACT_SILU ? silu_fwd(y) : y;
+        }
+    } else {
+      float m2 = 0.f, xh[NJMAX], dxh[NJMAX];
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j) {
+        xh[j] = z[j] * r;
+        const float y = xh[j] * gam[j];
+        const float d = (j < NJ) ? dy[j] * (ACT == RLX_ACT_SILU ? silu_grad(y) : 1.f) : 0.f;
+        dg[j] += d * xh[j];
+        dxh[j] = d * gam[j];
+        m2 += dxh[j] * xh[j];
+      }
+      m2 = wave_sum(m2) * invD;
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) Y[row * D + lane + 64 * j] = r * (dxh[j] - xh[j] * m2);
+    }
+  }
+  if (BWD) {
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j)
+      if (j < NJ) smem[w * D + lane + 64 * j] = dg[j];
+    __syncthreads();
+    for (int i = threadIdx.x; i < D; i += 256)
+      partials[(int64_t)blockIdx.x * D + i] = (smem[i] + smem[D + i]) + (smem[2 * D + i] + smem[3 * D + i]);
+  }
+}
+
+// LayerNorm(eps 1e-5) + tanh, forward / backward (ln_kernels.h with torch's eps and the activation as a compile-time constant)
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_mpo_ln_tanh(const float* __restrict__ Z, float* __restrict__ Y, const float* __restrict__ g,
+                                                     const float* __restrict__ be, float* __restrict__ partials, int64_t M, int D) {
+  ln_act_body<BWD, 8, RLX_ACT_TANH>(Z, Y, g, be, partials, M, D, RLX_ACT_TANH, MPO_LN_EPS);
+}
+
 int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st) {
   hipLaunchKernelGGL(k_fs_head_fwd, dim3(div_up(M, 8), div_up(N, 128)), dim3(128), 0, st, H, W, b, out, M, K, N);
   RLX_LAUNCH_CHECK();
@@ -227,6 +298,26 @@ int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int sch
   hipLaunchKernelGGL(k_normal_noise, dim3(elem_grid(n)), dim3(256), 0, st, out, n, k0, k1, scheme);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
+}
+
+template <bool BWD>
+static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st) {
+  const int D = o.out;
+  const size_t row = BWD ? (size_t)D * sizeof(float) : 0;   // LDS: four waves of [dg | db] (LayerNorm) or [dg] (RMSNorm)
+  const bool ln = o.norm == NORM_LAYER, th = o.act == RLX_ACT_TANH;
+  RLX_REQUIRE(D % 64 == 0 && D <= (th ? 512 : 768), RLX_EUNSUP, "norm_act: the row-norm kernels hold a row in one wave");
+  if (ln && o.act == RLX_ACT_SILU)      // (the activation as a run-time argument: k_ln_act_wide takes the switch once per launch)
+    hipLaunchKernelGGL(k_ln_act_wide<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.act, o.eps);
+  else if (ln && th && o.eps == MPO_LN_EPS)
+    hipLaunchKernelGGL(k_mpo_ln_tanh<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D);
+  else if (o.norm == NORM_RMS && o.act == RLX_ACT_SILU)
+    hipLaunchKernelGGL((k_rms_act<BWD, RLX_ACT_SILU>), dim3(grid), dim3(256), 4 * row, st, Z, Y, p + o.g, part, M, D, o.eps);
+  else RLX_REQUIRE(false, RLX_EUNSUP, "norm_act: no kernel for this (norm, activation, eps)");
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st) {
+  return part ? norm_act_t<true>(o, p, Z, Y, part, grid, M, st) : norm_act_t<false>(o, p, Z, Y, part, grid, M, st);
 }
 
 }  // namespace rlx

@@ -5,28 +5,20 @@
 // Dense head -- rlx_lnmlp_desc.  They are composed from the library's GEMM stages (launch_gemm_fwd / stage_dx / stage_dw: the
 // exact-fp32 MFMA engine below 4096 rows, the split-operand engine from there on -- trunk_images, net_pass.h), the dense-head
 // kernels of dense_head.hip and the row-wise LayerNorm + activation kernels of ln_kernels.h (k_ln_act_wide: widths up to 768,
-// eps argument, SiLU' from the recomputed pre-activation).  Arena, grids, key splitting and the backward tails shared with
-// fasttd3.hip, reppo.hip and mpo.hip are in net_pass.h.  CPU twin: oracle/fastsac.py,
+// eps argument, SiLU' from the recomputed pre-activation).  A network is a Chain of such blocks: its carve, forward, backward
+// and stage-arena size, with the arena, grids and key splitting, are net_pass.h's, shared with fasttd3.hip, reppo.hip and
+// mpo.hip; this file keeps the descriptor check, the losses and the update's streams.  CPU twin: oracle/fastsac.py,
 // pinned by outputs of the reference's own modules and closures (tests/golden/reference_fastsac.npz).
 //
 // Noise: the reference draws with torch's CUDA generator (Normal.rsample), which no other implementation reproduces; the
 // library uses its counter RNG (threefry, the key split per call like rlx_sac_*), and rlx_dbg_set_sac_noise injects a given
 // eps for parity tests.
-#include "ln_kernels.h"
 #include "net_pass.h"
 
 namespace rlx {
 
 constexpr float FS_LN_EPS = 1e-5f;          // torch.nn.LayerNorm default
 constexpr float FS_LOG_SQRT_2PI = 0.91893853320467274178f;
-
-struct LnLayer { int in, out; int64_t W, b, g, be; };
-struct LnLayout {
-  int n_hidden;
-  LnLayer layer[4];
-  int head_in, head_out;
-  int64_t hW, hb, n_params;
-};
 
 static int ln_check(const rlx_lnmlp_desc& d) {
   RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 4 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL, "rlx_lnmlp_desc: 1..4 hidden layers, positive widths");
@@ -36,97 +28,8 @@ static int ln_check(const rlx_lnmlp_desc& d) {
   return RLX_OK;
 }
 
-static LnLayout ln_layout(const rlx_lnmlp_desc& d) {
-  LnLayout L{};
-  L.n_hidden = d.n_hidden;
-  int64_t off = 0;
-  int in = d.in_dim;
-  for (int l = 0; l < d.n_hidden; ++l) {
-    LnLayer& o = L.layer[l];
-    o.in = in; o.out = d.hidden[l];
-    o.W = off; off += (int64_t)in * o.out;
-    o.b = off; off += o.out;
-    o.g = off; off += o.out;
-    o.be = off; off += o.out;
-    in = o.out;
-  }
-  L.head_in = in; L.head_out = d.out_dim;
-  L.hW = off; off += (int64_t)in * d.out_dim;
-  L.hb = off; off += d.out_dim;
-  L.n_params = off;
-  return L;
-}
-
-struct LnBufs { float* Z[4]; float* H[4]; };   // [M, out_l]: pre-LayerNorm values, activations (the backward reuses H_l for dH_l / dZ_l)
-
-static void ln_carve(const LnLayout& L, int64_t M, Arena& a, LnBufs* b) {
-  for (int l = 0; l < L.n_hidden; ++l) {
-    b->Z[l] = a.take((size_t)M * L.layer[l].out);
-    b->H[l] = a.take((size_t)M * L.layer[l].out);
-  }
-}
-
-using FsNet = NetRef<LnLayout>;   // parameter vector, layout, whether the pass needs the transposed images (input gradients)
-
-// forward through all hidden layers and the head; x: [M, in] with row stride ldx (a multiple of four, zero padded)
-static int ln_fwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* x, int ldx, const LnBufs& b, float* head_out, int64_t M,
-                  hipStream_t st) {
-  const float* h = x;
-  int ld = ldx;
-  for (int l = 0; l < L.n_hidden; ++l) {
-    const LnLayer& o = L.layer[l];
-    int rc = launch_gemm_fwd(ctx, h, p + o.W, p + o.b, b.Z[l], M, o.out, o.in, RLX_ACT_NONE, st, ld, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ln_act_wide<false>, dim3(rows_grid(ctx, M)), dim3(256), 0, st, (const float*)b.Z[l], b.H[l], p + o.g, p + o.be,
-                       (float*)nullptr, M, o.out, RLX_ACT_SILU, FS_LN_EPS);
-    RLX_LAUNCH_CHECK();
-    h = b.H[l];
-    ld = o.out;
-  }
-  return fs_head_fwd(h, p + L.hW, p + L.hb, head_out, M, L.head_in, L.head_out, st);
-}
-
-// floats the partial-sum buffers of one ln_bwd take from the deferred-reduction arena (stage_alloc rounds each to 64)
-static size_t ln_bwd_stage_floats(const rlx_ctx* ctx, const LnLayout& L, int64_t M, bool grads) {
-  size_t n = 0;
-  if (grads) n += head_stage_floats(L.head_in, L.head_out, M);
-  for (int l = 0; l < L.n_hidden; ++l) {
-    n += a64((size_t)bwd_rows_grid(ctx, M) * 2 * L.layer[l].out);
-    if (grads) n += a64(stage_dw_floats(ctx, M, L.layer[l].in, L.layer[l].out));
-  }
-  return n;
-}
-// backward from d_head [M, head_out].  grads != NULL: parameter gradients (flat layout); dx != NULL: input gradient [M, in] (row
-// stride lddx).  The activation buffers are consumed (dH_l / dZ_l overwrite H_l).
-// dx_nc > 0: only the input columns [dx_c0, dx_c0 + dx_nc) (the policy loss wants dQ/da, 12 of 60 columns: the column-restricted
-// product instead of an exact-fp32 GEMM over all of them -- 98 us x 4 per vector step were the one exact-engine GEMM of the step)
-static int ln_bwd(rlx_ctx* ctx, const LnLayout& L, const float* p, const float* x, int ldx, const LnBufs& b, const float* d_head,
-                  float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
-  const int last = L.n_hidden - 1;
-  int rc;
-  // head: weight / bias gradients from H_last, then dH_last over it
-  rc = fs_head_bwd(ctx, b.H[last], p + L.hW, d_head, grads ? grads + L.hW : nullptr, grads ? grads + L.hb : nullptr, M, L.head_in,
-                   L.head_out, st);
-  if (rc) return rc;
-  for (int l = last; l >= 0; --l) {
-    const LnLayer& o = L.layer[l];
-    const int grid = bwd_rows_grid(ctx, M);
-    float* part = stage_alloc(ctx, (size_t)grid * 2 * o.out);
-    if (!part) return RLX_ENOMEM;
-    hipLaunchKernelGGL(k_ln_act_wide<true>, dim3(grid), dim3(256), (size_t)8 * o.out * sizeof(float), st, (const float*)b.Z[l], b.H[l],
-                       p + o.g, p + o.be, part, M, o.out, RLX_ACT_SILU, FS_LN_EPS);
-    RLX_LAUNCH_CHECK();
-    if (grads) {
-      rc = norm_bwd_reduce(ctx, part, grid, o.out, grads + o.g, grads + o.be, st);
-      if (rc) return rc;
-      rc = stage_dw(ctx, l == 0 ? x : b.H[l - 1], l == 0 ? ldx : o.in, b.H[l], M, o.in, o.out, grads + o.W, grads + o.b, nullptr, nullptr, st);
-      if (rc) return rc;
-    }
-    if (l > 0) rc = stage_dx(ctx, b.H[l], p + o.W, b.H[l - 1], M, o.out, o.in, o.in, RLX_ACT_NONE, 0, st, nullptr);
-    else if (dx) rc = first_layer_dx(ctx, b.H[0], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
-    if (rc) return rc;
-  }
-  return RLX_OK;
+static Chain ln_layout(const rlx_lnmlp_desc& d) {
+  return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_LAYER, RLX_ACT_SILU, FS_LN_EPS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
@@ -407,12 +310,12 @@ int rlx_lnmlp_fwd_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* d, const float* params
   int rc = ln_check(*d);
   if (rc) return rc;
   bx_release_all(ctx);
-  const LnLayout L = ln_layout(*d);
+  const Chain L = ln_layout(*d);
   const int ldp = (d->in_dim + 3) & ~3;
-  LnBufs b;
+  ChainBufs b;
   float* xp;                         // the rows at a 16-byte pitch, when the caller's are not
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    ln_carve(L, M, a, &b);
+    chain_carve(L, M, a, &b);
     xp = a.take((size_t)M * ldp);
   });
   if (rc) return rc;
@@ -423,7 +326,7 @@ int rlx_lnmlp_fwd_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* d, const float* params
     x = xp;
     ldx = ldp;
   }
-  return ln_fwd(ctx, L, params, x, ldx, b, out, M, (hipStream_t)stream);
+  return chain_fwd(ctx, L, params, x, ldx, b, out, M, (hipStream_t)stream);
 }
 
 int rlx_fastsac_replay_sample_f32(rlx_ctx* ctx, const float* ring_states, const float* ring_next_states, const float* ring_actions,
@@ -457,18 +360,18 @@ int rlx_fastsac_act_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, const float* 
   const int A = pdesc->out_dim / 2;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const LnLayout L = ln_layout(*pdesc);
+  const Chain L = ln_layout(*pdesc);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  LnBufs b;
+  ChainBufs b;
   float *head, *xs;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    ln_carve(L, N, a, &b);
+    chain_carve(L, N, a, &b);
     head = a.take((size_t)N * 2 * A);
     xs = a.take((size_t)N * ldp);
   });
   if (rc) return rc;
   rc = fs_concat(obs, pdesc->in_dim, nullptr, 0, xs, ldp, N, st);
-  if (!rc) rc = ln_fwd(ctx, L, pparams, xs, ldp, b, head, N, st);
+  if (!rc) rc = chain_fwd(ctx, L, pparams, xs, ldp, b, head, N, st);
   if (rc) return rc;
   uint32_t sub[2] = {0, 0};
   if (!deterministic) next_key(key_io, sub, 1, scheme);      // key, subkey = split(key)
@@ -496,18 +399,18 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   const float* cn = critic_next_states ? critic_next_states : next_states;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const LnLayout LP = ln_layout(*pdesc), LQ = ln_layout(*qdesc);
+  const Chain LP = ln_layout(*pdesc), LQ = ln_layout(*qdesc);
   const int64_t nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3;
   // ---- arena: policy activations, one set for the two target passes (inference), two sets for the online critics
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  LnBufs bp, bt, b1, b2;
+  ChainBufs bp, bt, b1, b2;
   float *xc, *xn, *head, *lt1, *lt2, *l1, *l2, *d1, *d2, *lpn, *gq, *xs, *c51o;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    ln_carve(LP, B, a, &bp);
-    ln_carve(LQ, B, a, &bt);
-    ln_carve(LQ, B, a, &b1);
-    ln_carve(LQ, B, a, &b2);
+    chain_carve(LP, B, a, &bp);
+    chain_carve(LQ, B, a, &bt);
+    chain_carve(LQ, B, a, &b1);
+    chain_carve(LQ, B, a, &b2);
     xc = a.take((size_t)B * ldc);
     xn = a.take((size_t)B * ldc);
     head = a.take((size_t)B * 2 * A);
@@ -523,7 +426,7 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   next_key(key_io, ks, 1, scheme);                              // key, subkey = split(key)
   BxReleaseAll bx_all{ctx};
   {
-    const FsNet nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    const NetRef nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
     rc = trunk_images(ctx, nets, 5, B, st);
     if (rc) return rc;
   }
@@ -536,15 +439,15 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   rc = fs_concat(cs, Oc, actions, A, xc, ldc, B, st);
   if (!rc) rc = fk.fork();
   // ---- online critics on (s, a)
-  if (!rc) rc = ln_fwd(ctx, LQ, qparams, xc, ldc, b1, l1, B, fk.side());
-  if (!rc) rc = ln_fwd(ctx, LQ, qparams + nq, xc, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams, xc, ldc, b1, l1, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams + nq, xc, ldc, b2, l2, B, fk.side());
   // ---- next action and log-prob from the policy (no gradient), target critics on (s', a')
   if (!rc) rc = fs_concat(cn, Oc, nullptr, A, xn, ldc, B, fk.main());
   if (!rc) rc = fs_concat(next_states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
-  if (!rc) rc = ln_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
+  if (!rc) rc = chain_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
   if (!rc) rc = fs_sample(head, action_scale, ks, scheme, ctx->dbg_sac_eps[0], xn, ldc, Oc, lpn, B, A, *hp, 0, 0, B, st);
-  if (!rc) rc = ln_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
-  if (!rc) rc = ln_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
+  if (!rc) rc = chain_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
+  if (!rc) rc = chain_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
   if (!rc) rc = fk.join();
   // ---- the C51 loss and its logit gradients
   if (!rc) rc = rlx_c51_critic_loss_f32(ctx, l1, l2, lt1, lt2, rewards, dones, truncations, effective_n_steps, lpn, log_alpha, B, NA, hp->gamma,
@@ -553,10 +456,10 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   {
     GradScaleScope gscope(ctx, bx_grad_scale(B));   // d logits ~ 1 / B
     FsDefer defer(ctx);
-    rc = defer.begin(2 * ln_bwd_stage_floats(ctx, LQ, B, true));
+    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, true));
     if (!rc) rc = fk.fork();
-    if (!rc) rc = ln_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
-    if (!rc) rc = ln_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
     if (!rc) rc = fk.join();
     if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
     if (rc) return rc;
@@ -592,17 +495,17 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
   const float* cs = critic_states ? critic_states : states;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const LnLayout LP = ln_layout(*pdesc), LQ = ln_layout(*qdesc);
+  const Chain LP = ln_layout(*pdesc), LQ = ln_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3;
   const int nblk = div_up(B, 4);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  LnBufs bp, b1, b2;
+  ChainBufs bp, b1, b2;
   float *xp, *dx1, *dx2, *head, *dhead, *l1, *l2, *d1, *d2, *lp, *part, *gp, *xs;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    ln_carve(LP, B, a, &bp);
-    ln_carve(LQ, B, a, &b1);
-    ln_carve(LQ, B, a, &b2);
+    chain_carve(LP, B, a, &bp);
+    chain_carve(LQ, B, a, &b1);
+    chain_carve(LQ, B, a, &b2);
     for (float** x : {&xp, &dx1, &dx2}) *x = a.take((size_t)B * ldc);
     head = a.take((size_t)B * 2 * A);
     dhead = a.take((size_t)B * 2 * A);
@@ -619,20 +522,20 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
   const float inv_b = 1.0f / (float)B;
   BxReleaseAll bx_all{ctx};
   {
-    const FsNet nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    const NetRef nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
     rc = trunk_images(ctx, nets, 3, B, st);
     if (rc) return rc;
   }
   // policy on s, sampled action into the critics' input rows, both critics, seeds
   rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
   if (!rc) rc = fs_concat(states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
-  if (!rc) rc = ln_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
+  if (!rc) rc = chain_fwd(ctx, LP, pparams, xs, ldp, bp, head, B, st);
   if (!rc) rc = fs_sample(head, action_scale, ks, scheme, ctx->dbg_sac_eps[1], xp, ldc, Oc, lp, B, A, *hp, 0, 0, B, st);
   FsFork fk(ctx, st);
   if (!rc) rc = fk.begin();
   if (!rc) rc = fk.fork();
-  if (!rc) rc = ln_fwd(ctx, LQ, qparams + nq, xp, ldc, b2, l2, B, fk.side());
-  if (!rc) rc = ln_fwd(ctx, LQ, qparams, xp, ldc, b1, l1, B, fk.main());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams + nq, xp, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams, xp, ldc, b1, l1, B, fk.main());
   if (!rc) rc = fk.join();
   if (rc) return rc;
   hipLaunchKernelGGL(k_fs_policy_seed, dim3(nblk), dim3(256), 0, st, (const float*)l1, (const float*)l2, (const float*)lp, log_alpha, d1, d2,
@@ -641,12 +544,12 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
   {
     GradScaleScope gscope(ctx, bx_grad_scale(B));
     FsDefer defer(ctx);
-    rc = defer.begin(2 * ln_bwd_stage_floats(ctx, LQ, B, false) + ln_bwd_stage_floats(ctx, LP, B, true));
+    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
     if (rc) return rc;
     // the critics' input gradients (no parameter gradients; one critic per stream), then the policy's backward
     rc = fk.fork();
-    if (!rc) rc = ln_bwd(ctx, LQ, qparams + nq, xp, ldc, b2, d2, nullptr, dx2, ldc, B, fk.side(), Oc, A);
-    if (!rc) rc = ln_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams + nq, xp, ldc, b2, d2, nullptr, dx2, ldc, B, fk.side(), Oc, A);
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
     if (!rc) rc = fk.join();
     if (rc) return rc;
     int grid = div_up(B * A, 256);
@@ -655,7 +558,7 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
                        scheme, (const float*)dx1, (const float*)dx2, ldc, Oc, log_alpha, dhead, B, A, hp->log_std_min, hp->log_std_max, inv_b,
                        (int64_t)0, B);
     RLX_LAUNCH_CHECK();
-    rc = ln_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
+    rc = chain_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
     if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
     if (rc) return rc;
   }

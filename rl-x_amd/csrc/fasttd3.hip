@@ -4,11 +4,12 @@
 //
 // Networks (policy.py:38-47, q_network.py:28-36): plain Dense -> ReLU trunks and a Dense head -- rlx_mlp_desc with act = RELU,
 // ln_first = 0, has_logstd = 0 (flat layout: per layer W[in, out] row-major, b[out]; then the head), hidden widths multiples of
-// 64 up to 1024 (td3_check: the PPO / SAC check mlp_check_desc stays as it is).  The trunks are the library's GEMM stages with
-// the fused bias + ReLU epilogue (launch_gemm_fwd) and the ReLU' input-gradient epilogue (stage_dx), the split-operand engine
-// for passes of >= 4096 rows (trunk_images, net_pass.h), stage_dw for the weight gradients; the heads are dense_head.hip's
-// k_fs_head_* kernels (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head kernel k_td3_head_act
-// below.  Arena, grids, key splitting and the first layer's input gradient: net_pass.h, shared with fastsac.hip.
+// 64 up to 1024 (td3_check: the PPO / SAC check mlp_check_desc stays as it is).  A network is net_pass.h's Chain of plain blocks:
+// the library's GEMM stages with the fused bias + ReLU epilogue (launch_gemm_fwd) and the ReLU' input-gradient epilogue
+// (stage_dx), the split-operand engine for passes of >= 4096 rows (trunk_images), stage_dw for the weight gradients; the heads
+// are dense_head.hip's k_fs_head_* kernels (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head
+// kernel k_td3_head_act below.  Carve, forward, backward, stage-arena size, grids and key splitting: net_pass.h, shared with
+// fastsac.hip, reppo.hip and mpo.hip.
 //
 // fp16 window: the split-operand engine holds |weight| < 1023, |activation| < 4094, per-sample gradient < 8190.
 // ReLU activations are not bounded by a LayerNorm; a value outside the window turns the affected products into inf / NaN, the
@@ -34,60 +35,13 @@ static int td3_check(const rlx_mlp_desc& d) {
   return RLX_OK;
 }
 
-struct TdBufs { float* H[3]; };   // [M, out_l] ReLU outputs (the backward overwrites H_l with dZ_l)
-
-static void td3_carve(const MlpLayout& L, int64_t M, Arena& a, TdBufs* b) {
-  for (int l = 0; l < L.n_hidden; ++l) b->H[l] = a.take((size_t)M * L.layer[l].out);
+static Chain td3_layout(const rlx_mlp_desc& d) {   // the flat layout of rlx_mlp_desc without LayerNorm and log-std
+  return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_NONE, RLX_ACT_RELU);
 }
-
-using TdNet = NetRef<MlpLayout>;   // parameter vector, layout, whether the pass needs the transposed images (input gradients)
-
-// trunk forward (Dense + bias + ReLU fused in the GEMM epilogue), then the head when head_out != NULL; x: [M, in], row stride
-// ldx (a multiple of four, zero padded)
-static int td3_fwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float* x, int ldx, const TdBufs& b, float* head_out, int64_t M,
-                   hipStream_t st) {
-  const float* h = x;
-  int ld = ldx;
-  for (int l = 0; l < L.n_hidden; ++l) {
-    const LayerOff& o = L.layer[l];
-    const int rc = launch_gemm_fwd(ctx, h, p + o.W, p + o.b, b.H[l], M, o.out, o.in, RLX_ACT_RELU, st, ld, nullptr);
-    if (rc) return rc;
-    h = b.H[l];
-    ld = o.out;
-  }
-  if (!head_out) return RLX_OK;
-  return fs_head_fwd(h, p + L.head.W, p + L.head.b, head_out, M, L.head.in, L.head.out, st);
-}
-
-// floats the partial-sum buffers of one td3_bwd take from the deferred-reduction arena (head slabs: fs_head_bwd uses at most
-// div_up(M, 32) of them)
-static size_t td3_stage_floats(const rlx_ctx* ctx, const MlpLayout& L, int64_t M, bool grads) {
-  if (!grads) return 0;
-  size_t n = head_stage_floats(L.head.in, L.head.out, M);
-  for (int l = 0; l < L.n_hidden; ++l) n += a64(stage_dw_floats(ctx, M, L.layer[l].in, L.layer[l].out));
-  return n;
-}
-
-// backward from d_head [M, head_out].  grads != NULL: parameter gradients (flat layout); dx != NULL: input gradient (row stride
-// lddx), only the columns [dx_c0, dx_c0 + dx_nc) when dx_nc > 0 (the policy loss wants dQ/da: the column-restricted product).
-// The activation buffers are consumed (dZ_l overwrites H_l; ReLU' = (H_l > 0) is applied by the launch that overwrites it).
-static int td3_bwd(rlx_ctx* ctx, const MlpLayout& L, const float* p, const float* x, int ldx, const TdBufs& b, const float* d_head,
+// chain_bwd with the head's input gradient times ReLU'(H_last): H_l holds the ReLU output, each dZ_l overwrites it
+static int td3_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, const float* d_head,
                    float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
-  const int last = L.n_hidden - 1;
-  int rc = fs_head_bwd(ctx, b.H[last], p + L.head.W, d_head, grads ? grads + L.head.W : nullptr, grads ? grads + L.head.b : nullptr, M,
-                       L.head.in, L.head.out, st, /*relu_mask*/ true);
-  if (rc) return rc;
-  for (int l = last; l >= 0; --l) {
-    const LayerOff& o = L.layer[l];
-    if (grads) {
-      rc = stage_dw(ctx, l == 0 ? x : b.H[l - 1], l == 0 ? ldx : o.in, b.H[l], M, o.in, o.out, grads + o.W, grads + o.b, nullptr, nullptr, st);
-      if (rc) return rc;
-    }
-    if (l > 0) rc = stage_dx(ctx, b.H[l], p + o.W, b.H[l - 1], M, o.out, o.in, o.in, RLX_ACT_RELU, 1, st);
-    else if (dx) rc = first_layer_dx(ctx, b.H[0], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
-    if (rc) return rc;
-  }
-  return RLX_OK;
+  return chain_bwd(ctx, L, p, x, ldx, b, d_head, grads, dx, lddx, M, st, dx_c0, dx_nc, /*relu_mask*/ true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
@@ -222,7 +176,7 @@ __global__ __launch_bounds__(256) void k_td3_policy_loss(const float* __restrict
   if (threadIdx.x == 0) metrics[0] = ((s_buf[0] + s_buf[1]) + (s_buf[2] + s_buf[3])) * inv_b;
 }
 
-static int td3_head_act(const MlpLayout& L, const float* p, const float* H, int64_t M, int mode, const float* noise_scale, float smooth_eps,
+static int td3_head_act(const Chain& L, const float* p, const float* H, int64_t M, int mode, const float* noise_scale, float smooth_eps,
                         float smooth_clip, const uint32_t ks[2], int scheme, const float* inject, int64_t row_off, int64_t M_global, float* act,
                         int ld, int c0, float* proc, int clip_rescale, const float* low, const float* high, hipStream_t st) {
   const int A = L.head.out;
@@ -275,17 +229,17 @@ int rlx_fasttd3_act_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pp
   RLX_REQUIRE(pdesc->out_dim <= 64, RLX_EUNSUP, "rlx_fasttd3_act_f32: act_dim at most 64");
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const MlpLayout L = make_layout(*pdesc);
+  const Chain L = td3_layout(*pdesc);
   const int ldp = (pdesc->in_dim + 3) & ~3;
-  TdBufs b;
+  ChainBufs b;
   float* xs;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    td3_carve(L, N, a, &b);
+    chain_carve(L, N, a, &b);
     xs = a.take((size_t)N * ldp);
   });
   if (rc) return rc;
   rc = fs_concat(obs, pdesc->in_dim, nullptr, 0, xs, ldp, N, st);
-  if (!rc) rc = td3_fwd(ctx, L, pparams, xs, ldp, b, nullptr, N, st);
+  if (!rc) rc = chain_fwd(ctx, L, pparams, xs, ldp, b, nullptr, N, st);
   if (rc) return rc;
   uint32_t ks[2] = {0, 0};
   if (!deterministic) next_key(key_io, ks, 1, scheme);
@@ -312,17 +266,17 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   const float* cn = critic_next_states ? critic_next_states : next_states;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const MlpLayout LP = make_layout(*pdesc), LQ = make_layout(*qdesc);
+  const Chain LP = td3_layout(*pdesc), LQ = td3_layout(*qdesc);
   const int64_t nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
   // ---- arena: policy trunk, one set for the two target passes (inference, one after the other), two sets for the online critics
-  TdBufs bp, bt, b1, b2;
+  ChainBufs bp, bt, b1, b2;
   float *xc, *xn, *lt1, *lt2, *l1, *l2, *d1, *d2, *zeros, *gq, *xs, *ninf;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    td3_carve(LP, B, a, &bp);
-    td3_carve(LQ, B, a, &bt);
-    td3_carve(LQ, B, a, &b1);
-    td3_carve(LQ, B, a, &b2);
+    chain_carve(LP, B, a, &bp);
+    chain_carve(LQ, B, a, &bt);
+    chain_carve(LQ, B, a, &b1);
+    chain_carve(LQ, B, a, &b2);
     xc = a.take((size_t)B * ldc);
     xn = a.take((size_t)B * ldc);
     for (float** l : {&lt1, &lt2, &l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
@@ -337,7 +291,7 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   next_key(key_io, ks, 1, scheme);
   BxReleaseAll bx_all{ctx};
   {
-    const TdNet nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    const NetRef nets[5] = {{pparams, &LP, false}, {qtarget, &LQ, false}, {qtarget + nq, &LQ, false}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
     rc = trunk_images(ctx, nets, 5, B, st);
     if (rc) return rc;
   }
@@ -347,15 +301,15 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   rc = fk.begin();
   if (!rc) rc = fs_concat(cs, Oc, actions, A, xc, ldc, B, st);
   if (!rc) rc = fk.fork();
-  if (!rc) rc = td3_fwd(ctx, LQ, qparams, xc, ldc, b1, l1, B, fk.side());
-  if (!rc) rc = td3_fwd(ctx, LQ, qparams + nq, xc, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams, xc, ldc, b1, l1, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams + nq, xc, ldc, b2, l2, B, fk.side());
   if (!rc) rc = fs_concat(cn, Oc, nullptr, A, xn, ldc, B, fk.main());
   if (!rc) rc = fs_concat(next_states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
-  if (!rc) rc = td3_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
+  if (!rc) rc = chain_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
   if (!rc) rc = td3_head_act(LP, pparams, bp.H[LP.n_hidden - 1], B, TD_NOISE_SMOOTH, nullptr, hp->smoothing_epsilon, hp->smoothing_clip_value,
                              ks, scheme, ctx->dbg_sac_eps[0], 0, B, xn, ldc, Oc, nullptr, 0, nullptr, nullptr, st);
-  if (!rc) rc = td3_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
-  if (!rc) rc = td3_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
+  if (!rc) rc = chain_fwd(ctx, LQ, qtarget, xn, ldc, bt, lt1, B, st);
+  if (!rc) rc = chain_fwd(ctx, LQ, qtarget + nq, xn, ldc, bt, lt2, B, st);
   if (rc) return rc;
   RLX_HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * sizeof(float), st));
   RLX_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ninf, (int)0xff800000u, 1, st));
@@ -367,7 +321,7 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
   {
     GradScaleScope gscope(ctx, bx_grad_scale(B));   // d logits ~ 1 / B
     FsDefer defer(ctx);
-    rc = defer.begin(2 * td3_stage_floats(ctx, LQ, B, true));
+    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, true));
     if (!rc) rc = fk.fork();
     if (!rc) rc = td3_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
     if (!rc) rc = td3_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
@@ -400,16 +354,16 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
   const float* cs = critic_states ? critic_states : states;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const MlpLayout LP = make_layout(*pdesc), LQ = make_layout(*qdesc);
+  const Chain LP = td3_layout(*pdesc), LQ = td3_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
   const int NA = hp->nr_atoms, ldc = (Oc + A + 3) & ~3, ldp = (pdesc->in_dim + 3) & ~3;
   const int nblk = div_up(B, 4);
-  TdBufs bp, b1, b2;
+  ChainBufs bp, b1, b2;
   float *xp, *dx1, *dx2, *dhead, *l1, *l2, *d1, *d2, *part, *gp, *xs;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
-    td3_carve(LP, B, a, &bp);
-    td3_carve(LQ, B, a, &b1);
-    td3_carve(LQ, B, a, &b2);
+    chain_carve(LP, B, a, &bp);
+    chain_carve(LQ, B, a, &b1);
+    chain_carve(LQ, B, a, &b2);
     for (float** x : {&xp, &dx1, &dx2}) *x = a.take((size_t)B * ldc);
     dhead = a.take((size_t)B * A);
     for (float** l : {&l1, &l2, &d1, &d2}) *l = a.take((size_t)B * NA);
@@ -423,21 +377,21 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
   const uint32_t no_key[2] = {0, 0};
   BxReleaseAll bx_all{ctx};
   {
-    const TdNet nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
+    const NetRef nets[3] = {{pparams, &LP, true}, {qparams, &LQ, true}, {qparams + nq, &LQ, true}};
     rc = trunk_images(ctx, nets, 3, B, st);
     if (rc) return rc;
   }
   // policy on s, its action straight into the critics' input rows, both critics (one per stream), seeds
   rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
   if (!rc) rc = fs_concat(states, pdesc->in_dim, nullptr, 0, xs, ldp, B, st);
-  if (!rc) rc = td3_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
+  if (!rc) rc = chain_fwd(ctx, LP, pparams, xs, ldp, bp, nullptr, B, st);
   if (!rc) rc = td3_head_act(LP, pparams, bp.H[LP.n_hidden - 1], B, TD_NOISE_NONE, nullptr, 0.f, 0.f, no_key, 0, nullptr, 0, B, xp, ldc, Oc,
                              nullptr, 0, nullptr, nullptr, st);
   FsFork fk(ctx, st);
   if (!rc) rc = fk.begin();
   if (!rc) rc = fk.fork();
-  if (!rc) rc = td3_fwd(ctx, LQ, qparams + nq, xp, ldc, b2, l2, B, fk.side());
-  if (!rc) rc = td3_fwd(ctx, LQ, qparams, xp, ldc, b1, l1, B, fk.main());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams + nq, xp, ldc, b2, l2, B, fk.side());
+  if (!rc) rc = chain_fwd(ctx, LQ, qparams, xp, ldc, b1, l1, B, fk.main());
   if (!rc) rc = fk.join();
   if (rc) return rc;
   hipLaunchKernelGGL(k_td3_policy_seed, dim3(nblk), dim3(256), 0, st, (const float*)l1, (const float*)l2, d1, d2, part, B, NA, hp->v_min,
@@ -446,7 +400,7 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
   {
     GradScaleScope gscope(ctx, bx_grad_scale(B));
     FsDefer defer(ctx);
-    rc = defer.begin(2 * td3_stage_floats(ctx, LQ, B, false) + td3_stage_floats(ctx, LP, B, true));
+    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
     if (rc) return rc;
     // the critics' input gradients on the action columns (no parameter gradients; one critic per stream), then the policy's backward
     rc = fk.fork();

@@ -1,7 +1,8 @@
-// net_pass.h -- what the network passes of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip share on the host side: the launchers of
-// dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the common
-// tails of a norm block's and a first layer's backward.  The passes themselves (which layers, which activations, which streams)
-// stay in each algorithm's file.
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip on the host side: the launchers of
+// dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
+// themselves -- a Block (Linear -> {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
+// stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
+// of blocks, the streams, and what differs at the head (a ReLU mask, MPO's ELU copy) or in the graph (REPPO's critic).
 #pragma once
 #include "mlp.h"
 #include "gemm_bx.h"
@@ -21,6 +22,24 @@ int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int
 // out[i] = normal(bits(key, i of n))
 int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int scheme, hipStream_t st);
 
+// ---- blocks: Linear W[in, out], b -> {no norm | LayerNorm scale g, bias be | RMSNorm scale g} -> act; W / b / g / be are
+// offsets in the flat parameter vector (-1: absent), in that order.  The flat layouts are ABI: make_block only advances `off`.
+enum NormKind { NORM_NONE = 0, NORM_LAYER = 1, NORM_RMS = 2 };
+constexpr float MPO_LN_EPS = 1e-5f;   // torch.nn.LayerNorm default (k_mpo_ln_tanh has it compiled in)
+struct Block { int in, out; int64_t W, b, g, be; int norm, act; float eps; };
+static inline Block make_block(int64_t& off, int in, int out, int norm = NORM_NONE, int act = RLX_ACT_NONE, float eps = 0.f) {
+  Block o{in, out, off, 0, -1, -1, norm, act, eps};
+  off += (int64_t)in * out;
+  o.b = off; off += out;
+  if (norm != NORM_NONE) { o.g = off; off += out; }
+  if (norm == NORM_LAYER) { o.be = off; off += out; }
+  return o;
+}
+// row norm + activation of a block over [M, out] (dense_head.hip).  part == NULL: forward Y = act(norm(Z)); else backward: dY (in
+// Y) -> dZ, per-workgroup partials [grid][norm_part_width].  RLX_EUNSUP for a (norm, act) pair without a kernel.
+int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st);
+static inline int norm_part_width(const Block& o) { return (o.be >= 0 ? 2 : 1) * o.out; }   // [d scale | d bias] or [d scale]
+
 // ---- sizes and grids
 static inline size_t a64(size_t n) { return (n + 63) & ~size_t(63); }   // every arena buffer starts on a 256-byte boundary
 
@@ -35,7 +54,10 @@ static inline int rows_grid(const rlx_ctx* ctx, int64_t M) {
   if (grid > ctx->num_cus * 8) grid = ctx->num_cus * 8;
   return grid < 1 ? 1 : grid;
 }
-static inline int bwd_rows_grid(const rlx_ctx* ctx, int64_t M) {   // 16 rows per workgroup: fewer partial slabs (sac.hip: ln_bwd_grid)
+// Row-norm backward: every workgroup leaves a slab of partial sums, and the reduction's workgroups that own a D-long segment add
+// its slabs in a chain of S / 64 dependent round trips -- with one row per wave (1024 workgroups at 4096 rows) that chain was the
+// tail of the whole reduction launch (30 us); 16 rows per workgroup leave 256 slabs.
+static inline int bwd_rows_grid(const rlx_ctx* ctx, int64_t M) {
   int grid = div_up(M, 16);
   if (grid > ctx->num_cus * 4) grid = ctx->num_cus * 4;
   return grid < 1 ? 1 : grid;
@@ -96,23 +118,6 @@ static inline int net_images(rlx_ctx* ctx, const BxMat* mats, int n, int64_t M, 
   ctx->bx_n[1] = ctx->bx_n[0];
   return RLX_OK;
 }
-// the hidden layers of several networks of one layout type (n_hidden, layer[l].{in, out, W}); bwd: the pass needs the transposed
-// images too (input gradients)
-template <class Layout>
-struct NetRef { const float* p; const Layout* L; bool bwd; };
-template <class Layout>
-static int trunk_images(rlx_ctx* ctx, const NetRef<Layout>* nets, int n, int64_t M, hipStream_t st) {
-  BxMat mats[BX_MAX_JOBS];
-  int k = 0;
-  for (int i = 0; i < n; ++i)
-    for (int l = 0; l < nets[i].L->n_hidden; ++l) {
-      const auto& o = nets[i].L->layer[l];
-      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
-      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
-    }
-  return net_images(ctx, mats, k, M, st);
-}
-
 // ---- backward tails
 // The row-norm backward kernels leave per-workgroup partials: [grid][D] of d scale (RMSNorm: g_bias == NULL) or [grid][2 D] of
 // [d scale | d bias] (LayerNorm).  Their column sums, in workgroup order, are the gradients.
@@ -130,6 +135,117 @@ static inline int first_layer_dx(rlx_ctx* ctx, const float* dZ, const float* W, 
                                  int nc, hipStream_t st) {
   if (dx_cols_ok(N, nc)) return launch_dx_cols(dZ, W + (int64_t)c0 * N, dx + c0, M, N, nc, lddx, st);
   return stage_dx(ctx, dZ, W, dx, M, N, Kd, lddx, RLX_ACT_NONE, 0, st, nullptr);
+}
+
+// ---- a block's passes.  x: the block's input [M, in] at row stride ldx; Z: pre-norm values (normed blocks only); H: output
+static inline int block_fwd(rlx_ctx* ctx, const Block& o, const float* p, const float* x, int ldx, float* Z, float* H, int64_t M,
+                            hipStream_t st) {
+  if (o.norm == NORM_NONE) return launch_gemm_fwd(ctx, x, p + o.W, p + o.b, H, M, o.out, o.in, o.act, st, ldx, nullptr);
+  const int rc = launch_gemm_fwd(ctx, x, p + o.W, p + o.b, Z, M, o.out, o.in, RLX_ACT_NONE, st, ldx, nullptr);
+  return rc ? rc : norm_act(o, p, Z, H, nullptr, rows_grid(ctx, M), M, st);
+}
+// H holds dH of a normed block (-> dZ, in place) or dZ of a plain one (act' was applied by whoever wrote it).  grads != NULL: the
+// block's parameter gradients (flat layout) through the deferred reduction; the norm partial is taken either way.
+static inline int block_bwd(rlx_ctx* ctx, const Block& o, const float* p, const float* x, int ldx, const float* Z, float* H, float* grads,
+                            int64_t M, hipStream_t st) {
+  if (o.norm != NORM_NONE) {
+    const int grid = bwd_rows_grid(ctx, M);
+    float* part = stage_alloc(ctx, (size_t)grid * norm_part_width(o));
+    if (!part) return RLX_ENOMEM;
+    int rc = norm_act(o, p, Z, H, part, grid, M, st);
+    if (!rc && grads) rc = norm_bwd_reduce(ctx, part, grid, o.out, grads + o.g, o.be >= 0 ? grads + o.be : nullptr, st);
+    if (rc) return rc;
+  }
+  return grads ? stage_dw(ctx, x, ldx, H, M, o.in, o.out, grads + o.W, grads + o.b, nullptr, nullptr, st) : RLX_OK;
+}
+// floats block_bwd takes from the stage arena: its stage_alloc, and stage_dw's
+static inline size_t block_stage_floats(const rlx_ctx* ctx, const Block& o, int64_t M, bool grads) {
+  return (o.norm != NORM_NONE ? a64((size_t)bwd_rows_grid(ctx, M) * norm_part_width(o)) : 0) +
+         (grads ? a64(stage_dw_floats(ctx, M, o.in, o.out)) : 0);
+}
+// input gradient of block o from its dZ into `out` [M, in].  prev: the block whose output `out` holds -- a plain one gets its act'
+// in the epilogue (out becomes its dZ), a normed one (or NULL) does not
+static inline int block_dx(rlx_ctx* ctx, const Block& o, const Block* prev, const float* p, const float* dZ, float* out, int64_t M,
+                           hipStream_t st) {
+  const bool ep = prev && prev->norm == NORM_NONE && prev->act != RLX_ACT_NONE;
+  return stage_dx(ctx, dZ, p + o.W, out, M, o.out, o.in, o.in, ep ? prev->act : RLX_ACT_NONE, ep ? 1 : 0, st, nullptr);
+}
+
+// ---- a chain of blocks and a dense head
+struct Chain { int n_hidden; Block layer[4]; Block head; int64_t n_params; };
+// n_hidden blocks of one kind with the widths hidden[], then the head
+static inline Chain make_chain(int in, const int* hidden, int n_hidden, int out, int norm, int act, float eps = 0.f) {
+  Chain L{};
+  L.n_hidden = n_hidden;
+  int64_t off = 0;
+  for (int l = 0; l < n_hidden; ++l) {
+    L.layer[l] = make_block(off, in, hidden[l], norm, act, eps);
+    in = hidden[l];
+  }
+  L.head = make_block(off, in, out);
+  L.n_params = off;
+  return L;
+}
+struct ChainBufs { float* Z[4]; float* H[4]; };   // [M, out_l]; the backward overwrites H_l with dH_l / dZ_l
+static inline void chain_carve(const Chain& L, int64_t M, Arena& a, ChainBufs* b) {
+  for (int l = 0; l < L.n_hidden; ++l) {
+    b->Z[l] = L.layer[l].norm != NORM_NONE ? a.take((size_t)M * L.layer[l].out) : nullptr;
+    b->H[l] = a.take((size_t)M * L.layer[l].out);
+  }
+}
+// x: [M, in] at row stride ldx (a multiple of four, zero padded); head_out == NULL: the trunk only
+static inline int chain_fwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, float* head_out,
+                            int64_t M, hipStream_t st) {
+  for (int l = 0; l < L.n_hidden; ++l) {
+    const int rc = block_fwd(ctx, L.layer[l], p, l ? b.H[l - 1] : x, l ? L.layer[l].in : ldx, b.Z[l], b.H[l], M, st);
+    if (rc) return rc;
+  }
+  if (!head_out) return RLX_OK;
+  return fs_head_fwd(b.H[L.n_hidden - 1], p + L.head.W, p + L.head.b, head_out, M, L.head.in, L.head.out, st);
+}
+// Trunk backward from `top` = dH / dZ of the last block (b.H[last], or a copy of it); per block from the last: [norm backward,
+// norm reduce], dW, dX.  dx != NULL: the input gradient (row stride lddx; the columns [dx_c0, dx_c0 + dx_nc) only when dx_nc > 0)
+static inline int chain_trunk_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, float* top,
+                                  float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
+  for (int l = L.n_hidden - 1; l >= 0; --l) {
+    const Block& o = L.layer[l];
+    float* d = l == L.n_hidden - 1 ? top : b.H[l];
+    int rc = block_bwd(ctx, o, p, l ? b.H[l - 1] : x, l ? o.in : ldx, b.Z[l], d, grads, M, st);
+    if (rc) return rc;
+    if (l > 0) rc = block_dx(ctx, o, &L.layer[l - 1], p, d, b.H[l - 1], M, st);
+    else if (dx) rc = first_layer_dx(ctx, d, p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
+    if (rc) return rc;
+  }
+  return RLX_OK;
+}
+// backward from d_head [M, head.out]: the head (with the ReLU' mask of a ReLU trunk), then the trunk.  The buffers are consumed.
+static inline int chain_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, const float* d_head,
+                            float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0,
+                            bool relu_mask = false) {
+  float* top = b.H[L.n_hidden - 1];
+  const int rc = fs_head_bwd(ctx, top, p + L.head.W, d_head, grads ? grads + L.head.W : nullptr, grads ? grads + L.head.b : nullptr, M,
+                             L.head.in, L.head.out, st, relu_mask);
+  return rc ? rc : chain_trunk_bwd(ctx, L, p, x, ldx, b, top, grads, dx, lddx, M, st, dx_c0, dx_nc);
+}
+// floats one backward of the chain takes from the stage arena: fs_head_bwd's slabs and every block's
+static inline size_t chain_stage_floats(const rlx_ctx* ctx, const Chain& L, int64_t M, bool grads) {
+  size_t n = grads ? head_stage_floats(L.head.in, L.head.out, M) : 0;
+  for (int l = 0; l < L.n_hidden; ++l) n += block_stage_floats(ctx, L.layer[l], M, grads);
+  return n;
+}
+
+// weight images of the hidden layers of several chains; bwd: the pass needs the transposed images too (input gradients)
+struct NetRef { const float* p; const Chain* L; bool bwd; };
+static inline int trunk_images(rlx_ctx* ctx, const NetRef* nets, int n, int64_t M, hipStream_t st) {
+  BxMat mats[BX_MAX_JOBS];
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    for (int l = 0; l < nets[i].L->n_hidden; ++l) {
+      const Block& o = nets[i].L->layer[l];
+      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
+      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
+    }
+  return net_images(ctx, mats, k, M, st);
 }
 
 }  // namespace rlx
