@@ -173,6 +173,8 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   "gather_group_rows" (524288: in the two-chain schedules of rlx_ppo_update_f32 / rlx_ppo_update_dist_f32 the rows of that many samples -- one epoch at
  *   configs[1] -- are gathered by ONE launch into one of two alternating buffers, and the chains meet once per group instead of once
  *   per update; 0: one gather per update; needs "gather_records").
+ * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
+ *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,
  *  split recurrent chains, plane-tensor GEMMs with direct-to-LDS staging, ... -- are documented in DESIGN.md Appendix A; their
  *  code lives in the git history only.)                                                                                    */
@@ -841,6 +843,41 @@ int rlx_mpo_update_f32(rlx_ctx*, const rlx_mpo_desc*, float* pparams, float* pm,
                        const float* actions, const float* rewards, const float* dones, const float* truncations,
                        const float* effective_n_steps, int64_t B, uint32_t key_io[2], int scheme, int64_t step, float agent_lr,
                        float dual_lr, const rlx_mpo_hparams* hp, float* metrics_out, void* stream);
+
+/* =================================== ESPO ================================================
+ * Early-stopping policy optimisation (rl_x/algorithms/espo/pytorch).  The nets are PPO's arch A (policy.py:31-38, critic.py:24-30:
+ * two tanh layers of nr_hidden_units; the policy has the trailing policy_logstd), so acting, next values and GAE are
+ * rlx_ppo_rollout_f32 / rlx_actor_critic_fwd_sample_f32, rlx_ppo_next_values_f32 and rlx_gae_f32 (espo.py:99-110, 186-230).   */
+typedef struct rlx_espo_hparams { /* espo/pytorch/default_config.py:18-24 */
+  float max_ratio_delta;
+  float entropy_coef, critic_coef;
+  float max_grad_norm;               /* clip_grad_norm_ of both optimisers (espo.py:137, :154); <= 0: none */
+  float adam_b1, adam_b2, adam_eps;  /* torch.optim.Adam defaults (espo.py:87-88) */
+  int32_t delta_op;                  /* delta_calc_operator: 0 torch.mean, 1 torch.median (the LOWER median, sorted[(mb - 1) / 2]) */
+} rlx_espo_hparams;
+/* The whole optimisation phase of one iteration (espo.py:236-278): for epoch e = 0 .. max_epochs - 1 on the rollout rows idx[e, :]
+ * (idx: DEVICE int32[max_epochs, mb], each row drawn without replacement from [0, B), B = T * N) one policy step (policy_loss_fn,
+ * espo.py:113-141: ratio, approx_kl, ratio_delta, advantages normalised with the UNBIASED std, pg_loss = mean(-A^ ratio) without
+ * clipping, minus entropy_coef x entropy; clip_grad_norm_; Adam; policy_logstd is a parameter) and one critic step
+ * (critic_loss_fn, :144-158) on the same rows, both at Adam step *opt_count_io + e + 1 and learning rate lr; THEN the loop ends if
+ * ratio_delta > max_ratio_delta (:277-278: the epoch that trips the threshold is applied in full; a NaN never trips it).  The
+ * stop is decided on the device: epochs are submitted in chunks ("espo_chunk"), later epochs of chunks already submitted run as
+ * no-ops behind a device-side gate, and the host waits once, at the end of the call, to write *epochs_run_out (HOST, the
+ * reference's `epoch + 1`) and to advance *opt_count_io (HOST) by it.
+ * states: the FULL observation rows [B, O]; pidx / cidx: DEVICE int32[n_pidx] / [n_cidx] policy / critic column indices inside
+ * [0, O), or NULL (the net reads all O columns; n_* ignored).  pdesc / cdesc: arch A (n_hidden 2, act TANH, ln_first 0; both
+ * hidden widths one multiple of 64 in 64..512, the same for both nets), pdesc: in_dim = n_pidx or O, out_dim = action dim 1..64,
+ * has_logstd 1; cdesc: in_dim = n_cidx or O, out_dim 1, has_logstd 0.  Flat layouts: rlx_mlp_param_count.  2 <= mb <= 4096
+ * (torch.std of one element is NaN), mb <= B, max_epochs >= 1.  A descriptor or mb outside that is RLX_EUNSUP, every other bad
+ * argument RLX_EINVAL (an index outside its range included: nothing is applied then).
+ * metrics_out: DEVICE float[max_epochs, 8], one row per EXECUTED epoch = {pg_loss, critic_loss, entropy_loss, ratio_delta,
+ * approx_kl, policy_grad_norm, critic_grad_norm (both before clipping), reserved}; rows past *epochs_run_out are left untouched.
+ * A step whose gradient norm is not finite is skipped on the device, as everywhere in this library.                          */
+int rlx_espo_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* cdesc,
+                        float* cparams, float* cm, float* cv, const float* states, int O, const int32_t* pidx, int n_pidx,
+                        const int32_t* cidx, int n_cidx, const float* actions, const float* log_probs, const float* returns,
+                        const float* advantages, int64_t B, const int32_t* idx, int mb, int max_epochs, int64_t* opt_count_io, float lr,
+                        const rlx_espo_hparams* hp, float* metrics_out, int32_t* epochs_run_out, void* stream);
 
 /* =================================== PPO + LSTM =======================================
  * Recurrent policy (rl_x/algorithms/ppo_lstm/flax_full_jit/policy.py:32-142, "concat" and "film" decoders):

@@ -206,6 +206,10 @@ struct rlx_ctx {
   hipEvent_t sched_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t sched_cap = 0;
   int sched_pos = 0;
+  // ---- ESPO update (espo.hip): the device-side stop word is copied here after every chunk of epochs
+  int espo_chunk = 2;                     // epochs submitted between two copies of the stop word (option "espo_chunk"); the result does not depend on it
+  int32_t* espo_host = nullptr;           // pinned, one word per chunk in flight
+  hipEvent_t espo_ev[3] = {nullptr, nullptr, nullptr};
   // prefetched rank-local minibatch rows (rlx_ppo_dist_prefetch)
   bool pf_dist = false;
   int pf_T = 0, pf_nl = 0, pf_ng = 0, pf_off = 0, pf_mb = 0;

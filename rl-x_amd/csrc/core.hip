@@ -242,6 +242,7 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
   if (std::string(name) == "bx_gscale_log2") { ctx->bx_gscale = ldexpf(1.f, value < 0 ? 0 : (value > 40 ? 40 : value)); return RLX_OK; }
   if (std::string(name) == "gemm_bx") { ctx->gemm_bx = value != 0; return RLX_OK; }
   if (std::string(name) == "prof_sample") { ctx->prof_sample = value < 1 ? 1 : value; return RLX_OK; }
+  if (std::string(name) == "espo_chunk") { ctx->espo_chunk = value < 1 ? 1 : value; return RLX_OK; }
   if (std::string(name) == "fused_recurrent_act") { ctx->fused_recurrent_act = value != 0; return RLX_OK; }
   RLX_REQUIRE(false, RLX_EINVAL, "rlx_dbg_set_option: unknown option");
 }
@@ -299,6 +300,9 @@ int rlx_ctx_destroy(rlx_ctx* ctx) {
     if (ctx->sched_host[i]) (void)hipHostFree(ctx->sched_host[i]);
     if (ctx->sched_ev[i]) (void)hipEventDestroy(ctx->sched_ev[i]);
   }
+  if (ctx->espo_host) (void)hipHostFree(ctx->espo_host);
+  for (int i = 0; i < 3; ++i)
+    if (ctx->espo_ev[i]) (void)hipEventDestroy(ctx->espo_ev[i]);
   for (int b = 0; b < 3; ++b)
     for (int i = 0; i < rlx::SL_COUNT; ++i)
       if (ctx->slots[b][i].ptr) (void)hipFree(ctx->slots[b][i].ptr);

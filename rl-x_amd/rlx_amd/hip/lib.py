@@ -108,6 +108,12 @@ class MpoHparams(Structure):
         ("action_sampling_number", c_int32), ("action_clipping", c_int32), ("action_rescaling", c_int32)]
 
 
+class EspoHparams(Structure):
+    """rlx_espo_hparams (espo/pytorch/default_config.py:18-24); delta_op: 0 mean, 1 median"""
+    _fields_ = [(n, c_float) for n in ("max_ratio_delta", "entropy_coef", "critic_coef", "max_grad_norm", "adam_b1", "adam_b2",
+                                       "adam_eps")] + [("delta_op", c_int32)]
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -286,6 +292,9 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_int64, c_int, POINTER(MpoHparams), c_void_p]),
     "rlx_mpo_update_f32": (c_int, [c_void_p, POINTER(MpoDesc)] + [c_void_p] * 13 + [c_int, c_void_p, c_void_p] + [c_void_p] * 5 +
                            [c_int64, _U32P, c_int, c_int64, c_float, c_float, POINTER(MpoHparams), c_void_p, c_void_p]),
+    "rlx_espo_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                    c_int, _I64P, c_float, POINTER(EspoHparams), c_void_p, POINTER(c_int32), c_void_p]),
     "rlx_dist_overflow_count": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "rlx_ppo_dist_prefetch": (c_int, [c_void_p, _U32P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rlx_ppo_update_dist_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p,
@@ -1093,6 +1102,21 @@ class Ctx:
             _ptr(cidx, i32, True), _ptr(a, f), _ptr(r, f), _ptr(d, f), _ptr(tr, f), _ptr(n, f), int(s.shape[0]), k, scheme, int(step),
             float(agent_lr), float(dual_lr), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_mpo_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32)
+
+    # ---- ESPO (rl_x/algorithms/espo/pytorch)
+    def espo_update(self, pdesc, pparams, pm, pv, cdesc, cparams, cm, cv, states, actions, log_probs, returns, advantages, idx,
+                    opt_count, lr, hp, metrics_out, pidx=None, cidx=None):
+        """The epoch loop of one iteration.  states [B, O] (the full rows), actions [B, A], log_probs / returns / advantages [B];
+        idx int32 [max_epochs, mb]; metrics_out float [max_epochs, 8].  Blocks once, at its end.  -> (epochs run, new optimizer count)"""
+        f, i32 = self.torch.float32, self.torch.int32
+        cnt, run = c_int64(int(opt_count)), c_int32(0)
+        _check(self.lib.rlx_espo_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(cdesc), _ptr(cparams, f), _ptr(cm, f),
+            _ptr(cv, f), _ptr(states, f), int(states.shape[1]), _ptr(pidx, i32, True), 0 if pidx is None else int(pidx.numel()),
+            _ptr(cidx, i32, True), 0 if cidx is None else int(cidx.numel()), _ptr(actions, f), _ptr(log_probs, f), _ptr(returns, f),
+            _ptr(advantages, f), int(states.shape[0]), _ptr(idx, i32), int(idx.shape[1]), int(idx.shape[0]), ctypes.byref(cnt), float(lr),
+            ctypes.byref(hp), _ptr(metrics_out, f), ctypes.byref(run), _stream()), "rlx_espo_update_f32")
+        return run.value, cnt.value
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
