@@ -173,6 +173,10 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   "gather_group_rows" (524288: in the two-chain schedules of rlx_ppo_update_f32 / rlx_ppo_update_dist_f32 the rows of that many samples -- one epoch at
  *   configs[1] -- are gathered by ONE launch into one of two alternating buffers, and the chains meet once per group instead of once
  *   per update; 0: one gather per update; needs "gather_records").
+ * Round 7: "tail32_waves" (8 default; 4 or 8, anything else is RLX_EINVAL): waves per 32-row tile of k_tail32_bx, in its single,
+ *   twin (grid.y = 2) and valid-rows launches alike.  8 runs the same tile with the same LDS on 512 threads -- four waves per SIMD
+ *   instead of two -- with the same arithmetic in the same order: bit-identical results (tests/test_gpu_tail32_waves.py); 4 is
+ *   the earlier form.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,

@@ -141,6 +141,9 @@ struct rlx_ctx {
   bool l12_fused = true;                  // first + second layer forward in one launch when both split images are registered (k_l12fwd)
   int ppo_tail = -1;                      // PPO update: last hidden layer forward + head + loss + both input gradients in ONE launch per network (ppo.hip).
                                           // -1 (default): k_tail32_bx (32-row tiles) up to 8192 rows, k_tail_bx (64-row) above; 0 off; 1 / 2 force a form
+  int tail32_waves = 8;                   // k_tail32_bx: waves per 32-row tile, 4 or 8 (same LDS: two or four waves per SIMD; bit-identical results).
+                                          // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 67.14 vs 68.34 ms per iteration at 32768-row
+                                          // minibatches (block-to-block sd 0.19 / 0.24), 112.41 vs 115.96 at 4096 rows
   int ppo_twin = -1;                      // PPO update: policy || critic as twin launches (grid.y = 2) on ONE stream.  -1 (default): for
                                           // minibatches of 6144 to 16384 rows on one rank (below: two chains with grouped gathers), never with a real
                                           // RCCL communicator of more than one rank (its all-reduce would be exposed: twin_shapes_ok);

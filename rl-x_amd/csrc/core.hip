@@ -236,6 +236,11 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
   if (std::string(name) == "gather_group_rows") { ctx->gather_group_rows = value; return RLX_OK; }
   if (std::string(name) == "gather_records") { ctx->gather_records = value != 0; return RLX_OK; }
   if (std::string(name) == "ppo_tail") { ctx->ppo_tail = value < 0 ? -1 : (value > 2 ? 2 : value); return RLX_OK; }
+  if (std::string(name) == "tail32_waves") {
+    RLX_REQUIRE(value == 4 || value == 8, RLX_EINVAL, "rlx_dbg_set_option: tail32_waves is 4 or 8");
+    ctx->tail32_waves = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "bx_force_mi") { ctx->bx_force_mi = value; return RLX_OK; }
   if (std::string(name) == "adam_emit") { ctx->adam_emit = value != 0; return RLX_OK; }
   if (std::string(name) == "bx_debug") { ctx->bx_debug = value; return RLX_OK; }

@@ -1013,14 +1013,26 @@ __global__ __launch_bounds__(256, 2) void k_tail_bx(TailNet p, TailNet c, const 
 // first form moves 122.  Padded LDS rows (stride + 16 bytes) keep every fragment / store address a per-lane base + an immediate.
 // 256 threads: wave w owns output columns [32 w, 32 w + 32) of the forward and column tiles 2 w, 2 w + 1 of the input gradient;
 // the head runs 8 threads per row.  65 KB of LDS: two workgroups per CU.
+//
+// NWV = 8 (option tail32_waves): the same tile, LDS layout and arithmetic on 512 threads -- four waves per SIMD instead of two at the
+// same two workgroups per CU.  Waves 0-3 run phase A and the head exactly as the four-wave form does (their row scalars requested
+// before the K loop); waves 4-7 meanwhile stage the head weights and request the weight fragments of their phase-C tile, then only
+// attend the head's barriers.  dZ3 runs 16 threads per row (8 columns each, d_out from Ds, H3 taken from the tile before the barrier
+// that frees it), phase C one column tile per wave.  Every sum keeps its operands and its order: the results are bit-identical.
 // ---------------------------------------------------------------------------------------
+#ifndef RLX_T32_STAMPS
+#define RLX_T32_STAMPS 0
+#endif
 constexpr int T32_ROWS = 32;
-template <bool POLICY, int ACT, int N2>
+template <bool POLICY, int ACT, int N2, int NWV>
 __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__ smem, const float* __restrict__ mb_a,
                                             const float* __restrict__ aux, const double* __restrict__ stats,
                                             float* __restrict__ metrics, int64_t M, float inv_mb, float clip, float ent_coef,
-                                            float critic_coef, const int32_t* __restrict__ valid_rows, float gs) {
+                                            float critic_coef, const int32_t* __restrict__ valid_rows, float gs,
+                                            unsigned long long* __restrict__ stamps) {
+  static_assert(NWV == 4 || NWV == 8, "tail32: four or eight waves per tile");
   constexpr int K = TL_K3, AP = 8, NP = 2, RP = T32_ROWS / NP, KQ = K / 8;     // head: 8 threads per row, 16 columns each
+  constexpr int NT = 64 * NWV, TPR = NT / T32_ROWS;                            // threads; threads per row of the plane split and of dZ3
   constexpr int HROW = 2 * N2 + 16, HPL = T32_ROWS * HROW;                     // H2 planes: padded rows
   constexpr int DROW = 2 * K + 16, DPL = T32_ROWS * DROW;                      // dZ3 planes
   constexpr int TREG = (T32_ROWS * TL_TS * 4 > 2 * DPL) ? T32_ROWS * TL_TS * 4 : 2 * DPL;   // fp32 H3 tile, then the dZ3 planes
@@ -1031,20 +1043,50 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
   float* Ds = Ws + K * AP;                                        // [32][8]
   float* DLs = Ds + T32_ROWS * AP;                                // [32][8]
   float* red = DLs + T32_ROWS * AP;                               // [16] metric sums, then [NP][K][8]
+  float* BL = red + NP * K * AP;                                  // [2][8] head bias, logstd (NWV == 8): the 16 floats behind the partial sums
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
   const int64_t m0 = (int64_t)blockIdx.x * T32_ROWS;
   const int A = n.A, PS = n.PS;
+  // NWV == 8: waves 0-3 are the head waves (wave-uniform, so every branch on it is a scalar one; all barriers sit outside them)
+  const bool hw = NWV == 4 || __builtin_amdgcn_readfirstlane(w) < 4;
+  // phase stamps (tools/tail32_phases.py): compiled in only with -DRLX_T32_STAMPS=1
+#if RLX_T32_STAMPS
+#define T32_STAMP(I) if (stamps && t == 0 && blockIdx.x == 0 && blockIdx.y == 0) stamps[I] = clock64();
+#define T32_WALL(I) if (stamps && t == 0 && blockIdx.x == 0 && blockIdx.y == 0) stamps[I] = wall_clock64();      // constant 100 MHz: calibrates the clock64 ticks
+#else
+#define T32_STAMP(I)
+#define T32_WALL(I)
+#endif
+  T32_STAMP(0)
+  T32_WALL(14)
+  // phase C's weight fragments (declared here: with NWV == 8 waves 4-7 request theirs during phase A)
+  constexpr int NTC = N2 / 32, JW = NTC / NWV;                    // column tiles of the output, per wave
+  // weight fragments PFC 16-k blocks ahead (L2 latency per block otherwise); one column tile per wave has half the matrix work per
+  // block to cover a request with, so NWV == 8 keeps twice the blocks in flight (the same 32 registers)
+  constexpr int PFC = RLX_T32_PFC * (NWV / 4), NBC = K / 16, wstepC = NTC * X_NP * 64;
+  const u32x4* wt = n.W3t + (int64_t)(w * JW) * X_NP * 64 + lane;   // image: [kb][NTC column tiles][2 planes][64]
+  u32x4 bc[PFC][JW][X_NP];
+  auto c_prologue = [&]() {
+#pragma unroll
+    for (int u = 0; u < PFC; ++u)
+#pragma unroll
+      for (int j = 0; j < JW; ++j)
+#pragma unroll
+        for (int p = 0; p < X_NP; ++p) bc[u][j][p] = wt[(int64_t)u * wstepC + (j * X_NP + p) * 64];
+  };
   // ------------------------------------------------------------------ the H2 tile -> resident planes
   {
-    constexpr int NV = T32_ROWS * N2 / 4 / 256;                   // float4 pieces per thread (8 at N2 = 256)
+    constexpr int NV = T32_ROWS * N2 / 4 / NT;                    // float4 pieces per thread (8 at N2 = 256 on four waves, 4 on eight)
     float4 hv[NV];
-    const int sr = t >> 3, sc = (t & 7) * 4;                      // row, first column of the thread's pieces (then + 32 i)
+    const int sr = t / TPR, sc = (t % TPR) * 4;                   // row, first column of the thread's pieces (then + 4 TPR i)
     const float* hp = n.H2 + (m0 + sr) * N2 + sc;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) hv[i] = *reinterpret_cast<const float4*>(hp + 32 * i);
-    for (int i = t; i < K * AP; i += 256) {                       // (head weights, under the loads' latency)
-      const int k = i >> 3, a = i & 7;
-      Ws[i] = a < A ? n.Wh[k * A + a] : 0.f;
+    for (int i = 0; i < NV; ++i) hv[i] = *reinterpret_cast<const float4*>(hp + 4 * TPR * i);
+    if (NWV == 4) {
+      for (int i = t; i < K * AP; i += 256) {                     // (head weights, under the loads' latency)
+        const int k = i >> 3, a = i & 7;
+        Ws[i] = a < A ? n.Wh[k * A + a] : 0.f;
+      }
     }
     char* d0 = H2P + sr * HROW + sc * 2;
 #pragma unroll
@@ -1052,13 +1094,51 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
       uint32_t a0, a1, b0, b1;
       bx_split2(hv[i].x * X_ASCALE, hv[i].y * X_ASCALE, a0, a1);
       bx_split2(hv[i].z * X_ASCALE, hv[i].w * X_ASCALE, b0, b1);
-      *reinterpret_cast<u32x2*>(d0 + 64 * i) = u32x2{a0, b0};
-      *reinterpret_cast<u32x2*>(d0 + 64 * i + HPL) = u32x2{a1, b1};
+      *reinterpret_cast<u32x2*>(d0 + 8 * TPR * i) = u32x2{a0, b0};
+      *reinterpret_cast<u32x2*>(d0 + 8 * TPR * i + HPL) = u32x2{a1, b1};
     }
   }
+  T32_STAMP(1)
   __syncthreads();
+  T32_STAMP(2)
+  // head geometry: 8 threads per row (threads 0..255 in both forms)
+  const int r = t >> 3, q8 = t & 7;
+  const int64_t row = m0 + r;
+  float bias[AP], ls[AP];
+  float pre_act[AP], pre_lp = 0.f, pre_ret = 0.f, pre_adv = 0.f, amean = 0.f, ainv = 0.f, astd = 0.f, pre_b3 = 0.f;
+  bool pre_valid = false;
+  if (NWV == 8) {
+    if (hw) {   // the head's row scalars, requested before the K loop instead of inside the head phase
+      // (unconditional loads of in-bounds elements -- every row of the tile has its record, a >= A reads element A - 1 -- and the
+      //  selection where the value is used: a load behind a condition becomes a branch with its own wait, one latency after another)
+      pre_valid = row < (valid_rows ? (int64_t)*valid_rows : M);
+      pre_b3 = n.b3[w * 32 + li];
+      if (POLICY) {
+#pragma unroll
+        for (int a = 0; a < AP; ++a) pre_act[a] = mb_a[row * A + (a < A ? a : A - 1)];
+      }
+      if (POLICY) {
+        adv_norm_from_stats(stats, amean, ainv, astd);
+        pre_lp = aux[row * 3 + 0];
+        pre_adv = aux[row * 3 + 2];
+      } else {
+        pre_ret = aux[row * 3 + 1];
+      }
+    } else {    // waves 4-7: the first weight fragments of their phase-C tile into registers; head weights, bias and logstd into LDS
+      c_prologue();
+      const int i0 = t - 256, a = i0 & 7, ac = a < A ? a : A - 1;
+      float wv[K * AP / 256], bl = 0.f;
+#pragma unroll
+      for (int u = 0; u < K * AP / 256; ++u) wv[u] = n.Wh[((i0 >> 3) + 32 * u) * A + ac];
+      if (i0 < AP) bl = n.bh[ac];
+      else if (POLICY && i0 < 2 * AP) bl = n.logstd[ac];
+#pragma unroll
+      for (int u = 0; u < K * AP / 256; ++u) Ws[i0 + 256 * u] = a < A ? wv[u] : 0.f;
+      if (i0 < 2 * AP) BL[i0] = a < A ? bl : 0.f;
+    }
+  }
   // ------------------------------------------------------------------ phase A: H3 = act(H2 @ W3 + b3), wave w: columns [32 w, 32 w + 32)
-  {
+  if (hw) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -1093,23 +1173,27 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
 #pragma unroll
     for (int u = 0; u < PF; ++u) T32_BLOCK(NB - PF + u, false)
 #undef T32_BLOCK
-    const float so = X_AINV * X_WINV, bv = n.b3[w * 32 + li];
+    T32_STAMP(3)
+    const float so = X_AINV * X_WINV, bv = NWV == 8 ? pre_b3 : n.b3[w * 32 + li];
     float* tb = T + (4 * lh) * TL_TS + w * 32 + li;
 #pragma unroll
     for (int r = 0; r < 16; ++r) tb[((r & 3) + 8 * (r >> 2)) * TL_TS] = act_fwd_t<ACT>(fmaf(acc[r], so, bv));
   }
+  T32_STAMP(4)
   __syncthreads();
+  T32_STAMP(5)
   // ------------------------------------------------------------------ phase B: head, loss, seeds, head-gradient partials (8 threads per row)
-  const int r = t >> 3, q8 = t & 7;
-  const int64_t row = m0 + r;
-  const bool valid = row < (valid_rows ? (int64_t)*valid_rows : M);
-  float bias[AP], ls[AP];
+  const bool valid = NWV == 8 ? pre_valid : row < (valid_rows ? (int64_t)*valid_rows : M);
 #pragma unroll
   for (int a = 0; a < AP; ++a) {
-    bias[a] = a < A ? n.bh[a] : 0.f;
-    ls[a] = (POLICY && a < A) ? n.logstd[a] : 0.f;
+    bias[a] = NWV == 8 ? BL[a] : (a < A ? n.bh[a] : 0.f);
+    ls[a] = NWV == 8 ? BL[AP + a] : ((POLICY && a < A) ? n.logstd[a] : 0.f);
   }
   hl_f4 h[KQ / 4];
+  float d[AP], m0s = 0.f, m1s = 0.f, m2s = 0.f;
+#pragma unroll
+  for (int a = 0; a < AP; ++a) d[a] = 0.f;
+  if (hw) {
   {
     const hl_f4* hp = reinterpret_cast<const hl_f4*>(T + r * TL_TS + q8 * KQ);
 #pragma unroll
@@ -1135,22 +1219,18 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     out[a] += dpp_f(out[a], 2);
     out[a] += bias[a];
   }
-  float d[AP], m0s = 0.f, m1s = 0.f, m2s = 0.f;
-#pragma unroll
-  for (int a = 0; a < AP; ++a) d[a] = 0.f;
   if (POLICY) {
     float nlp = 0.f, zs[AP], isd[AP];
 #pragma unroll
     for (int a = 0; a < AP; ++a) {
       isd[a] = 1.0f / expf(ls[a]);
-      const float act_a = (valid && a < A) ? mb_a[row * A + a] : out[a];
+      const float act_a = (valid && a < A) ? (NWV == 8 ? pre_act[a] : mb_a[row * A + a]) : out[a];
       zs[a] = (act_a - out[a]) * isd[a];
       if (a < A) nlp += -0.5f * zs[a] * zs[a] - 0.5f * LOG_2PI - ls[a];
     }
-    float amean, ainv, astd;
-    adv_norm_from_stats(stats, amean, ainv, astd);
-    const float logp_old = valid ? aux[row * 3 + 0] : 0.f;
-    const float advn = valid ? (aux[row * 3 + 2] - amean) * ainv : 0.f;
+    if (NWV == 4) adv_norm_from_stats(stats, amean, ainv, astd);
+    const float logp_old = valid ? (NWV == 8 ? pre_lp : aux[row * 3 + 0]) : 0.f;
+    const float advn = valid ? ((NWV == 8 ? pre_adv : aux[row * 3 + 2]) - amean) * ainv : 0.f;
     const float logratio = valid ? nlp - logp_old : 0.f;
     const float ratio = expf(logratio);
     const float pg1 = -advn * ratio;
@@ -1179,7 +1259,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     }
   } else {
     if (valid) {
-      const float diff = out[0] - aux[row * 3 + 1];
+      const float diff = out[0] - (NWV == 8 ? pre_ret : aux[row * 3 + 1]);
       if (q8 == 0) m0s = 0.5f * diff * diff;
       d[0] = critic_coef * inv_mb * diff;
     }
@@ -1192,6 +1272,8 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
   m1s = wave_sum(m1s);
   m2s = wave_sum(m2s);
   if ((t & 63) == 0) { red[(t >> 6) * 4 + 0] = m0s; red[(t >> 6) * 4 + 1] = m1s; red[(t >> 6) * 4 + 2] = m2s; }
+  }   // hw
+  T32_STAMP(6)
   __syncthreads();
   float* pw = n.partials + (int64_t)blockIdx.x * PS;
   if (t == 0) {
@@ -1201,11 +1283,13 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     pm[2] = (red[2] + red[6]) + (red[10] + red[14]);
   }
   __syncthreads();
+  T32_STAMP(7)
   {  // head weight gradient: thread (k, row group): RP rows in order, then the NP groups in order
     const int k = t % K, part = t / K;
     float dw[AP];
 #pragma unroll
     for (int a = 0; a < AP; ++a) dw[a] = 0.f;
+    if (hw) {
     for (int rr = part * RP; rr < (part + 1) * RP; ++rr) {
       const float hv = T[rr * TL_TS + k];
       const hl_f4 d0 = *reinterpret_cast<const hl_f4*>(Ds + rr * AP), d1 = *reinterpret_cast<const hl_f4*>(Ds + rr * AP + 4);
@@ -1214,6 +1298,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     }
 #pragma unroll
     for (int a = 0; a < AP; ++a) red[(part * K + k) * AP + a] = dw[a];
+    }   // hw
     __syncthreads();
     if (part == 0) {
 #pragma unroll
@@ -1230,21 +1315,44 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     pw[K * A + t] = sb;
     pw[K * A + A + t] = sl;
   }
-  __syncthreads();                                 // every read of T as H3 is done
-  {  // dZ3 = (d_out @ Wh^T) * act'(H3): to HBM (fp32, the weight-gradient job's operand) and as fp16 planes into the tile
-    hl_f4* gp = reinterpret_cast<hl_f4*>(n.dZ3 + row * K + q8 * KQ);
-    char* dp = D3P + r * DROW + q8 * KQ * 2;
+  // NWV == 8: dZ3 runs 16 threads per row, 8 columns each -- d_out from Ds, the thread's H3 values out of the tile before the barrier
+  // after which the dZ3 planes overwrite it; waves 0-3 request the first weight fragments of their phase-C tile here
+  constexpr int CQ = K / TPR;                      // dZ3 columns per thread
+  // (NWV == 8: a half-wave shares its column group and spreads over the 32 rows, so its reads of the head weights are broadcasts --
+  //  with the 16 column groups side by side in a wave the rows of Ws they read, 256 bytes apart, met on the same LDS banks: phase
+  //  stamps, dZ3 at 7.8 k clocks against 4.4 k on four waves)
+  const int zr = NWV == 8 ? (t & 31) : t / TPR, zc = (NWV == 8 ? (t >> 5) : (t % TPR)) * CQ;
+  hl_f4 h3[CQ / 4];
+  float dd[AP];
+  if (NWV == 8) {
+    const hl_f4* hp = reinterpret_cast<const hl_f4*>(T + zr * TL_TS + zc);
 #pragma unroll
-    for (int j = 0; j < KQ / 4; ++j) {
+    for (int j = 0; j < CQ / 4; ++j) h3[j] = hp[j];
+    const hl_f4 d0 = *reinterpret_cast<const hl_f4*>(Ds + zr * AP), d1 = *reinterpret_cast<const hl_f4*>(Ds + zr * AP + 4);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { dd[a] = d0[a]; dd[4 + a] = d1[a]; }
+    if (hw) c_prologue();
+  }
+  T32_STAMP(8)
+  __syncthreads();                                 // every read of T as H3 is done
+  T32_STAMP(9)
+  {  // dZ3 = (d_out @ Wh^T) * act'(H3): to HBM (fp32, the weight-gradient job's operand) and as fp16 planes into the tile
+    hl_f4* gp = reinterpret_cast<hl_f4*>(n.dZ3 + (m0 + zr) * K + zc);
+    char* dp = D3P + zr * DROW + zc * 2;
+#pragma unroll
+    for (int j = 0; j < CQ / 4; ++j) {
       hl_f4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float* wr = Ws + (q8 * KQ + 4 * j + e) * AP;
+        const float* wr = Ws + (zc + 4 * j + e) * AP;
         const hl_f4 w0 = *reinterpret_cast<const hl_f4*>(wr), w1 = *reinterpret_cast<const hl_f4*>(wr + 4);
         float sacc = 0.f;
 #pragma unroll
-        for (int a = 0; a < 4; ++a) { sacc = fmaf(d[a], w0[a], sacc); sacc = fmaf(d[4 + a], w1[a], sacc); }
-        o[e] = sacc * act_grad_t<ACT>(h[j][e]);
+        for (int a = 0; a < 4; ++a) {
+          sacc = fmaf(NWV == 8 ? dd[a] : d[a], w0[a], sacc);
+          sacc = fmaf(NWV == 8 ? dd[4 + a] : d[4 + a], w1[a], sacc);
+        }
+        o[e] = sacc * act_grad_t<ACT>(NWV == 8 ? h3[j][e] : h[j][e]);
       }
       gp[j] = o;
       uint32_t a0, a1, b0, b1;
@@ -1254,26 +1362,19 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
       *reinterpret_cast<u32x2*>(dp + 8 * j + DPL) = u32x2{a1, b1};
     }
   }
+  T32_STAMP(10)
   __syncthreads();
+  T32_STAMP(11)
   // ------------------------------------------------------------------ phase C: dZ2 = (dZ3 @ W3^T) * act'(H2); wave w: column tiles 2 w, 2 w + 1
   {
-    constexpr int NTC = N2 / 32, JW = NTC / 4;                    // column tiles of the output, per wave
     f32x16 acc[JW];
 #pragma unroll
     for (int j = 0; j < JW; ++j)
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) acc[j][rr] = 0.f;
     const char* ard = D3P + li * DROW + lh * 16;
-    const u32x4* wt = n.W3t + (int64_t)(w * JW) * X_NP * 64 + lane;   // image: [kb][NTC column tiles][2 planes][64]
-    constexpr int wstep = NTC * X_NP * 64;
-    constexpr int PFC = RLX_T32_PFC, NBC = K / 16;                          // weight fragments four 16-k blocks ahead (L2 latency per block otherwise)
-    u32x4 bc[PFC][JW][X_NP];
-#pragma unroll
-    for (int u = 0; u < PFC; ++u)
-#pragma unroll
-      for (int j = 0; j < JW; ++j)
-#pragma unroll
-        for (int p = 0; p < X_NP; ++p) bc[u][j][p] = wt[(int64_t)u * wstep + (j * X_NP + p) * 64];
+    constexpr int wstep = wstepC;
+    if (NWV == 4) c_prologue();
 #define T32C_BLOCK(QU, REFILL)                                                                                        \
   {                                                                                                                   \
     u32x4 av[X_NP];                                                                                                   \
@@ -1298,6 +1399,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
 #pragma unroll
     for (int u = 0; u < PFC; ++u) T32C_BLOCK(NBC - PFC + u, false)
 #undef T32C_BLOCK
+    T32_STAMP(12)
     const float so2 = X_WINV / gs;
 #pragma unroll
     for (int j = 0; j < JW; ++j) {
@@ -1314,20 +1416,24 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
       }
     }
   }
+  T32_STAMP(13)
+  T32_WALL(15)
+#undef T32_STAMP
+#undef T32_WALL
 }
 
-template <int ACT, int N2>
-__global__ __launch_bounds__(256, 2) void k_tail32_bx(TailNet p, TailNet c, const float* __restrict__ mb_a,
+template <int ACT, int N2, int NWV>
+__global__ __launch_bounds__(64 * NWV, NWV / 2) void k_tail32_bx(TailNet p, TailNet c, const float* __restrict__ mb_a,
                                                       const float* __restrict__ aux, const double* __restrict__ stats,
                                                       float* __restrict__ metrics, int64_t M, float inv_mb, float clip,
                                                       float ent_coef, float critic_coef, const int32_t* __restrict__ valid_rows,
-                                                      float gs, int both, int which) {
+                                                      float gs, int both, int which, unsigned long long* __restrict__ stamps) {
   extern __shared__ __attribute__((aligned(16))) char tl32_smem[];
   const bool critic = both ? blockIdx.y != 0 : which != 0;
   if (!critic)
-    tail32_body<true, ACT, N2>(p, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs);
+    tail32_body<true, ACT, N2, NWV>(p, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs, stamps);
   else
-    tail32_body<false, ACT, N2>(c, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs);
+    tail32_body<false, ACT, N2, NWV>(c, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs, stamps);
 }
 
 // rows per workgroup (= per block of head partials) of the tail form in use
@@ -1365,14 +1471,22 @@ static int launch_tail(rlx_ctx* ctx, const TailNet* p, const TailNet* c, const M
     constexpr int HPL = T32_ROWS * (2 * 256 + 16), DPL = T32_ROWS * (2 * TL_K3 + 16);
     constexpr int TREG = (T32_ROWS * TL_TS * 4 > 2 * DPL) ? T32_ROWS * TL_TS * 4 : 2 * DPL;
     const size_t lds32 = 2 * HPL + TREG + ((size_t)TL_K3 * 8 + 2 * T32_ROWS * 8 + 16 + 2 * TL_K3 * 8) * sizeof(float);
-    static AttrOnce attr32;
-    if (!attr32.done()) {
-      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tail32_bx<RLX_ACT_ELU, 256>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr32.mark();
-    }
-    RLX_PLAUNCH((k_tail32_bx<RLX_ACT_ELU, 256>), dim3((unsigned)(mb / T32_ROWS), both ? 2 : 1), dim3(256), lds32, st, tp, tc, s.mb_a,
-                s.aux, s.stats, metrics, mb, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, s.valid_rows, gs, both, which);
+    unsigned long long* stamps = RLX_T32_STAMPS ? (unsigned long long*)ctx->dbg_stamps : nullptr;
+#define RLX_TAIL32_LAUNCH(NWV)                                                                                       \
+  {                                                                                                                  \
+    static AttrOnce attr32;                                                                                          \
+    if (!attr32.done()) {                                                                                            \
+      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tail32_bx<RLX_ACT_ELU, 256, NWV>),             \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                      \
+      attr32.mark();                                                                                                 \
+    }                                                                                                                \
+    RLX_PLAUNCH((k_tail32_bx<RLX_ACT_ELU, 256, NWV>), dim3((unsigned)(mb / T32_ROWS), both ? 2 : 1), dim3(64 * NWV), lds32, st, tp, \
+                tc, s.mb_a, s.aux, s.stats, metrics, mb, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, s.valid_rows, gs,   \
+                both, which, stamps);                                                                                \
+  }
+    if (ctx->tail32_waves == 8) RLX_TAIL32_LAUNCH(8)     // (default) eight waves per 32-row tile: same LDS, four waves per SIMD, bit-identical results
+    else RLX_TAIL32_LAUNCH(4)
+#undef RLX_TAIL32_LAUNCH
     RLX_LAUNCH_CHECK();
     return RLX_OK;
   }

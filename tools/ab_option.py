@@ -2,7 +2,9 @@
 """A/B a library option inside ONE process (box-to-box and run-to-run variance is several per cent, larger than most kernel
 changes): alternates blocks of PPO bench iterations with the option at value A and at value B.
     python tools/ab_option.py gemm_bx 1 0 [--blocks 4] [--iters 5]
-    python tools/ab_option.py attr:rollout_one_call 1 0        (an attribute of the plugin object instead of a library option)"""
+    python tools/ab_option.py attr:rollout_one_call 1 0        (an attribute of the plugin object instead of a library option)
+    python tools/ab_option.py tail32_waves 4 8 --minibatch-size-global 4096     (another minibatch size, as bench.py's flag)
+Prints the blocks, their mean and their standard deviation (the block-to-block spread a difference has to clear)."""
 import argparse
 import os
 import sys
@@ -24,11 +26,14 @@ ap.add_argument("a", type=int)
 ap.add_argument("b", type=int)
 ap.add_argument("--blocks", type=int, default=4)
 ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--minibatch-size-global", type=int, default=0)
 args = ap.parse_args()
 config = ConfigDict()
 config.runner = runner_cfg("train")
 config.algorithm = get_algorithm_config("ppo.hip")
 config.environment = get_environment_config("synthetic.random_obs")
+if args.minibatch_size_global:
+    config.algorithm.minibatch_size = args.minibatch_size_global
 env, _ = get_environment_create_train_and_eval_env("synthetic.random_obs")(config)
 model = get_algorithm_model_class("ppo.hip")(config, env, env, "/tmp/x", None)
 batch = model._alloc_batch()
@@ -57,4 +62,6 @@ for blk in range(args.blocks):
         torch.cuda.synchronize()
         res[v].append(1e3 * (time.perf_counter() - t0) / args.iters)
 for v, xs in res.items():
-    print(f"{args.option}={v}: " + " ".join(f"{x:.2f}" for x in xs) + f"  | mean {sum(xs)/len(xs):.2f} ms/iteration")
+    mean = sum(xs) / len(xs)
+    sd = (sum((x - mean) ** 2 for x in xs) / max(1, len(xs) - 1)) ** 0.5
+    print(f"{args.option}={v}: " + " ".join(f"{x:.2f}" for x in xs) + f"  | mean {mean:.3f} ms/iteration, sd {sd:.3f} over {len(xs)} blocks")
