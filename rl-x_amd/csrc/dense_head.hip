@@ -7,7 +7,8 @@
 namespace rlx {
 
 // Dense heads (nr_atoms = 101 or 2 * act_dim outputs: widths the float4-tiled GEMM stages do not take -- their contraction and
-// leading dimensions have to be multiples of four).  K <= 768 inputs, any N; small next to the trunk, so plain kernels.
+// leading dimensions have to be multiples of four).  Any K (the callers' widths end at 1024) and N; small next to the trunk, so
+// plain kernels.
 // out[M, N] = H[M, K] @ W[K, N] + b: a workgroup of 128 threads per 8 rows x 128 columns, thread <-> output column.  The H values
 // of a row are the same for every lane: their addresses are wave-uniform, so they arrive through the scalar cache as SGPR operands
 // of the FMAs -- no LDS, no barrier, eight W loads in flight per thread.  (With H in LDS the kernel was LDS-issue bound: eight

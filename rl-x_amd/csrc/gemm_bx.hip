@@ -693,7 +693,7 @@ int bx_prepare_mats(rlx_ctx* ctx, const BxMat* mats, int n, hipStream_t st) {
   int64_t entries = 0;
   for (int i = 0; i < n; ++i) {
     if (mats[i].K % 4 != 0 || mats[i].N % 4 != 0) continue;
-    if (jobs.n + 2 > BX_MAX_JOBS) break;
+    if (jobs.n + (mats[i].fwd ? 1 : 0) + (mats[i].trans ? 1 : 0) > BX_MAX_JOBS) break;
     if (mats[i].fwd) add_job(jobs, blocks, entries, mats[i].W, mats[i].N, mats[i].K, mats[i].N, 0);
     if (mats[i].trans) add_job(jobs, blocks, entries, mats[i].W, mats[i].N, mats[i].N, mats[i].K, 1);
   }

@@ -11,7 +11,7 @@
 namespace rlx {
 
 // ---- dense_head.hip
-// out[M, N] = H[M, K] @ W[K, N] + b (K <= 768, any N)
+// out[M, N] = H[M, K] @ W[K, N] + b (any K and N: FastSAC's widths end at 768, FastTD3's at 1024)
 int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
 // gW != NULL: weight / bias gradients from H_dH = H (slab partials into the stage arena: head_stage_floats); then dH over H_dH,
 // times ReLU'(H) with relu_mask
@@ -234,16 +234,25 @@ static inline size_t chain_stage_floats(const rlx_ctx* ctx, const Chain& L, int6
   return n;
 }
 
-// weight images of the hidden layers of several chains; bwd: the pass needs the transposed images too (input gradients)
+// weight images of the hidden layers of several chains; bwd: the pass needs the transposed images too (input gradients).
+// The budget is the image builder's job table: BX_MAX_JOBS images in one launch, a forward image is one job and a transposed one
+// another.  Matrices are taken in the order listed (nets[0] first, layer 0 first) and the list ENDS at the first matrix whose
+// jobs no longer fit: that layer and everything after it run on the exact engine.  No descriptor its two callers (fastsac.hip,
+// fasttd3.hip) accept gets there -- the largest is FastSAC's critic update with four hidden layers: 4 + 2 * 4 + 2 * (4 + 3) = 26
+// jobs (FastTD3: 3 + 2 * 3 + 2 * (3 + 2) = 19).  mpo.hip registers its two matrices through net_images directly.
 struct NetRef { const float* p; const Chain* L; bool bwd; };
 static inline int trunk_images(rlx_ctx* ctx, const NetRef* nets, int n, int64_t M, hipStream_t st) {
   BxMat mats[BX_MAX_JOBS];
-  int k = 0;
-  for (int i = 0; i < n; ++i)
+  int k = 0, jobs = 0;
+  bool full = false;
+  for (int i = 0; i < n && !full; ++i)
     for (int l = 0; l < nets[i].L->n_hidden; ++l) {
       const Block& o = nets[i].L->layer[l];
-      if (o.in % 4 != 0 || k >= BX_MAX_JOBS / 2) continue;      // (a ragged first layer stays on the exact engine)
-      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, nets[i].bwd && l > 0};
+      if (o.in % 4 != 0) continue;                               // (a ragged first layer stays on the exact engine)
+      const bool trans = nets[i].bwd && l > 0;
+      if (jobs + 1 + (trans ? 1 : 0) > BX_MAX_JOBS) { full = true; break; }
+      jobs += 1 + (trans ? 1 : 0);
+      mats[k++] = BxMat{nets[i].p + o.W, o.in, o.out, true, trans};
     }
   return net_images(ctx, mats, k, M, st);
 }

@@ -53,29 +53,35 @@ def make_params(seed, obs_dim, act_dim, nr_atoms, critic_obs_dim=None, policy_hi
     return policy, critics
 
 
-def forward(flat, in_dim, hidden, out_dim, x):
-    """flat, x: torch tensors.  -> head output [M, out_dim] of the ReLU network."""
+def forward(flat, in_dim, hidden, out_dim, x, keep=None):
+    """flat, x: torch tensors.  -> head output [M, out_dim] of the ReLU network.  keep (a list) receives (input rows, pre-activation)
+    of every hidden layer; a pre-activation that takes part in a backward keeps its gradient (.grad after it)."""
     off, d, h = 0, in_dim, x
     for li, width in enumerate(list(hidden) + [out_dim]):
         W = flat[off:off + d * width].reshape(d, width); off += d * width
         b = flat[off:off + width]; off += width
+        x_in = h
         h = h @ W + b
         if li < len(hidden):
+            if keep is not None:
+                if h.requires_grad:
+                    h.retain_grad()
+                keep.append((x_in, h))
             h = torch.relu(h)
         d = width
     return h
 
 
-def _t(a):
-    return torch.tensor(np.asarray(a, dtype=np.float64))
+def _t(a, dtype=np.float64):
+    return torch.tensor(np.asarray(a, dtype=dtype))
 
 
-def policy_action(pflat, obs_dim, act_dim, obs, hidden=POLICY_HIDDEN):
-    return torch.tanh(forward(pflat, obs_dim, hidden, act_dim, obs))
+def policy_action(pflat, obs_dim, act_dim, obs, hidden=POLICY_HIDDEN, keep=None):
+    return torch.tanh(forward(pflat, obs_dim, hidden, act_dim, obs, keep))
 
 
-def critic_logits(qflat, obs_dim, act_dim, nr_atoms, obs, act, hidden=CRITIC_HIDDEN):
-    return forward(qflat, obs_dim + act_dim, hidden, nr_atoms, torch.cat([obs, act], dim=1))
+def critic_logits(qflat, obs_dim, act_dim, nr_atoms, obs, act, hidden=CRITIC_HIDDEN, keep=None):
+    return forward(qflat, obs_dim + act_dim, hidden, nr_atoms, torch.cat([obs, act], dim=1), keep)
 
 
 def act(pflat, obs_dim, act_dim, obs, eps, noise_scales, low=None, high=None, hidden=POLICY_HIDDEN):
@@ -90,19 +96,22 @@ def act(pflat, obs_dim, act_dim, obs, eps, noise_scales, low=None, high=None, hi
 
 
 def critic_step(pflat, q1, q2, t1, t2, obs_dim, act_dim, nr_atoms, batch, noise_next, hp, clipped, critic_batch=None,
-                policy_hidden=POLICY_HIDDEN, critic_hidden=CRITIC_HIDDEN):
+                policy_hidden=POLICY_HIDDEN, critic_hidden=CRITIC_HIDDEN, dtype=np.float64, trace=None):
     """batch = (states, next_states, actions, rewards, dones, truncations, n_steps) with the POLICY's observation columns;
     critic_batch = (critic states, critic next states) or None (the same columns).  obs_dim: the critic's observation width.
+    dtype: the precision the whole step is evaluated in (np.float32: what float32 alone costs).  trace (a list): receives
+    forward's `keep` records of every network pass, in call order.
     -> dict(q_loss, q_min, q_max, g_q1, g_q2, next_actions)"""
+    _t = lambda x: torch.tensor(np.asarray(x, dtype=dtype))
     s, s2, a, rew, done, trunc, nst = (_t(x) for x in batch)
     cs, cs2 = (s, s2) if critic_batch is None else (_t(critic_batch[0]), _t(critic_batch[1]))
     with torch.no_grad():
         pin = s2.shape[1]
         noise = torch.clamp(_t(noise_next) * hp["smoothing_epsilon"], -hp["smoothing_clip_value"], hp["smoothing_clip_value"])
-        a2 = torch.clamp(policy_action(_t(pflat), pin, act_dim, s2, policy_hidden) + noise, -1.0, 1.0)
-        nl1 = critic_logits(_t(t1), obs_dim, act_dim, nr_atoms, cs2, a2, critic_hidden).numpy()
-        nl2 = critic_logits(_t(t2), obs_dim, act_dim, nr_atoms, cs2, a2, critic_hidden).numpy()
-    zero = np.zeros(rew.shape[0])
+        a2 = torch.clamp(policy_action(_t(pflat), pin, act_dim, s2, policy_hidden, trace) + noise, -1.0, 1.0)
+        nl1 = critic_logits(_t(t1), obs_dim, act_dim, nr_atoms, cs2, a2, critic_hidden, trace).numpy()
+        nl2 = critic_logits(_t(t2), obs_dim, act_dim, nr_atoms, cs2, a2, critic_hidden, trace).numpy()
+    zero = np.zeros(rew.shape[0], dtype)
     args = (rew.numpy(), done.numpy(), trunc.numpy(), nst.numpy(), zero, 0.0, hp["gamma"], hp["v_min"], hp["v_max"])
     p1, v1 = c51.project(nl1, *args)
     p2, v2 = c51.project(nl2, *args)
@@ -111,8 +120,8 @@ def critic_step(pflat, q1, q2, t1, t2, obs_dim, act_dim, nr_atoms, batch, noise_
     else:
         tgt1, tgt2 = p1, p2
     Q1, Q2 = _t(q1).requires_grad_(True), _t(q2).requires_grad_(True)
-    l1 = critic_logits(Q1, obs_dim, act_dim, nr_atoms, cs, a, critic_hidden)
-    l2 = critic_logits(Q2, obs_dim, act_dim, nr_atoms, cs, a, critic_hidden)
+    l1 = critic_logits(Q1, obs_dim, act_dim, nr_atoms, cs, a, critic_hidden, trace)
+    l2 = critic_logits(Q2, obs_dim, act_dim, nr_atoms, cs, a, critic_hidden, trace)
     loss = -(_t(tgt1) * torch.log_softmax(l1, dim=1)).sum(dim=1).mean() - (_t(tgt2) * torch.log_softmax(l2, dim=1)).sum(dim=1).mean()
     loss.backward()
     return dict(q_loss=float(loss.detach()), q_min=float(v1.min()), q_max=float(v1.max()), g_q1=Q1.grad.numpy(), g_q2=Q2.grad.numpy(),
@@ -121,15 +130,16 @@ def critic_step(pflat, q1, q2, t1, t2, obs_dim, act_dim, nr_atoms, batch, noise_
 
 
 def policy_step(pflat, q1, q2, obs_dim, act_dim, nr_atoms, states, hp, clipped, critic_states=None, policy_hidden=POLICY_HIDDEN,
-                critic_hidden=CRITIC_HIDDEN):
-    """-> dict(policy_loss, g_policy, q_value, actions)"""
+                critic_hidden=CRITIC_HIDDEN, dtype=np.float64, trace=None):
+    """dtype, trace: as in critic_step (the atoms z stay float64).  -> dict(policy_loss, g_policy, q_value, actions)"""
+    _t = lambda x: torch.tensor(np.asarray(x, dtype=dtype))
     s = _t(states)
     cs = s if critic_states is None else _t(critic_states)
     P = _t(pflat).requires_grad_(True)
-    a = policy_action(P, s.shape[1], act_dim, s, policy_hidden)
+    a = policy_action(P, s.shape[1], act_dim, s, policy_hidden, trace)
     z = torch.linspace(hp["v_min"], hp["v_max"], nr_atoms, dtype=torch.float64)
-    v1 = (torch.softmax(critic_logits(_t(q1), obs_dim, act_dim, nr_atoms, cs, a, critic_hidden), dim=1) * z).sum(dim=1)
-    v2 = (torch.softmax(critic_logits(_t(q2), obs_dim, act_dim, nr_atoms, cs, a, critic_hidden), dim=1) * z).sum(dim=1)
+    v1 = (torch.softmax(critic_logits(_t(q1), obs_dim, act_dim, nr_atoms, cs, a, critic_hidden, trace), dim=1) * z).sum(dim=1)
+    v2 = (torch.softmax(critic_logits(_t(q2), obs_dim, act_dim, nr_atoms, cs, a, critic_hidden, trace), dim=1) * z).sum(dim=1)
     q = torch.minimum(v1, v2) if clipped else (v1 + v2) / 2.0
     loss = -q.mean()
     loss.backward()

@@ -1,0 +1,138 @@
+"""Python mirror of the host selection arithmetic the FastSAC / FastTD3 passes go through (rl-x_amd/csrc: net_pass.h, dense_head.hip,
+mlp.hip, gemm_bx.h / gemm_bx.hip, fastsac.hip): which kernel, which grid and which GEMM engine a shape gets.  The shape tests
+recompute each case's claims from these, and build the engine each profiled GEMM row has to show."""
+
+BX_MAX_JOBS = 32          # gemm_bx.h
+SPLIT_ROWS = 4096         # net_images / bx_dw_usable: rows from which the split-operand engine serves a pass
+HEAD_FWD_MAX_LDS = 128 * 1024
+F16_MAX = 65504.0
+X_WLIMIT, X_ALIMIT = 1023.0, 4094.0     # gemm_bx.h: |weight| and |activation| inside the fp16 window of the split operands
+
+
+def div_up(a, b):
+    return -(-a // b)
+
+
+def pad4(n):
+    return (n + 3) & ~3
+
+
+def dx_cols_ok(K, nc):
+    """mlp.hip dx_cols_ok: launch_dx_cols takes a first layer of width K and nc input columns"""
+    return 1 <= nc <= 64 and K % 4 == 0 and (16 * (K + 4) + K * nc) * 4 <= HEAD_FWD_MAX_LDS
+
+
+def head_nj(K, N):
+    """dense_head.hip fs_head_bwd: the tiled kernel's NJ (2 / 4 / 8 / 12), 0 = the untiled kernel"""
+    TK = K // 8
+    TN = 256 // TK if 0 < TK <= 256 else 0
+    nj = div_up(N, TN) if TN else 99
+    if not (K % 8 == 0 and nj <= 12 and 16 * (K + N) * 4 <= 48 * 1024):
+        return 0
+    return 2 if nj <= 2 else 4 if nj <= 4 else 8 if nj <= 8 else 12
+
+
+def head_masked_threads(K):
+    """threads of k_fs_head_dw_tiled with tk >= TK (idle)"""
+    TK = K // 8
+    return 256 - TK * (256 // TK)
+
+
+def rows_grid(num_cus, M):
+    """net_pass.h rows_grid -> (workgroups, capped)"""
+    g = div_up(M, 4)
+    return (num_cus * 8, True) if g > num_cus * 8 else (max(g, 1), False)
+
+
+def bwd_rows_grid(num_cus, M):
+    g = div_up(M, 16)
+    return (num_cus * 4, True) if g > num_cus * 4 else (max(g, 1), False)
+
+
+def elem_grid(n):
+    """net_pass.h elem_grid / fs_concat: 256-thread blocks, at most 4096 -> (blocks, capped)"""
+    g = div_up(n, 256)
+    return (4096, True) if g > 4096 else (max(g, 1), False)
+
+
+def policy_grad_grid(B, A):
+    """rlx_fastsac_policy_update_f32: k_fs_policy_grad's grid, at most 2048 blocks"""
+    g = div_up(B * A, 256)
+    return (2048, True) if g > 2048 else (g, False)
+
+
+def sample_rows_per_block(A):
+    """k_fs_sample: (rows per 256-thread block, idle trailing threads)"""
+    rpb = 256 // A
+    return rpb, 256 - rpb * A
+
+
+def bx_grad_scale(rows):
+    """gemm_bx.h bx_grad_scale: 8 * 2^ceil(log2 rows)"""
+    s, r = 8.0, 1
+    while r < rows and s < 1e9:
+        r, s = r << 1, s * 2.0
+    return s
+
+
+def bx_dw_usable(bx, M, Kd, ldh, N):
+    return bool(bx) and M >= SPLIT_ROWS and N % 4 == 0 and ldh % 4 == 0 and ldh >= pad4(Kd)
+
+
+def trunk_images(nets):
+    """net_pass.h trunk_images over nets = [(in_dim, hidden, bwd)] -> (matrices, jobs, {(net index, layer)} that got images).  The
+    list ends at the first matrix whose jobs (one forward image, one transposed for an input gradient) pass BX_MAX_JOBS."""
+    mats, jobs, have = 0, 0, set()
+    for i, (in_dim, hidden, bwd) in enumerate(nets):
+        d = in_dim
+        for l, w in enumerate(hidden):
+            if d % 4 == 0:
+                need = 1 + (1 if bwd and l > 0 else 0)
+                if jobs + need > BX_MAX_JOBS:
+                    return mats, jobs, have
+                mats, jobs = mats + 1, jobs + need
+                have.add((i, l))
+            d = w
+    return mats, jobs, have
+
+
+def expected_engines(update, bx, B, p_in, p_hidden, c_in, c_hidden, A):
+    """{(kernel, M, N, K): engine} of every trunk GEMM the profiler sees in one `update` ("critic" / "policy") of FastSAC or FastTD3
+    (prof rows: k_gemm_fwd (rows, out, in); k_gemm_dx (rows, in, out); k_gemm_dw (in, out, rows)).  c_in = critic obs + A.
+    Split-operand engine (1) from 4096 rows on, when it is switched on: every forward whose in % 4 == 0 and whose image fitted
+    the job table, every input gradient of a layer l > 0, every weight gradient bx_dw_usable accepts (row pitches are padded to 4)."""
+    if update == "critic":       # policy, two targets (forward only), two online critics (forward, backward with weight gradients)
+        nets = [(p_in, p_hidden, False), (c_in, c_hidden, False), (c_in, c_hidden, False), (c_in, c_hidden, True), (c_in, c_hidden, True)]
+        grads, dx_first = {3, 4}, set()
+    else:                        # policy (backward with weight gradients), two critics (input gradients down to the action columns)
+        nets = [(p_in, p_hidden, True), (c_in, c_hidden, True), (c_in, c_hidden, True)]
+        grads, dx_first = {0}, {1, 2}
+    on = bool(bx) and B >= SPLIT_ROWS
+    have = trunk_images(nets)[2] if on else set()
+    out = {}
+
+    def put(key, eng):
+        assert out.setdefault(key, eng) == eng, ("two GEMMs of one shape on different engines", key)
+    for i, (in_dim, hidden, bwd) in enumerate(nets):
+        d = in_dim
+        for l, w in enumerate(hidden):
+            put(("k_gemm_fwd", B, w, d), 1 if (i, l) in have else 0)
+            if bwd and l > 0:
+                put(("k_gemm_dx", B, d, w), 1 if (i, l) in have else 0)
+            if bwd and l == 0 and i in dx_first and not dx_cols_ok(w, A):
+                put(("k_gemm_dx", B, d, w), 0)                      # first_layer_dx's whole-GEMM fallback: no transposed image
+            if i in grads:
+                put(("k_gemm_dw", d, w, B), 1 if bx_dw_usable(on, B, d, pad4(d), w) else 0)
+            d = w
+    return out
+
+
+def check_engines(rows, expected):
+    """every profiled trunk GEMM row has the engine the selection code gives its shape, and every expected shape was seen"""
+    seen = {}
+    for q in rows:
+        if q["kernel"] in ("k_gemm_fwd", "k_gemm_dx", "k_gemm_dw"):
+            seen.setdefault((q["kernel"], q["M"], q["N"], q["K"]), set()).add(q["engine"])
+    bad = {k: (sorted(v), expected.get(k)) for k, v in seen.items() if v != {expected.get(k)}}
+    assert not bad, bad
+    assert set(expected) <= set(seen), sorted(set(expected) - set(seen))

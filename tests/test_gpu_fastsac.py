@@ -7,26 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+from fastsac_cases import _hp, _t
 from oracle import fastsac as ofs
-from rlx_amd.hip import FastSacHparams, lnmlp_desc
+from rlx_amd.hip import lnmlp_desc
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(__file__), "golden", "reference_fastsac.npz")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(dev)
-
-
-def _hp(h, nr_atoms, clipped):
-    hp = FastSacHparams()
-    for k in ("gamma", "tau", "v_min", "v_max", "log_std_min", "log_std_max", "target_entropy", "weight_decay"):
-        setattr(hp, k, float(h[k]))
-    hp.lr_policy = hp.lr_critic = hp.lr_alpha = float(h["learning_rate"])
-    hp.adam_b1, hp.adam_b2, hp.adam_eps = float(h["adam_beta1"]), float(h["adam_beta2"]), 1e-8
-    hp.nr_atoms, hp.clipped_double_q = int(nr_atoms), int(bool(clipped))
-    hp.max_grad_norm = float(h.get("max_grad_norm", -1.0))      # fixture case 2: 0.05 (torch clip_grad_norm_ active in both steps)
-    return hp
 
 
 def _fixture_case(c):
@@ -111,7 +97,8 @@ def test_critic_and_policy_steps_match_the_reference_closures(ctx, dev, c):
 
 def test_steps_at_the_default_batch_against_the_float64_oracle(ctx, dev):
     """B = 8192 (fastsac/pytorch/default_config.py:17), obs 48 / act 12, nr_atoms 101: the weight-gradient kernels run on the
-    split-operand engine at this size; second optimizer step (non-zero moments)."""
+    split-operand engine at this size; the first optimizer step (opt_count 0, zero moments -- the second step, with non-zero
+    moments, is test_gpu_fastsac_shapes.py's)."""
     from rlx_amd.hip import lib as L
     rng = np.random.default_rng(2)
     O, A, NA, B = 48, 12, 101, 8192

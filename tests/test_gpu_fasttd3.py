@@ -9,29 +9,11 @@ import torch
 
 import fasttd3_twin as tw
 from oracle import prng
-from rlx_amd.hip import FastTd3Hparams, relu_mlp_desc
+from fasttd3_cases import KINK_TAU, MAX_FLIPS, _explain, _fwd_flip, _hp, _kinks, _rel, _t
+from rlx_amd.hip import relu_mlp_desc
 from test_fasttd3_twin import check_sampled, fixture_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(dev)
-
-
-def _hp(h, nr_atoms, clipped):
-    hp = FastTd3Hparams()
-    for k in ("gamma", "tau", "v_min", "v_max", "weight_decay", "smoothing_epsilon", "smoothing_clip_value", "max_grad_norm"):
-        setattr(hp, k, float(h[k]))
-    hp.lr_policy = hp.lr_critic = float(h["learning_rate"])
-    hp.adam_b1, hp.adam_b2, hp.adam_eps = 0.9, 0.999, 1e-8
-    hp.nr_atoms, hp.clipped_double_q = int(nr_atoms), int(bool(clipped))
-    return hp
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
 @pytest.mark.parametrize("c", [0, 1, 2])
@@ -142,63 +124,6 @@ def test_critic_and_policy_steps_match_the_reference_closures(ctx, dev, c):
     assert pmv[1] == pytest.approx(float(g("policy_grad_norm")), rel=1e-5)
     check_sampled(z, "c%d_gpolicy" % c, pm.cpu().numpy().astype(np.float64) / 0.1, 1e-5)
     check_sampled(z, "c%d_pparams_after" % c, P.cpu().numpy(), 1e-5)
-
-
-def _kinks(flat, in_dim, hidden, x, tau=8e-6):
-    """[(|z| / rms, row, layer, unit)] of the ReLU pre-activations of the batch within tau of zero relative to their row's RMS
-    (float64): a unit-sample within fp32 rounding of its kink has an undefined fp32 gradient -- any fp32 evaluation may land on
-    either side, and that sample's whole backward contribution through the unit flips with it."""
-    h, off, d, out = x.astype(np.float64), 0, in_dim, []
-    for li, w in enumerate(hidden):
-        W = flat[off:off + d * w].reshape(d, w); off += d * w
-        z = h @ W + flat[off:off + w]; off += w
-        m = np.abs(z) / np.sqrt((z * z).mean(axis=1, keepdims=True))
-        out += [(float(m[i, j]), int(i), li, int(j)) for i, j in zip(*np.nonzero(m < tau))]
-        h, d = np.maximum(z, 0.0), w
-    return out
-
-
-def _fwd_flip(flat, in_dim, hidden, out_dim, x, flips):
-    """the twin's ReLU network on ONE row with the on / off state of the units `flips` ({(layer, unit)}) inverted"""
-    off, d, h = 0, in_dim, x
-    for li, w in enumerate(list(hidden) + [out_dim]):
-        W = flat[off:off + d * w].reshape(d, w); off += d * w
-        z = h @ W + flat[off:off + w]; off += w
-        if li < len(hidden):
-            m = (z > 0).to(z.dtype)
-            for (l, j) in flips:
-                if l == li:
-                    m[0, j] = 1.0 - m[0, j]
-            z = z * m
-        h, d = z, w
-    return h
-
-
-def _explain(gd, ge, cands, delta, limit):
-    """Which kink / tie candidates did the device evaluate on their other side?  Candidates are taken closest to their kink first;
-    one is taken when its alternative -- ge + delta(cand): the twin's gradient with that one unit-sample / row choice inverted --
-    brings the device result closer (by more than 0.1 %).  That is the test 2 r.d > |d|^2 for the residual r = gd - ga: a
-    candidate that did not flip on the device has no component in r, so it is not taken; flips are independent samples, so their
-    alternatives add.  -> (adjusted expectation, taken candidates)"""
-    ga, taken = ge.copy(), []
-    for c in sorted(cands, key=lambda c: c[0]):
-        if _rel(gd, ga) < 1e-6 or len(taken) >= limit:
-            break
-        alt = ga + delta(c)
-        if _rel(gd, alt) < 0.999 * _rel(gd, ga):
-            ga, taken = alt, taken + [c]
-    return ga, taken
-
-
-# ReLU kink window (|z| / row RMS of the float64 pre-activation) and the number of flips allowed per update step.  Measured on
-# this test's clipped policy step: a plain float32 evaluation of the formula (torch on the CPU) is 3.5e-5 from float64, and
-# 7.9e-8 once it takes its ReLU masks from float64 -- the whole difference is 10 unit-samples on the other side of their kink
-# (1 in the policy, 9 in the critics), at margins 8e-9 .. 8.4e-7; the exact-fp32 and split-operand engines land at 3.5e-5 and
-# 3.7e-5 on the same inputs before any flip is accounted for.  On the MI355X (split-operand engine) the steps below take 3 .. 4 flips
-# (critic steps; mean-of-two policy step) and 13 in the clipped policy step, 4.2e-5 -> 5.7e-6; the first of those 13 is the
-# policy's unit-sample that the CPU float32 evaluation flips too.
-KINK_TAU = 4e-6
-MAX_FLIPS = 16
 
 
 @pytest.mark.parametrize("clipped", [True, False])
