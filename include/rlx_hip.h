@@ -177,6 +177,10 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   twin (grid.y = 2) and valid-rows launches alike.  8 runs the same tile with the same LDS on 512 threads -- four waves per SIMD
  *   instead of two -- with the same arithmetic in the same order: bit-identical results (tests/test_gpu_tail32_waves.py); 4 is
  *   the earlier form.
+ * Round 8: "ln_row_once" (1 default; 0 or 1, anything else is RLX_EINVAL): in k_dx_l1bwd's split-operand forms and k_l12fwd every
+ *   wave computes the LayerNorm mean and 1 / std of a tile's 32 rows once (one row per lane) and the per-row loops load them,
+ *   instead of every lane recomputing both for each of its 16 rows at every use.  The same operations in the same order:
+ *   bit-identical results (tests/test_gpu_ln_row_once.py); 0 is the earlier form.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,

@@ -144,6 +144,11 @@ struct rlx_ctx {
   int tail32_waves = 8;                   // k_tail32_bx: waves per 32-row tile, 4 or 8 (same LDS: two or four waves per SIMD; bit-identical results).
                                           // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 67.14 vs 68.34 ms per iteration at 32768-row
                                           // minibatches (block-to-block sd 0.19 / 0.24), 112.41 vs 115.96 at 4096 rows
+  int ln_row_once = 1;                    // k_dx_l1bwd<BX> / k_l12fwd: 1 every wave computes a row's LayerNorm mean and 1 / std ONCE (lanes 0-31, one row
+                                          // each: ln_row_stats in l1fused.hip) and the per-row loops load them; 0 the earlier form, every lane
+                                          // recomputes both for each of its 16 rows at every use.  Same operations in the same order: bit-identical.
+                                          // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 63.80 vs 65.65 ms per iteration at 32768-row
+                                          // minibatches (block-to-block sd 0.08 / 0.13), 108.82 vs 110.85 at 4096 rows
   int ppo_twin = -1;                      // PPO update: policy || critic as twin launches (grid.y = 2) on ONE stream.  -1 (default): for
                                           // minibatches of 6144 to 16384 rows on one rank (below: two chains with grouped gathers), never with a real
                                           // RCCL communicator of more than one rank (its all-reduce would be exposed: twin_shapes_ok);

@@ -241,6 +241,11 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
     ctx->tail32_waves = value;
     return RLX_OK;
   }
+  if (std::string(name) == "ln_row_once") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: ln_row_once is 0 or 1");
+    ctx->ln_row_once = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "bx_force_mi") { ctx->bx_force_mi = value; return RLX_OK; }
   if (std::string(name) == "adam_emit") { ctx->adam_emit = value != 0; return RLX_OK; }
   if (std::string(name) == "bx_debug") { ctx->bx_debug = value; return RLX_OK; }

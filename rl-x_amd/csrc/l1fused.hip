@@ -37,6 +37,9 @@ namespace rlx {
 #ifndef RLX_LF_ABL
 #define RLX_LF_ABL 0   // timing ablation of k_dx_l1bwd (round-4 one-off scripts, git history): 1 no main product, 2 nothing after it, 4 no dW1 MFMAs, 8 no z1 MFMAs
 #endif
+#ifndef RLX_LF_STAMPS
+#define RLX_LF_STAMPS 0   // 1: phase stamps of k_dx_l1bwd (tools/dx_phases.py), a tuning aid: never in a build that is timed as a whole
+#endif
 constexpr int LF_ROWS = 32;
 constexpr int LF_THREADS = 256;
 constexpr int LF_XS = 33;  // Xs[row][k] stride
@@ -56,6 +59,21 @@ __device__ __forceinline__ float half_sum(float v) {
   return __int_as_float((int)r[0]) + __int_as_float((int)r[1]);
 }
 
+// LayerNorm mean and 1 / std of a tile's 32 rows, ONCE per wave and row.  v: the wave's folded sums as the fold leaves them in registers,
+// lanes 0-31 sum z and lanes 32-63 sum z^2 of row (lane & 31); v_permlane32_swap hands every lane both sums of its row.  Every lane
+// computes mean and 1 / std (rs) of row (lane & 31) -- one rsqrt sequence per lane instead of one per lane, row and use in the per-row
+// loops -- and the value returned goes to the wave's [2][32] LDS slot in the sums' place: lanes 0-31 mean, lanes 32-63 1 / std.
+// The operations and their order are the per-row loops' earlier ones (m = s invH; t = round(m m); fma(ss, invH, -t); max; add;
+// rsqrt), pinned against -ffp-contract=fast: bit-identical results.
+__device__ __forceinline__ float ln_row_stats(float v, int lane, float invH, float& rs) {
+  const unsigned u = (unsigned)__float_as_int(v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  const float s = __int_as_float((int)r[0]), ss = __int_as_float((int)r[1]);
+  const float mean = __fmul_rn(s, invH);
+  rs = rsqrtf(fmaxf(0.f, __fmaf_rn(ss, invH, -__fmul_rn(mean, mean))) + 1e-6f);
+  return lane < 32 ? mean : rs;
+}
+
 struct L1FusedArgs {
   const float* X;      // [M, O]
   const float* dZ2;    // [M, N2]
@@ -72,6 +90,7 @@ struct L1FusedArgs {
   float gs, gso;       // BX kernels: power-of-two scale of the dZ2 operand and 1 / (gs * X_WSCALE)
   const void* W1x;     // BX kernels: fragment-ordered split image of B(k = obs index, j = h1 column), K padded to 32 (two 16-k blocks)
   const uint32_t* xmax;  // BX kernels, optional: DEVICE bit pattern of max |X| -> power-of-two scale of the X planes (common.h: x_scale_from_max); NULL: X_ASCALE
+  unsigned long long* stamps;   // tuning aid (rlx_dbg_set_stamps, -DRLX_LF_STAMPS=1): clock64() of thread 0 of workgroup 0 at the phase boundaries of its first two tiles
 };
 
 // BX: LDS image of the dZ2 row tile as two fp16 planes (gemm_bx.h), [32 rows][N2 k] with 2 * N2 bytes per row; the 16-byte k-slots of a
@@ -113,9 +132,12 @@ __device__ __forceinline__ void lf_x_stage(char* __restrict__ img, int r, int k,
 // waves on every SIMD so one wave's VALU-heavy LayerNorm epilogue fills the issue slots the other
 // leaves idle (a single wave per SIMD ran the epilogue at ~7 cycles per instruction).
 // TWIN: grid.y == 2, blockIdx.y == 1 works on the argument set a2 (the second of two equally shaped networks on the same rows)
-template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN = false>
+// ROW1 (option ln_row_once, LN only): the row statistics are finished once per wave and row (ln_row_stats) and the per-row loops load
+// mean and 1 / std; false: every lane recomputes them for each of its 16 rows in both loops (the earlier form, kept for the A/B)
+template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN = false, bool ROW1 = false>
 __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1FusedArgs a2) {
   if (TWIN && blockIdx.y) a = a2;
+  static_assert(!ROW1 || LN, "ROW1 is a form of the LayerNorm statistics");
   constexpr int H1 = 32 * NT * NW;
   constexpr int NTHREADS = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -206,6 +228,19 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
     stage_store(0);
   }
   int buf = 0;
+  // phase stamps (tools/dx_phases.py): compiled in only with -DRLX_LF_STAMPS=1
+#if RLX_LF_STAMPS
+  int sti = 0;
+#define LF_STAMP() if (a.stamps && t == 0 && blockIdx.x == 0 && blockIdx.y == 0 && sti < 18) a.stamps[sti++] = clock64();
+#define LF_WALL(I) if (a.stamps && t == 0 && blockIdx.x == 0 && blockIdx.y == 0) a.stamps[I] = wall_clock64();      // constant 100 MHz: calibrates the clock64 ticks
+#define LF_WALL_END() if (sti == 17) { LF_WALL(19) }      // the end of the second tile
+#else
+#define LF_STAMP()
+#define LF_WALL(I)
+#define LF_WALL_END()
+#endif
+  LF_STAMP()
+  LF_WALL(18)
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, buf ^= (dbuf ? 1 : 0)) {
     const int64_t r0 = tile * LF_ROWS;
     float* As = As0 + buf * a_img;
@@ -254,6 +289,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
       }
       __syncthreads();
     }
+    LF_STAMP()      // tile start: staged, past the top barrier
     // ---- main GEMM: dH1 tile; barrier-free K loop
     const float* a0 = As + li * AS + 4 * lh;
     if (RLX_LF_ABL & 1) {
@@ -315,6 +351,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[j][r]));
       continue;
     }
+    LF_STAMP()      // K loop (+ rescale, next tile's stage store)
     // ---- recompute z1 = X @ W1 + b1 in the same accumulator layout
     f32x16 z[NT];
     if (BX) {
@@ -356,6 +393,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
           z[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, w0[kk * H1 + 32 * j], z[j], 0, 0, 0);
       }
     }
+    LF_STAMP()      // z1 recompute
     // accumulator register r of half lh is row rho = (r&3) + 8*(r>>2) + 4*lh of the tile
     // LayerNorm row statistics.  Per-wave partials (4 rows per 16-B LDS store, lane 0 of each half), then
     // ONE wave folds the NW partials per row in fixed order, then every lane fetches its 16 rows with four
@@ -389,17 +427,23 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         }
       }
       __syncthreads();
+      float rs_row = 0.f;       // ROW1: 1 / std of row (lane & 31)
       {
         float v = 0.f;
 #pragma unroll
         for (int q = 0; q < NW; ++q) v += redA[((lane >> 5) * NW + q) * 32 + (lane & 31)];
-        totA[lane] = v;
+        totA[lane] = ROW1 ? ln_row_stats(v, lane, invH, rs_row) : v;      // ROW1: mean | 1 / std in the sums' place
       }
       if (BX && RLX_LF_DWSCALE && dw_scale == 0.f) {
         // scale of the dW1 operand (see the dW1 block below): gs / (largest 1 / std(z1) of this tile's 32 rows, as a power of
         // two) -- one value per lane from the wave's copy of the row statistics, a wave maximum, and the result lives in an SGPR
-        const float mean = totA[lane & 31] * invH;
-        float rs = rsqrtf(fmaxf(0.f, totA[32 + (lane & 31)] * invH - mean * mean) + 1e-6f);
+        float rs;
+        if (ROW1) {
+          rs = rs_row;
+        } else {
+          const float mean = totA[lane & 31] * invH;
+          rs = rsqrtf(fmaxf(0.f, totA[32 + (lane & 31)] * invH - mean * mean) + 1e-6f);
+        }
         if (r0 + (lane & 31) >= a.M) rs = 0.f;        // rows past the end of a ragged last tile are all-zero observations
         rs = fmaxf(rs, dpp_f(rs, 0));
         rs = fmaxf(rs, dpp_f(rs, 1));
@@ -411,6 +455,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         dw_scale = a.gs * x_pow2_inv(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rs))));
       }
     }
+    LF_STAMP()      // first reduction: partials, barrier, fold (+ ROW1: the row statistics, + first tile: dw_scale)
     // dy = dH1 * act'(h);  z <- xhat;  acc <- d xhat;  row sums m1, m2
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -424,7 +469,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * g + e;
         float mean = 0.f, rstd_r = 1.f;
-        if (red_on) {
+        if (ROW1) {
+          mean = sv[e];
+          rstd_r = ssv[e];
+        } else if (red_on) {
           mean = sv[e] * invH;
           rstd_r = rsqrtf(fmaxf(0.f, ssv[e] * invH - mean * mean) + 1e-6f);
         }
@@ -454,6 +502,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         }
       }
     }
+    LF_STAMP()      // element-wise loop 1
     if (red_on) {
       __syncthreads();
       float v = 0.f;
@@ -461,6 +510,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
       for (int q = 0; q < NW; ++q) v += redB[((lane >> 5) * NW + q) * 32 + (lane & 31)];
       totB[lane] = v * invH;
     }
+    LF_STAMP()      // second reduction: barrier, fold
     // dZ1 (in acc), bias gradient, and dW1 += X^T dZ1 with the accumulator registers as the B operand:
     // MFMA step r contracts row rho(r,0) (lanes 0-31) and row rho(r,1) (lanes 32-63).
     const float* xt = Xs + li;  // exact form, A operand: A[i = obs index li][k = lh] = X[rho(r, lh)][li]
@@ -470,15 +520,17 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
       if (red_on) {
         m1v = *reinterpret_cast<const lf_v4*>(totB + 8 * g + 4 * lh);
         m2v = *reinterpret_cast<const lf_v4*>(totB + 32 + 8 * g + 4 * lh);
-        sv2 = *reinterpret_cast<const lf_v4*>(totA + 8 * g + 4 * lh);           // the row statistics again (wave-private copy):
-        ssv2 = *reinterpret_cast<const lf_v4*>(totA + 32 + 8 * g + 4 * lh);     // 1 / std is recomputed instead of kept in 16 registers
+        if (!ROW1) sv2 = *reinterpret_cast<const lf_v4*>(totA + 8 * g + 4 * lh);     // the row statistics again (wave-private copy):
+        ssv2 = *reinterpret_cast<const lf_v4*>(totA + 32 + 8 * g + 4 * lh);     // 1 / std is re-read (ROW1) or recomputed instead of kept in 16 registers
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * g + e;
         const int rho = 8 * g + 4 * lh + e;
         float rstd_r = 1.f;
-        if (red_on) {
+        if (ROW1) {
+          rstd_r = ssv2[e];
+        } else if (red_on) {
           const float mean = sv2[e] * invH;
           rstd_r = rsqrtf(fmaxf(0.f, ssv2[e] * invH - mean * mean) + 1e-6f);
         }
@@ -492,6 +544,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         }
       }
     }
+    LF_STAMP()      // element-wise loop 2
     if (BX && !(RLX_LF_ABL & 4)) {
       // dW1 += X^T dZ1 on the fp16 pipe: A = XT planes (LDS), B = the lane's dZ1 values split in registers -- k-slot e of 16-k
       // step s_ is accumulator register 8 s_ + e (see lf_x_stage for the row order).
@@ -525,7 +578,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         }
       }
     }
+    LF_STAMP()      // dW1 product (issue only: its results are awaited in the next tile or the slab store)
+    LF_WALL_END()
   }
+#undef LF_WALL_END
+#undef LF_STAMP
+#undef LF_WALL
   // ---- one slab per workgroup
   float* out = a.partials + (int64_t)blockIdx.x * (O + 3) * H1;
 #pragma unroll
@@ -737,7 +795,8 @@ __device__ __forceinline__ void l12_xa_stage(char* __restrict__ img, int r, int 
   *reinterpret_cast<uint16_t*>(da + LF_XPLANE) = (uint16_t)p1;
 }
 
-template <int ACT, int NT2, bool TWIN, bool NTS = false>
+// ROW1 (option ln_row_once): as in k_dx_l1bwd -- mean and 1 / std once per wave and row (ln_row_stats); false: the earlier form
+template <int ACT, int NT2, bool TWIN, bool NTS = false, bool ROW1 = false>
 __global__ __launch_bounds__(512, NT2 == 1 ? 4 : 2) void k_l12fwd(L12Args a, L12Args a2) {
   if (TWIN && blockIdx.y) a = a2;
   constexpr int NW = 8, NT = 2, H1 = L12_H1, NTHREADS = 512, N2 = NW * NT2 * 32;
@@ -869,12 +928,18 @@ __global__ __launch_bounds__(512, NT2 == 1 ? 4 : 2) void k_l12fwd(L12Args a, L12
       float v = 0.f;
 #pragma unroll
       for (int q = 0; q < NW; ++q) v += redA[((lane >> 5) * NW + q) * 32 + (lane & 31)];
-      totA[lane] = v;
+      float rs_row;
+      totA[lane] = ROW1 ? ln_row_stats(v, lane, invH, rs_row) : v;      // ROW1: mean | 1 / std in the sums' place
     }
     if (a.stats && w == 0 && lane < 32 && r0 + lane < a.M) {      // [2][M]: what the recomputing weight-gradient kernel reads
-      const float mean = totA[lane] * invH;
-      a.stats[r0 + lane] = mean;
-      a.stats[a.M + r0 + lane] = rsqrtf(fmaxf(0.f, totA[32 + lane] * invH - mean * mean) + 1e-6f);
+      if (ROW1) {
+        a.stats[r0 + lane] = totA[lane];
+        a.stats[a.M + r0 + lane] = totA[32 + lane];
+      } else {
+        const float mean = totA[lane] * invH;
+        a.stats[r0 + lane] = mean;
+        a.stats[a.M + r0 + lane] = rsqrtf(fmaxf(0.f, totA[32 + lane] * invH - mean * mean) + 1e-6f);
+      }
     }
     L12_STAMP()
     // ---- normalise, activate; h1 -> HBM (128-byte row segments) and, as fp16 planes, into the LDS image of the second layer's A operand
@@ -888,8 +953,8 @@ __global__ __launch_bounds__(512, NT2 == 1 ? 4 : 2) void k_l12fwd(L12Args a, L12
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * gq + e;
         const int rho = 8 * gq + e;              // row inside the tile, minus the 4 * lh
-        const float mean = sv[e] * invH;
-        const float rs = rsqrtf(fmaxf(0.f, ssv[e] * invH - mean * mean) + 1e-6f);
+        const float mean = ROW1 ? sv[e] : sv[e] * invH;
+        const float rs = ROW1 ? ssv[e] : rsqrtf(fmaxf(0.f, ssv[e] * invH - mean * mean) + 1e-6f);
         const bool inb = r0 + rho + 4 * lh < a.M;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -989,6 +1054,7 @@ bool l12fwd_supported(const rlx_mlp_desc& d) {
 // tw (optional): a second network of the same shapes on the same rows (twin launch)
 int launch_l12fwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const float* params, const float* x, float* h1, float* h2,
                   const void* w1x, const void* w2x, int64_t M, hipStream_t st, const L12Twin* tw, float* stats) {
+  const bool row1 = ctx->ln_row_once != 0;
   const LayerOff &o0 = L.layer[0], &o1 = L.layer[1];
   L12Args a;
   a.X = x; a.W1x = w1x; a.b1 = params + o0.b; a.g = params + o0.g; a.be = params + o0.be; a.W2x = w2x; a.b2 = params + o1.b;
@@ -1008,25 +1074,32 @@ int launch_l12fwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const
   const int per = tw ? ctx->num_cus : 2 * ctx->num_cus;
   const int grid = (int)(nt < per ? nt : per);
   const size_t lds = (size_t)X_NP * LF_ROWS * L12_AROW + 2 * X_NP * LF_XPLANE + (2 * 8 * 32 + 8 * 64) * sizeof(float);
-#define RLX_L12_LAUNCH(NT2V)                                                                                       \
+#define RLX_L12_ATTR(...)                                                                                          \
+  RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_l12fwd<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#define RLX_L12_LAUNCH_ROW(NT2V, ROWV)                                                                             \
   {                                                                                                                \
     static AttrOnce attr_set;                                                                                        \
     if (!attr_set.done()) {                                                                                               \
-      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_l12fwd<RLX_ACT_ELU, NT2V, false>),            \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                    \
-      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_l12fwd<RLX_ACT_ELU, NT2V, true>),             \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                    \
-      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_l12fwd<RLX_ACT_ELU, NT2V, false, true>),      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                    \
+      RLX_L12_ATTR(RLX_ACT_ELU, NT2V, false, false, ROWV)                                                          \
+      RLX_L12_ATTR(RLX_ACT_ELU, NT2V, true, false, ROWV)                                                           \
+      RLX_L12_ATTR(RLX_ACT_ELU, NT2V, false, true, ROWV)                                                           \
       attr_set.mark();                                                                                               \
     }                                                                                                              \
-    if (tw) { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, true>), dim3(grid, 2), dim3(512), lds, st, a, a2); }         \
-    else if (M >= 16384) { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, false, true>), dim3(grid), dim3(512), lds, st, a, a2); } \
-    else { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, false>), dim3(grid), dim3(512), lds, st, a, a2); }              \
+    if (tw) { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, true, false, ROWV>), dim3(grid, 2), dim3(512), lds, st, a, a2); } \
+    else if (M >= 16384) { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, false, true, ROWV>), dim3(grid), dim3(512), lds, st, a, a2); } \
+    else { RLX_PLAUNCH((k_l12fwd<RLX_ACT_ELU, NT2V, false, false, ROWV>), dim3(grid), dim3(512), lds, st, a, a2); } \
+  }
+  // (the form is a template parameter chosen here, not a branch in the kernel: option ln_row_once)
+#define RLX_L12_LAUNCH(NT2V)                                                                                       \
+  {                                                                                                                \
+    if (row1) RLX_L12_LAUNCH_ROW(NT2V, true)                                                                       \
+    else RLX_L12_LAUNCH_ROW(NT2V, false)                                                                           \
   }
   if (N2 == 256) RLX_L12_LAUNCH(1)
   else RLX_L12_LAUNCH(2)
 #undef RLX_L12_LAUNCH
+#undef RLX_L12_LAUNCH_ROW
+#undef RLX_L12_ATTR
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }
@@ -1128,6 +1201,7 @@ int launch_l1fused(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, cons
   a.gs = ctx->bx_gscale;
   a.gso = X_WINV / a.gs;
   a.xmax = ctx->l1_xmax;
+  a.stamps = RLX_LF_STAMPS ? (unsigned long long*)ctx->dbg_stamps : nullptr;
   L1FusedArgs a2 = a;
   if (tw) {
     a2.dZ2 = tw->dZ2; a2.W1 = tw->params + o0.W; a2.b1 = tw->params + o0.b;
@@ -1163,10 +1237,22 @@ int launch_l1fused(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, cons
     else if (bxk) { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, LNV, true>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
     else { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, LNV, false>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); }    \
   }
+    // option ln_row_once (a template parameter chosen here, not a branch in the kernel): the split-operand LayerNorm forms with the row
+    // statistics finished once per wave and row; the exact-fp32 form (gemm_bx = 0) keeps the earlier loops
+#define RLX_LF_LAUNCH_ROW1(NTV, NWV, ACTV)                                                                      \
+  {                                                                                                            \
+    RLX_LF_ATTR((k_dx_l1bwd<NTV, NWV, ACTV, true, true, false, true>))                                         \
+    RLX_LF_ATTR((k_dx_l1bwd<NTV, NWV, ACTV, true, true, true, true>))                                          \
+    if (tw) { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, true, true, true, true>), dim3(grid, 2), dim3(64 * NWV), lds, st, a, a2); } \
+    else { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, true, true, false, true>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
+  }
+    if (H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first && bxk && ctx->ln_row_once) RLX_LF_LAUNCH_ROW1(2, 8, RLX_ACT_ELU)
+    else
     if (H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first) RLX_LF_LAUNCH(2, 8, RLX_ACT_ELU, true)
     else if (H1 == 256 && d.act == RLX_ACT_TANH && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_TANH, false)
     else if (H1 == 256 && d.act == RLX_ACT_RELU && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_RELU, false)
     else RLX_REQUIRE(false, RLX_EUNSUP, "l1fused: unsupported (hidden[0], act, ln) combination");
+#undef RLX_LF_LAUNCH_ROW1
 #undef RLX_LF_LAUNCH
 #undef RLX_LF_ATTR
   }
