@@ -95,6 +95,26 @@ inline void adam_job_plan(AdamJob& J, const TA& emit, const TB& emit_t) {
   J.n_rest_blocks = (int)(nb > 2048 ? 2048 : nb);      // (strided beyond that: every block re-reduces the norm's partials)
 }
 
+// host: the job of one parameter set at `step` (1-based).  sched_dev (optional, DEVICE {lr, 1 - b1^step, 1 - b2^step}): the
+// per-update values come from a device table instead of the launch arguments (the SAC update keeps them next to its key: one small
+// upload per call); emit (optional): the matrices of p whose weight images the step rewrites
+inline AdamJob make_adam_job(float* params, const float* grads, float* m, float* v, int64_t n, const float* partials, int n_partials,
+                             int64_t step, float lr, float max_norm, float b1, float b2, float* norm_out, const float* sched_dev,
+                             const BxEmit* emit, float* polyak_target, float tau, float weight_decay, int clip_mode) {
+  AdamJob J{params, grads, m, v, n, partials, n_partials, max_norm, norm_out, sched_dev, polyak_target, tau, weight_decay};
+  J.clip_mode = clip_mode;
+  J.lr = lr;
+  J.bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  J.bc2 = (float)(1.0 - pow((double)b2, (double)step));
+  BxEmit em;
+  em.n = 0;
+  if (emit) em = *emit;
+  BxEmit none;
+  none.n = 0;
+  adam_job_plan(J, em, none);
+  return J;
+}
+
 // one element's fp16 planes of val * X_WSCALE (bx_split2 in k_bx_wfrag, element by element)
 __device__ __forceinline__ void adam_split(float val, uint16_t& h0, uint16_t& h1) {
   uint32_t p0, p1;

@@ -1,5 +1,5 @@
-// dense_head.hip -- the kernels every network pass of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip shares (net_pass.h declares
-// their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat,
+// dense_head.hip -- the kernels every network pass of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip and espo.hip shares (net_pass.h
+// declares their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat,
 // the N(0, 1) noise block, and the row norm + activation kernels of a Block with their one launcher (norm_act).
 #include "ln_kernels.h"
 #include "net_pass.h"
@@ -47,9 +47,10 @@ __global__ __launch_bounds__(128) void k_fs_head_fwd(const float* __restrict__ H
       if (r0 + r < M) out[(r0 + r) * N + n] = acc[r] + bv;
   }
 }
-// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k.  RELU_MASK (FastTD3): H_dH
-// holds the ReLU output H on entry and dH * (H > 0) on exit (each entry is read by the thread that overwrites it).
-template <bool RELU_MASK>
+// dH[M, K] = d[M, N] @ W[K, N]^T: a workgroup per 8 rows, d rows in LDS, thread <-> input column k.  ACT != NONE: dH holds the
+// output H of a plain ACT block on entry and that block's dZ = dH act'(H) on exit (each entry is read by the thread that overwrites
+// it).  ReLU is a select, not a product: dH * 0 would be -0 / NaN where dH is negative / non-finite.
+template <int ACT>
 __global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d, const float* __restrict__ W, float* __restrict__ dH,
                                                     int64_t M, int K, int N) {
   extern __shared__ float s_d[];   // [8][N]
@@ -72,7 +73,8 @@ __global__ __launch_bounds__(256) void k_fs_head_dx(const float* __restrict__ d,
 #pragma unroll
     for (int r = 0; r < 8; ++r)
       if (r0 + r < M) {
-        if (RELU_MASK) acc[r] = dH[(r0 + r) * K + k] > 0.f ? acc[r] : 0.f;
+        if (ACT == RLX_ACT_RELU) acc[r] = dH[(r0 + r) * K + k] > 0.f ? acc[r] : 0.f;
+        else if (ACT != RLX_ACT_NONE) acc[r] = acc[r] * act_grad_from_out(dH[(r0 + r) * K + k], ACT);
         dH[(r0 + r) * K + k] = acc[r];
       }
   }
@@ -250,7 +252,9 @@ int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int6
 }
 
 int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
-                bool relu_mask) {
+                int act) {
+  RLX_REQUIRE(act == RLX_ACT_NONE || act == RLX_ACT_RELU || act == RLX_ACT_TANH || act == RLX_ACT_ELU, RLX_EUNSUP,
+              "fs_head_bwd: the input-gradient epilogue takes no activation, ReLU, tanh or ELU");
   if (gW) {
     const int boff = (K * N + 3) & ~3;
     const int64_t PS = boff + ((N + 3) & ~3);
@@ -281,8 +285,12 @@ int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float
     const int rc = stage_reduce(ctx, tab, nullptr, nullptr, st);
     if (rc) return rc;
   }
-  if (relu_mask) hipLaunchKernelGGL(k_fs_head_dx<true>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
-  else hipLaunchKernelGGL(k_fs_head_dx<false>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N);
+#define FS_HEAD_DX(ACT) hipLaunchKernelGGL(k_fs_head_dx<ACT>, dim3(div_up(M, 8)), dim3(256), (size_t)8 * N * sizeof(float), st, d, W, H_dH, M, K, N)
+  if (act == RLX_ACT_RELU) FS_HEAD_DX(RLX_ACT_RELU);
+  else if (act == RLX_ACT_TANH) FS_HEAD_DX(RLX_ACT_TANH);
+  else if (act == RLX_ACT_ELU) FS_HEAD_DX(RLX_ACT_ELU);
+  else FS_HEAD_DX(RLX_ACT_NONE);
+#undef FS_HEAD_DX
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }

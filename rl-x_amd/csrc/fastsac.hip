@@ -6,8 +6,8 @@
 // exact-fp32 MFMA engine below 4096 rows, the split-operand engine from there on -- trunk_images, net_pass.h), the dense-head
 // kernels of dense_head.hip and the row-wise LayerNorm + activation kernels of ln_kernels.h (k_ln_act_wide: widths up to 768,
 // eps argument, SiLU' from the recomputed pre-activation).  A network is a Chain of such blocks: its carve, forward, backward
-// and stage-arena size, with the arena, grids and key splitting, are net_pass.h's, shared with fasttd3.hip, reppo.hip and
-// mpo.hip; this file keeps the descriptor check, the losses and the update's streams.  CPU twin: oracle/fastsac.py,
+// and stage-arena size, with the arena, grids and key splitting, are net_pass.h's, shared with fasttd3.hip, reppo.hip, mpo.hip
+// and espo.hip; this file keeps the descriptor check, the losses and the update's streams.  CPU twin: oracle/fastsac.py,
 // pinned by outputs of the reference's own modules and closures (tests/golden/reference_fastsac.npz).
 //
 // Noise: the reference draws with torch's CUDA generator (Normal.rsample), which no other implementation reproduces; the
@@ -454,14 +454,13 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
                                         hp->v_min, hp->v_max, hp->clipped_double_q, d1, d2, c51o, stream);
   if (rc) return rc;
   {
-    GradScaleScope gscope(ctx, bx_grad_scale(B));   // d logits ~ 1 / B
-    FsDefer defer(ctx);
-    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, true));
+    BwdPass bwd(ctx, B);   // d logits ~ 1 / B
+    rc = bwd.begin(2 * chain_stage_floats(ctx, LQ, B, true));
     if (!rc) rc = fk.fork();
     if (!rc) rc = chain_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
     if (!rc) rc = chain_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
     if (!rc) rc = fk.join();
-    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
   // ---- entropy coefficient (uses alpha BEFORE its own step inside the C51 target: the launch order above), then AdamW + Polyak
@@ -470,11 +469,7 @@ int rlx_fastsac_critic_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, con
   hipLaunchKernelGGL(k_fs_alpha_step, dim3(1), dim3(256), 0, st, (const float*)lpn, B, log_alpha, am, av, (const float*)c51o,
                      hp->target_entropy, hp->lr_alpha, hp->weight_decay, hp->adam_b1, hp->adam_b2, hp->adam_eps, bc1, bc2, metrics_out);
   RLX_LAUNCH_CHECK();
-  const int nsq = launch_sumsq_partials(gq, 2 * nq, sq, st);
-  RLX_LAUNCH_CHECK();
-  rc = launch_clip_adam(qparams, gq, qm, qv, 2 * nq, sq, nsq, step, hp->lr_critic, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
-                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 5, st, nullptr, nullptr, qtarget, hp->tau, hp->weight_decay,
-                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  rc = torch_clip_adam(qparams, gq, qm, qv, 2 * nq, sq, step, hp->lr_critic, *hp, metrics_out + 5, st, qtarget, hp->tau, hp->weight_decay);
   if (rc) return rc;
   *opt_count_io += 1;
   return RLX_OK;
@@ -542,9 +537,8 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
                      part, B, NA, hp->v_min, hp->v_max, hp->clipped_double_q, inv_b);
   RLX_LAUNCH_CHECK();
   {
-    GradScaleScope gscope(ctx, bx_grad_scale(B));
-    FsDefer defer(ctx);
-    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
+    BwdPass bwd(ctx, B);
+    rc = bwd.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
     if (rc) return rc;
     // the critics' input gradients (no parameter gradients; one critic per stream), then the policy's backward
     rc = fk.fork();
@@ -559,17 +553,12 @@ int rlx_fastsac_policy_update_f32(rlx_ctx* ctx, const rlx_lnmlp_desc* pdesc, flo
                        (int64_t)0, B);
     RLX_LAUNCH_CHECK();
     rc = chain_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
-    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_fs_policy_metrics, dim3(1), dim3(256), 0, st, (const float*)part, nblk, log_alpha, inv_b, metrics_out);
   RLX_LAUNCH_CHECK();
-  const int64_t step = *opt_count_io + 1;
-  const int nsq = launch_sumsq_partials(gp, np_, sq, st);
-  RLX_LAUNCH_CHECK();
-  rc = launch_clip_adam(pparams, gp, pm, pv, np_, sq, nsq, step, hp->lr_policy, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
-                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 2, st, nullptr, nullptr, nullptr, 0.f, hp->weight_decay,
-                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, *opt_count_io + 1, hp->lr_policy, *hp, metrics_out + 2, st, nullptr, 0.f, hp->weight_decay);
   if (rc) return rc;
   *opt_count_io += 1;
   return RLX_OK;

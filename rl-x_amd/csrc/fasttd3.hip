@@ -7,9 +7,9 @@
 // 64 up to 1024 (td3_check: the PPO / SAC check mlp_check_desc stays as it is).  A network is net_pass.h's Chain of plain blocks:
 // the library's GEMM stages with the fused bias + ReLU epilogue (launch_gemm_fwd) and the ReLU' input-gradient epilogue
 // (stage_dx), the split-operand engine for passes of >= 4096 rows (trunk_images), stage_dw for the weight gradients; the heads
-// are dense_head.hip's k_fs_head_* kernels (the input-gradient one with its ReLU' mask) or, where a tanh follows, the fused head
-// kernel k_td3_head_act below.  Carve, forward, backward, stage-arena size, grids and key splitting: net_pass.h, shared with
-// fastsac.hip, reppo.hip and mpo.hip.
+// are dense_head.hip's k_fs_head_* kernels (the input-gradient one with the ReLU' epilogue chain_bwd gives a plain last block) or,
+// where a tanh follows, the fused head kernel k_td3_head_act below.  Carve, forward, backward, stage-arena size, grids and key
+// splitting: net_pass.h, shared with fastsac.hip, reppo.hip, mpo.hip and espo.hip.
 //
 // fp16 window: the split-operand engine holds |weight| < 1023, |activation| < 4094, per-sample gradient < 8190.
 // ReLU activations are not bounded by a LayerNorm; a value outside the window turns the affected products into inf / NaN, the
@@ -37,11 +37,6 @@ static int td3_check(const rlx_mlp_desc& d) {
 
 static Chain td3_layout(const rlx_mlp_desc& d) {   // the flat layout of rlx_mlp_desc without LayerNorm and log-std
   return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_NONE, RLX_ACT_RELU);
-}
-// chain_bwd with the head's input gradient times ReLU'(H_last): H_l holds the ReLU output, each dZ_l overwrites it
-static int td3_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, const float* d_head,
-                   float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
-  return chain_bwd(ctx, L, p, x, ldx, b, d_head, grads, dx, lddx, M, st, dx_c0, dx_nc, /*relu_mask*/ true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
@@ -319,23 +314,18 @@ int rlx_fasttd3_critic_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const
                                         hp->v_min, hp->v_max, hp->clipped_double_q, d1, d2, metrics_out, stream);
   if (rc) return rc;
   {
-    GradScaleScope gscope(ctx, bx_grad_scale(B));   // d logits ~ 1 / B
-    FsDefer defer(ctx);
-    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, true));
+    BwdPass bwd(ctx, B);   // d logits ~ 1 / B
+    rc = bwd.begin(2 * chain_stage_floats(ctx, LQ, B, true));
     if (!rc) rc = fk.fork();
-    if (!rc) rc = td3_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
-    if (!rc) rc = td3_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams + nq, xc, ldc, b2, d2, gq + nq, nullptr, 0, B, fk.side());
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams, xc, ldc, b1, d1, gq, nullptr, 0, B, fk.main());
     if (!rc) rc = fk.join();
-    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
   // ---- one AdamW over both critics (fasttd3.py:89), clip_grad_norm_ semantics, then the Polyak step (:316-320) in the same launch
-  const int64_t step = *opt_count_io + 1;
-  const int nsq = launch_sumsq_partials(gq, 2 * nq, sq, st);
-  RLX_LAUNCH_CHECK();
-  rc = launch_clip_adam(qparams, gq, qm, qv, 2 * nq, sq, nsq, step, hp->lr_critic, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
-                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 3, st, nullptr, nullptr, qtarget, hp->tau, hp->weight_decay,
-                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  rc = torch_clip_adam(qparams, gq, qm, qv, 2 * nq, sq, *opt_count_io + 1, hp->lr_critic, *hp, metrics_out + 3, st, qtarget, hp->tau,
+                       hp->weight_decay);
   if (rc) return rc;
   *opt_count_io += 1;
   return RLX_OK;
@@ -398,31 +388,25 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
                      hp->v_max, hp->clipped_double_q, inv_b);
   RLX_LAUNCH_CHECK();
   {
-    GradScaleScope gscope(ctx, bx_grad_scale(B));
-    FsDefer defer(ctx);
-    rc = defer.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
+    BwdPass bwd(ctx, B);
+    rc = bwd.begin(2 * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
     if (rc) return rc;
     // the critics' input gradients on the action columns (no parameter gradients; one critic per stream), then the policy's backward
     rc = fk.fork();
-    if (!rc) rc = td3_bwd(ctx, LQ, qparams + nq, xp, ldc, b2, d2, nullptr, dx2, ldc, B, fk.side(), Oc, A);
-    if (!rc) rc = td3_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams + nq, xp, ldc, b2, d2, nullptr, dx2, ldc, B, fk.side(), Oc, A);
+    if (!rc) rc = chain_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
     if (!rc) rc = fk.join();
     if (rc) return rc;
     hipLaunchKernelGGL(k_td3_tanh_bwd, dim3(elem_grid(B * A)), dim3(256), 0, st, (const float*)xp, (const float*)dx1, (const float*)dx2, ldc, Oc,
                        dhead, B, A);
     RLX_LAUNCH_CHECK();
-    rc = td3_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
-    if (!rc) rc = stage_reduce_flush(ctx, nullptr, nullptr, st);
+    rc = chain_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
+    if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_td3_policy_loss, dim3(1), dim3(256), 0, st, (const float*)part, nblk, inv_b, metrics_out);
   RLX_LAUNCH_CHECK();
-  const int64_t step = *opt_count_io + 1;
-  const int nsq = launch_sumsq_partials(gp, np_, sq, st);
-  RLX_LAUNCH_CHECK();
-  rc = launch_clip_adam(pparams, gp, pm, pv, np_, sq, nsq, step, hp->lr_policy, hp->max_grad_norm > 0.f ? hp->max_grad_norm : -1.f,
-                        hp->adam_b1, hp->adam_b2, hp->adam_eps, metrics_out + 1, st, nullptr, nullptr, nullptr, 0.f, hp->weight_decay,
-                        /*clip_mode: torch clip_grad_norm_*/ 1);
+  rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, *opt_count_io + 1, hp->lr_policy, *hp, metrics_out + 1, st, nullptr, 0.f, hp->weight_decay);
   if (rc) return rc;
   *opt_count_io += 1;
   return RLX_OK;

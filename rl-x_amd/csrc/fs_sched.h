@@ -1,8 +1,10 @@
 // fs_sched.h -- the stream fork / join of the distributional off-policy updates (fastsac.hip, fasttd3.hip: a critic pair whose two
-// halves go to two streams) and the deferred parameter-gradient reduction (those two, reppo.hip and mpo.hip: the backward passes
-// of a step gather all their slab partials into one reduction launch).  Included through net_pass.h.
+// halves go to two streams; espo.hip: the critic step of an epoch) and the deferred parameter-gradient reduction (those three,
+// reppo.hip and mpo.hip: the backward passes of a step gather all their slab partials into one reduction launch).  Nothing here
+// touches the arithmetic; the epilogue rule of the input gradients is net_pass.h's, which includes this file.
 #pragma once
 #include "mlp.h"
+#include "gemm_bx.h"
 
 namespace rlx {
 
@@ -57,7 +59,13 @@ struct FsDefer {
     c->defer = &d;
     return RLX_OK;
   }
+  int finish(hipStream_t st) { return stage_reduce_flush(c, nullptr, nullptr, st); }   // the one reduction launch
   ~FsDefer() { if (c->defer == &d) c->defer = nullptr; }
+};
+// FsDefer plus the split-operand gradient scale of a pass over `rows` rows, for the scope's lifetime
+struct BwdPass : FsDefer {
+  GradScaleScope gscope;
+  BwdPass(rlx_ctx* ctx, int64_t rows) : FsDefer(ctx), gscope(ctx, bx_grad_scale(rows)) {}
 };
 
 }  // namespace rlx

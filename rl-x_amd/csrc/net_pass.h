@@ -1,8 +1,11 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip and mpo.hip on the host side: the launchers of
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip and espo.hip on the host side: the launchers of
 // dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
-// of blocks, the streams, and what differs at the head (a ReLU mask, MPO's ELU copy) or in the graph (REPPO's critic).
+// of blocks, the streams, and what differs in the graph (REPPO's critic).
+// The epilogue rule of every input gradient (block_dx, head_bwd): the buffer it writes holds the output H of the block below; a
+// plain block (NORM_NONE) with an activation gets act'(H) there, in place, so the buffer then holds that block's dZ; a normed
+// block (or no block) gets none -- its norm backward takes dH.
 #pragma once
 #include "mlp.h"
 #include "gemm_bx.h"
@@ -14,9 +17,9 @@ namespace rlx {
 // out[M, N] = H[M, K] @ W[K, N] + b (any K and N: FastSAC's widths end at 768, FastTD3's at 1024)
 int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st);
 // gW != NULL: weight / bias gradients from H_dH = H (slab partials into the stage arena: head_stage_floats); then dH over H_dH,
-// times ReLU'(H) with relu_mask
+// times act'(H) (act: RLX_ACT_NONE, RELU, TANH or ELU; anything else is RLX_EUNSUP)
 int fs_head_bwd(rlx_ctx* ctx, float* H_dH, const float* W, const float* d, float* gW, float* gb, int64_t M, int K, int N, hipStream_t st,
-                bool relu_mask = false);
+                int act);
 // out[M, ld] = [obs (Oc columns) | act (A columns; zeros when NULL) | zero padding]
 int fs_concat(const float* obs, int Oc, const float* act, int A, float* out, int ld, int64_t M, hipStream_t st);
 // out[i] = normal(bits(key, i of n))
@@ -97,6 +100,13 @@ static inline int arena_carve(rlx_ctx* ctx, ScratchSlot slot, Carve&& carve, siz
 }
 
 struct BxReleaseAll { rlx_ctx* c; ~BxReleaseAll() { bx_release_all(c); } };   // drops the registered weight images at scope exit
+// stage_dw on the exact engine for the scope's lifetime (bx_dw_usable reads ctx->gemm_bx)
+struct ExactDwScope {
+  rlx_ctx* c;
+  bool was;
+  explicit ExactDwScope(rlx_ctx* ctx) : c(ctx), was(ctx->gemm_bx) { ctx->gemm_bx = false; }
+  ~ExactDwScope() { c->gemm_bx = was; }
+};
 
 // key, *subkeys = split(key, 1 + nsub): advances key_io, sub receives 2 nsub words
 static inline void next_key(uint32_t key_io[2], uint32_t* sub, int nsub, int scheme) {
@@ -128,6 +138,16 @@ static inline int norm_bwd_reduce(rlx_ctx* ctx, const float* part, int grid, int
   tab.seg[tab.n++] = ReduceSeg{part, g_scale, (int64_t)D, stride, grid, 0, 1.f, 0.f, 1};
   if (g_bias) tab.seg[tab.n++] = ReduceSeg{part + D, g_bias, (int64_t)D, stride, grid, 0, 1.f, 0.f, 1};
   return stage_reduce(ctx, tab, nullptr, nullptr, st);
+}
+// Sum of squares of the gradients, then clip + Adam the torch way (clip_mode 1: torch.nn.utils.clip_grad_norm_; hp.max_grad_norm
+// <= 0: no clipping) with hp's Adam constants; sq: REDUCE_MAX_BLOCKS floats; the gradient norm goes to *norm_out
+template <class HP>
+static inline int torch_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, float* sq, int64_t step, float lr, const HP& hp,
+                                  float* norm_out, hipStream_t st, float* polyak_target = nullptr, float tau = 0.f, float weight_decay = 0.f) {
+  const int nsq = launch_sumsq_partials(g, n, sq, st);
+  RLX_LAUNCH_CHECK();
+  return launch_clip_adam(p, g, m, v, n, sq, nsq, step, lr, hp.max_grad_norm > 0.f ? hp.max_grad_norm : -1.f, hp.adam_b1, hp.adam_b2,
+                          hp.adam_eps, norm_out, st, nullptr, nullptr, polyak_target, tau, weight_decay, 1);
 }
 // Input gradient of a first layer W[Kd, N] from dZ [M, N] into dx (row stride lddx): with nc > 0 only the columns [c0, c0 + nc)
 // (a policy loss wants dQ/da) through the column-restricted product where it takes the shape, else the whole GEMM.
@@ -163,12 +183,20 @@ static inline size_t block_stage_floats(const rlx_ctx* ctx, const Block& o, int6
   return (o.norm != NORM_NONE ? a64((size_t)bwd_rows_grid(ctx, M) * norm_part_width(o)) : 0) +
          (grads ? a64(stage_dw_floats(ctx, M, o.in, o.out)) : 0);
 }
-// input gradient of block o from its dZ into `out` [M, in].  prev: the block whose output `out` holds -- a plain one gets its act'
-// in the epilogue (out becomes its dZ), a normed one (or NULL) does not
+// the epilogue of an input gradient written over the output of block `prev` (the rule in the header): a plain block's activation
+static inline int dx_epilogue(const Block* prev) { return prev && prev->norm == NORM_NONE ? prev->act : RLX_ACT_NONE; }
+// input gradient of block o from its dZ into `out` [M, in], which holds the output of block prev (or NULL)
 static inline int block_dx(rlx_ctx* ctx, const Block& o, const Block* prev, const float* p, const float* dZ, float* out, int64_t M,
                            hipStream_t st) {
-  const bool ep = prev && prev->norm == NORM_NONE && prev->act != RLX_ACT_NONE;
-  return stage_dx(ctx, dZ, p + o.W, out, M, o.out, o.in, o.in, ep ? prev->act : RLX_ACT_NONE, ep ? 1 : 0, st, nullptr);
+  const int ep = dx_epilogue(prev);
+  return stage_dx(ctx, dZ, p + o.W, out, M, o.out, o.in, o.in, ep, ep != RLX_ACT_NONE, st, nullptr);
+}
+// the head step of a block stack from d_head [M, head.out]: the head's parameter gradients (grads != NULL: flat layout, slabs into
+// the stage arena), then its input gradient over H [M, head.in], which holds the output of block `below` (or NULL)
+static inline int head_bwd(rlx_ctx* ctx, const Block& head, const Block* below, const float* p, float* H, const float* d_head, float* grads,
+                           int64_t M, hipStream_t st) {
+  return fs_head_bwd(ctx, H, p + head.W, d_head, grads ? grads + head.W : nullptr, grads ? grads + head.b : nullptr, M, head.in, head.out, st,
+                     dx_epilogue(below));
 }
 
 // ---- a chain of blocks and a dense head
@@ -203,29 +231,19 @@ static inline int chain_fwd(rlx_ctx* ctx, const Chain& L, const float* p, const 
   if (!head_out) return RLX_OK;
   return fs_head_fwd(b.H[L.n_hidden - 1], p + L.head.W, p + L.head.b, head_out, M, L.head.in, L.head.out, st);
 }
-// Trunk backward from `top` = dH / dZ of the last block (b.H[last], or a copy of it); per block from the last: [norm backward,
-// norm reduce], dW, dX.  dx != NULL: the input gradient (row stride lddx; the columns [dx_c0, dx_c0 + dx_nc) only when dx_nc > 0)
-static inline int chain_trunk_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, float* top,
-                                  float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
-  for (int l = L.n_hidden - 1; l >= 0; --l) {
-    const Block& o = L.layer[l];
-    float* d = l == L.n_hidden - 1 ? top : b.H[l];
-    int rc = block_bwd(ctx, o, p, l ? b.H[l - 1] : x, l ? o.in : ldx, b.Z[l], d, grads, M, st);
-    if (rc) return rc;
-    if (l > 0) rc = block_dx(ctx, o, &L.layer[l - 1], p, d, b.H[l - 1], M, st);
-    else if (dx) rc = first_layer_dx(ctx, d, p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
-    if (rc) return rc;
-  }
-  return RLX_OK;
-}
-// backward from d_head [M, head.out]: the head (with the ReLU' mask of a ReLU trunk), then the trunk.  The buffers are consumed.
+// backward from d_head [M, head.out]: the head step, then per block from the last: [norm backward, norm reduce], dW, dX.  The
+// buffers are consumed.  dx != NULL: the input gradient (row stride lddx; the columns [dx_c0, dx_c0 + dx_nc) only when dx_nc > 0)
 static inline int chain_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, const float* d_head,
-                            float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0,
-                            bool relu_mask = false) {
-  float* top = b.H[L.n_hidden - 1];
-  const int rc = fs_head_bwd(ctx, top, p + L.head.W, d_head, grads ? grads + L.head.W : nullptr, grads ? grads + L.head.b : nullptr, M,
-                             L.head.in, L.head.out, st, relu_mask);
-  return rc ? rc : chain_trunk_bwd(ctx, L, p, x, ldx, b, top, grads, dx, lddx, M, st, dx_c0, dx_nc);
+                            float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
+  int rc = head_bwd(ctx, L.head, &L.layer[L.n_hidden - 1], p, b.H[L.n_hidden - 1], d_head, grads, M, st);
+  for (int l = L.n_hidden - 1; l >= 0 && !rc; --l) {
+    const Block& o = L.layer[l];
+    rc = block_bwd(ctx, o, p, l ? b.H[l - 1] : x, l ? o.in : ldx, b.Z[l], b.H[l], grads, M, st);
+    if (rc) return rc;
+    if (l > 0) rc = block_dx(ctx, o, &L.layer[l - 1], p, b.H[l], b.H[l - 1], M, st);
+    else if (dx) rc = first_layer_dx(ctx, b.H[l], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);
+  }
+  return rc;
 }
 // floats one backward of the chain takes from the stage arena: fs_head_bwd's slabs and every block's
 static inline size_t chain_stage_floats(const rlx_ctx* ctx, const Chain& L, int64_t M, bool grads) {

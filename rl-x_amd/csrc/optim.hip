@@ -109,25 +109,6 @@ void adam_schedule_entry(float* out3, int64_t step, float lr, float b1, float b2
   out3[2] = (float)(1.0 - pow((double)b2, (double)step));
 }
 
-// sched_dev (optional, DEVICE {lr, 1 - b1^step, 1 - b2^step}): the per-update values come from a device table instead of the
-// launch arguments (the SAC update keeps them next to its key: one small upload per call)
-static AdamJob make_adam_job(float* params, const float* grads, float* m, float* v, int64_t n, const float* partials, int n_partials,
-                             int64_t step, float lr, float max_norm, float b1, float b2, float* norm_out, const float* sched_dev,
-                             const BxEmit* emit, float* polyak_target, float tau, float weight_decay, int clip_mode) {
-  AdamJob J{params, grads, m, v, n, partials, n_partials, max_norm, norm_out, sched_dev, polyak_target, tau, weight_decay};
-  J.clip_mode = clip_mode;
-  J.lr = lr;
-  J.bc1 = (float)(1.0 - pow((double)b1, (double)step));
-  J.bc2 = (float)(1.0 - pow((double)b2, (double)step));
-  BxEmit em;
-  em.n = 0;
-  if (emit) em = *emit;
-  BxEmit none;
-  none.n = 0;
-  adam_job_plan(J, em, none);
-  return J;
-}
-
 int launch_clip_adam(float* params, const float* grads, float* m, float* v, int64_t n, const float* sumsq_partials,
                      int n_partials, int64_t step, float lr, float max_norm, float b1, float b2, float eps,
                      float* norm_out, hipStream_t st, const float* sched_dev, const BxEmit* emit, float* polyak_target,

@@ -344,7 +344,7 @@ def check_against_twin(c, r, st, eps, step, label=""):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the cases
-NAMES = ["narrow", "wide", "act64", "split3", "split_ragged", "many_rows"]
+NAMES = ["narrow", "wide", "act64", "split3", "split_ragged", "many_rows", "head320"]
 
 
 def shape_case(name, num_cus=256):
@@ -356,6 +356,7 @@ def shape_case(name, num_cus=256):
         "split3": lambda: Case(274, 48, 12, (256, 128, 64), (256, 128, 64), 51, 4099, clipped=False),
         "split_ragged": lambda: Case(275, 45, 17, (256, 128, 64), (256, 128, 64), 101, 4099),
         "many_rows": lambda: Case(276, 64, 64, (64,), (64,), 21, 64 * num_cus + 37, clipped=False),
+        "head320": lambda: Case(277, 1, 1, (64, 320), (64, 320), 21, 13),
     }[name]()
     if name == "narrow":        # the one row: not done, a reward past v_max -- the projected target sits on the top atom
         c.batch[3][:] = 8.5

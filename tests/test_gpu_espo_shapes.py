@@ -1,6 +1,8 @@
 """GPU: rlx_espo_update_f32 across the shape envelope it accepts, against the float64 twin (tests/espo_twin.py) at the bars of
 tests/test_gpu_espo.py: action dim 1 and 64, hidden 64 / 256 / 512, ragged observation widths 11 and 17 (with and without index
 sets), minibatches of 2, 63, 65, 1000 and 4096 rows (below / above one wave, one row per thread of the loss workgroup, all four),
+hidden 320 at 13 rows (the head's input gradient, with its tanh' epilogue, gives a workgroup 8 rows and strides the width by 256
+threads: a last workgroup of 5 rows and a second stride with 64 of 256 threads active, at observation and action width 1),
 both ratio_delta operators, B = mb, and per case a SECOND call from the twin's state after the first (non-zero moments, the
 optimizer count carried over).  Each case runs three epochs; where the twin's ratio_delta grows from epoch 0 to epoch 1 the
 threshold is put between them, so the stop is exercised too.  The inputs satisfy the fixture generator's two margin conditions,
@@ -31,6 +33,7 @@ CASES = {
     "index_sets_7_and_10_of_11": (18, 11, 3, 64, 300, 63, "median", 7, 10),
     "index_sets_17_to_5_and_17": (19, 17, 4, 256, 300, 65, "mean", 5, 17, 3e-4),
     "mb1001_median_A64": (20, 17, 64, 64, 1200, 1001, "median", None, None, 3e-4),
+    "H320_mb13": (21, 1, 1, 320, 40, 13, "mean", None, None, 3e-4),
 }
 _TWIN = {}
 

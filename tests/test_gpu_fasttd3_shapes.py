@@ -26,6 +26,10 @@ test_shape_case_reaches_its_paths from a mirror of the host selection code (test
 | many_rows    | 64 / 64 / 64 | 64 | (64)           | (64)           | 21  | 64 num_cus + 37 | elem_grid's cap in k_td3_head_act and          |
 |              |              |    |                |                |     |                 | k_td3_tanh_bwd (B A > 2^20), fs_concat's cap,  |
 |              |              |    |                |                |     |                 | > 256 loss partials; mean of two               |
+| head320      | 1 / 1 / 1    | 1  | (64, 320)      | (64, 320)      | 21  | 13              | the heads' input gradient with its ReLU'       |
+|              |              |    |                |                |     |                 | epilogue (8 rows per workgroup, the width in   |
+|              |              |    |                |                |     |                 | strides of 256): a last workgroup of 5 rows, a |
+|              |              |    |                |                |     |                 | second stride with 64 threads active; clipped  |
 
 The profiler confirms the engine of every trunk GEMM it sees (net_paths.expected_engines), and everything runs on engine 0 with the
 split engine switched off in the context.  Also: acting at A 1 and at A 64 with N A past elem_grid's cap, against the twin and over
@@ -83,6 +87,7 @@ def test_shape_case_reaches_its_paths(name):
         "split_ragged": lambda: B >= 4096 and Op % 4 != 0 and (Oc + A) % 4 != 0 and cu[:2] == (10, 14) and pu[:2] == (6, 12) and dxc and
         npth.bx_dw_usable(True, B, Oc + A, ldc, c.ch[0]) and npth.bx_dw_usable(True, B, Op, ldp, c.ph[0]) and c.clipped,
         "many_rows": lambda: npth.elem_grid(B * A)[1] and npth.elem_grid(B * ldc)[1] and npth.div_up(B, 4) > 256 and B >= 4096 and dxc and A == 64,
+        "head320": lambda: c.ph[-1] == c.ch[-1] == 320 and 256 < 320 < 512 and B > 8 and B % 8 == 5 and Op == Oc == A == 1 and c.clipped,
     }[name]
     assert want(), (name, heads, dxc, cu[:2], pu[:2])
     assert name == "many_rows" or B % 4 != 0 or B == 1
