@@ -181,6 +181,11 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   wave computes the LayerNorm mean and 1 / std of a tile's 32 rows once (one row per lane) and the per-row loops load them,
  *   instead of every lane recomputing both for each of its 16 rows at every use.  The same operations in the same order:
  *   bit-identical results (tests/test_gpu_ln_row_once.py); 0 is the earlier form.
+ * Round 9: "l1_stats_handover" (1 default; 0 or 1, anything else is RLX_EINVAL): in the PPO minibatch pass k_l12fwd leaves the
+ *   LayerNorm mean and 1 / std of every row in a [2][M] array next to h1 and the fused first-layer backward of the same pass loads
+ *   them instead of rebuilding them from its recomputed z1.  Active only with "ln_row_once" = 1 on the split-operand engine
+ *   ("gemm_bx" = 1) where the pass's forward was k_l12fwd -- there both kernels run the same code on the same rows: bit-identical
+ *   results (tests/test_gpu_l1_stats_handover.py); everywhere else, and with 0, the earlier kernels run unchanged.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,

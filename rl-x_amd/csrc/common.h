@@ -131,6 +131,17 @@ struct rlx_ctx {
                                           // consumers' MFMA time); off by default
   float* l12_stats = nullptr;             // set by the caller of a minibatch pass that wants that: [2][M] scratch for the statistics
   bool l12_ran = false;                   // mlp_trunk_fwd took the k_l12fwd path with the statistics (h1 was not stored)
+  int l1_stats_handover = 1;              // PPO minibatch pass: 1 k_l12fwd always leaves the rows' LayerNorm mean | 1 / std ([2][M], next to h1) and the fused
+                                          // first-layer backward of the same pass loads them (k_dx_l1bwd_stats) instead of rebuilding them from its
+                                          // recomputed z1 -- one workgroup barrier and the sum / fold code less per row tile; 0 the earlier kernels.
+                                          // Active only where both kernels are the split-operand LayerNorm forms with ln_row_once = 1 and this pass's
+                                          // forward was k_l12fwd: there the two computations are the same code, so the results are bit-identical.
+                                          // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 65.36 vs 67.12 ms per iteration at 32768-row
+                                          // minibatches (block-to-block sd 0.15 / 0.17), 107.10 vs 108.91 at 4096 rows
+  float* l1_hand_req = nullptr;           // set by a minibatch pass that wants the handover: [2][M] scratch k_l12fwd fills when dw_recompute does not
+                                          // already make it write l12_stats (then that array serves both readers)
+  const float* l1_hand[2] = {nullptr, nullptr};   // set by launch_l12fwd<ROW1>: the arrays it filled (twin: [1] the second network's); cleared with
+                                          // l12_stats by the pass's scope, so a backward never reads what its own forward did not write
   bool dw_merge = true;                   // weight gradients of the two upper layers in one two-job launch when the tail kernel has produced both dZ (bx_launch_dw2)
   void* dbg_stamps = nullptr;             // test / tuning hook: device array of clock64() stamps written by instrumented kernels (fwd2h.hip)
   bool fwd2h = true;                      // 256-256 nets (SAC): the whole forward incl. the head in one launch per 32-row tile (fwd2h.hip)

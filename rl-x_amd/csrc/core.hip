@@ -246,6 +246,11 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
     ctx->ln_row_once = value;
     return RLX_OK;
   }
+  if (std::string(name) == "l1_stats_handover") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: l1_stats_handover is 0 or 1");
+    ctx->l1_stats_handover = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "bx_force_mi") { ctx->bx_force_mi = value; return RLX_OK; }
   if (std::string(name) == "adam_emit") { ctx->adam_emit = value != 0; return RLX_OK; }
   if (std::string(name) == "bx_debug") { ctx->bx_debug = value; return RLX_OK; }

@@ -91,7 +91,10 @@ struct L1FusedArgs {
   const void* W1x;     // BX kernels: fragment-ordered split image of B(k = obs index, j = h1 column), K padded to 32 (two 16-k blocks)
   const uint32_t* xmax;  // BX kernels, optional: DEVICE bit pattern of max |X| -> power-of-two scale of the X planes (common.h: x_scale_from_max); NULL: X_ASCALE
   unsigned long long* stamps;   // tuning aid (rlx_dbg_set_stamps, -DRLX_LF_STAMPS=1): clock64() of thread 0 of workgroup 0 at the phase boundaries of its first two tiles
+  const float* stats;  // HAND kernels: the rows' LayerNorm mean | 1 / std as this pass's k_l12fwd left them (L12Args::stats: [2][M])
 };
+constexpr int LF_RED = 2048;                                  // floats of the reduction region: [2 phases][2 stats][NW][32] partials + [2 phases][NW][2][32] wave copies
+constexpr int LF_RED_HAND = 2 * 64 + 2 * 8 * 32 + 8 * 64;     // HAND: [2 buffers][2][32] handed-over statistics + the second phase's partials and wave copies
 
 // BX: LDS image of the dZ2 row tile as two fp16 planes (gemm_bx.h), [32 rows][N2 k] with 2 * N2 bytes per row; the 16-byte k-slots of a
 // row are XOR-swizzled with the low four row bits (N2 % 128 == 0), which makes the 16 rows of every ds_read_b128 service
@@ -134,10 +137,22 @@ __device__ __forceinline__ void lf_x_stage(char* __restrict__ img, int r, int k,
 // TWIN: grid.y == 2, blockIdx.y == 1 works on the argument set a2 (the second of two equally shaped networks on the same rows)
 // ROW1 (option ln_row_once, LN only): the row statistics are finished once per wave and row (ln_row_stats) and the per-row loops load
 // mean and 1 / std; false: every lane recomputes them for each of its 16 rows in both loops (the earlier form, kept for the A/B)
-template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN = false, bool ROW1 = false>
-__global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1FusedArgs a2) {
+// HAND (option l1_stats_handover, ROW1 + BX only; the entry point is k_dx_l1bwd_stats): mean and 1 / std of the tile's rows are NOT
+// rebuilt from the recomputed z1 -- no partial sums, no LDS partials, no barrier, no fold, no ln_row_stats -- but loaded from the
+// [2][M] array in which k_l12fwd<ROW1> of the SAME pass left them (a.stats).  That kernel formed them from the same z1 product with the
+// same code (partial sums, half_sum4, fixed-order fold, ln_row_stats), so the loaded words are the words this kernel would compute:
+// bit-identical results.  64 threads fetch the NEXT tile's 64 values with its dZ2 / X rows (stage_load) and put them into a
+// per-buffer [2][32] LDS slot (stage_store) that the tile-top barrier publishes with the images; every wave reads its rows' float4s
+// from that slot where the other forms read the wave's own copy.  Rows past M (a ragged last tile; the forward does not write them)
+// take the fixed pair mean 0 | 1 / std 1: their dZ2 rows are zero, so dH1 = 0 and every term they add to dgamma, dbeta, db1, the
+// row sums and the dW1 operand is (+-0) x (a finite value) = +-0 under ANY finite pair, and x + (+-0) leaves every accumulator bit
+// (accumulators start at +0 and never become -0); the dW1 scale ignores such rows (rs = 0) as before.
+// The host selects this form only where this pass's forward was k_l12fwd<ROW1> with a statistics array (launch_l1fused).
+template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN, bool ROW1, bool HAND>
+__device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2) {
   if (TWIN && blockIdx.y) a = a2;
   static_assert(!ROW1 || LN, "ROW1 is a form of the LayerNorm statistics");
+  static_assert(!HAND || (ROW1 && BX), "HAND takes the statistics of k_l12fwd<ROW1>: the split-operand LayerNorm form only");
   constexpr int H1 = 32 * NT * NW;
   constexpr int NTHREADS = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
   const int a_img = BX ? X_NP * LF_ROWS * a.N2 / 2 : LF_ROWS * (a.N2 + 4);   // floats per buffer
   float* Xs0 = As0 + nbuf * a_img;                    // nbuf x [32][33]   X tile (cols >= O zero); BX: nbuf x LF_XIMG bytes of planes
   const int x_img = BX ? LF_XIMG / 4 : LF_ROWS * LF_XS;   // floats per buffer
-  float* red = Xs0 + nbuf * x_img;                    // [2 phases][2 stats][NW][32]
+  float* red = Xs0 + nbuf * x_img;                    // [2 phases][2 stats][NW][32] (LF_RED floats); HAND: [2 buffers][2][32] statistics first (LF_RED_HAND)
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
   const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
   const int O = a.O, N2 = a.N2;
@@ -194,34 +209,52 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
   constexpr int SA_N = LF_ROWS * (LFP_N2 / 4) / NTHREADS, SX_N = LF_ROWS * 32 / NTHREADS;
   lf_v4 sa[SA_N];
   float sx[SX_N];
+  float sh = 0.f;                              // HAND, threads 0-63: mean (0-31) / 1 / std (32-63) of row (t & 31) of the staged tile
+  auto hand_load = [&](int64_t rr, int tt) -> float {  // rows past M: the fixed pair 0 | 1 (see the head comment)
+    const float* sb = a.stats + rr;            // (uniform base + a 32-bit lane offset: the host takes this form below 2^30 rows only)
+    const uint32_t off = (uint32_t)(tt >> 5) * (uint32_t)a.M + (uint32_t)(tt & 31);
+    return rr + (tt & 31) < a.M ? sb[off] : (tt < 32 ? 0.f : 1.f);
+  };
+  // HAND: the staging index math starts from a copy of t that hipcc cannot see through.  Hoisted out of the tile loop, the lanes' row
+  // pointers and LDS addresses of the stage loads and stores are loop invariants that it spills (20 registers, where the other forms
+  // spill 7); recomputed per tile they are a few VALU instructions and the kernel spills nothing.
+  auto t_opaque = [&]() -> int {
+    int tt = t;
+    if (HAND) asm volatile("" : "+v"(tt));
+    return tt;
+  };
   auto stage_load = [&](int64_t tl) {          // dbuf only (N2 == LFP_N2)
     const int64_t rr = tl * LF_ROWS;
+    const int ts = t_opaque();
+    if (HAND && ts < 64) sh = hand_load(rr, ts);
 #pragma unroll
     for (int c = 0; c < SA_N; ++c) {
-      const int i = t + c * NTHREADS, r = i / (LFP_N2 / 4), c4 = (i % (LFP_N2 / 4)) * 4;
+      const int i = ts + c * NTHREADS, r = i / (LFP_N2 / 4), c4 = (i % (LFP_N2 / 4)) * 4;
       sa[c] = (rr + r < a.M) ? *reinterpret_cast<const lf_v4*>(a.dZ2 + (rr + r) * LFP_N2 + c4) : lf_v4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int c = 0; c < SX_N; ++c) {
-      const int i = t + c * NTHREADS, r = i >> 5, k = i & 31;
+      const int i = ts + c * NTHREADS, r = i >> 5, k = i & 31;
       sx[c] = (k < O && rr + r < a.M) ? a.X[(rr + r) * O + k] : 0.f;
     }
   };
   auto stage_store = [&](int b) {
     float* Ad = As0 + b * a_img;
     float* Xd = Xs0 + b * x_img;
+    const int ts = t_opaque();
 #pragma unroll
     for (int c = 0; c < SA_N; ++c) {
-      const int i = t + c * NTHREADS, r = i / (LFP_N2 / 4), c4 = (i % (LFP_N2 / 4)) * 4;
+      const int i = ts + c * NTHREADS, r = i / (LFP_N2 / 4), c4 = (i % (LFP_N2 / 4)) * 4;
       if (BX) lf_bx_stage4(reinterpret_cast<char*>(Ad), r, c4, sa[c], LFP_N2, a.gs);
       else *reinterpret_cast<lf_v4*>(Ad + r * (LFP_N2 + 4) + c4) = sa[c];
     }
 #pragma unroll
     for (int c = 0; c < SX_N; ++c) {
-      const int i = t + c * NTHREADS;
+      const int i = ts + c * NTHREADS;
       if (BX) lf_x_stage(reinterpret_cast<char*>(Xd), i >> 5, i & 31, sx[c], xs);
       else Xd[(i >> 5) * LF_XS + (i & 31)] = sx[c];
     }
+    if (HAND && ts < 64) red[b * 64 + ts] = sh;
   };
   if (dbuf && (int64_t)blockIdx.x < ntiles) {
     stage_load(blockIdx.x);
@@ -287,6 +320,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         if (BX) lf_bx_stage4(reinterpret_cast<char*>(As), r, c4, v, N2, a.gs);
         else *reinterpret_cast<lf_v4*>(As + r * AS + c4) = v;
       }
+      if (HAND && t < 64) red[t] = hand_load(r0, t);
       __syncthreads();
     }
     LF_STAMP()      // tile start: staged, past the top barrier
@@ -403,42 +437,46 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
     // order: the same bits in every wave) into a wave-private slot and reads its 16 rows back -- same-wave LDS write ->
     // read needs no barrier, so a reduction costs one workgroup barrier instead of two
     float* redA = red;                       // [2][NW][32]
-    float* redB = red + 2 * NW * 32;         // [2][NW][32]
-    float* totA = redB + 2 * NW * 32 + w * 64;            // [2][32], this wave's copy
-    float* totB = redB + 2 * NW * 32 + NW * 64 + w * 64;  // [2][32], this wave's copy
+    float* redB = red + (HAND ? 2 * 64 : 2 * NW * 32);    // [2][NW][32]
+    float* totA = HAND ? red + buf * 64 : redB + 2 * NW * 32 + w * 64;            // [2][32], this wave's copy; HAND: the tile's slot, filled a tile ago
+    float* totB = redB + 2 * NW * 32 + (HAND ? 0 : NW * 64) + w * 64;             // [2][32], this wave's copy
     if (red_on) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float sv[4], ssv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          float s = 0.f, ss = 0.f;
-#pragma unroll
-          for (int j = 0; j < NT; ++j) { s += z[j][r]; ss += z[j][r] * z[j][r]; }
-          sv[e] = s;
-          ssv[e] = ss;
-        }
-        const float st = half_sum4(sv[0], sv[1], sv[2], sv[3], lb0, lb1);       // row 8g + 4lh + (li & 3)
-        const float sst = half_sum4(ssv[0], ssv[1], ssv[2], ssv[3], lb0, lb1);
-        if (li < 4) {
-          redA[(0 * NW + w) * 32 + 8 * g + 4 * lh + li] = st;
-          redA[(1 * NW + w) * 32 + 8 * g + 4 * lh + li] = sst;
-        }
-      }
-      __syncthreads();
       float rs_row = 0.f;       // ROW1: 1 / std of row (lane & 31)
-      {
-        float v = 0.f;
+      if (!HAND) {
 #pragma unroll
-        for (int q = 0; q < NW; ++q) v += redA[((lane >> 5) * NW + q) * 32 + (lane & 31)];
-        totA[lane] = ROW1 ? ln_row_stats(v, lane, invH, rs_row) : v;      // ROW1: mean | 1 / std in the sums' place
+        for (int g = 0; g < 4; ++g) {
+          float sv[4], ssv[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            float s = 0.f, ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) { s += z[j][r]; ss += z[j][r] * z[j][r]; }
+            sv[e] = s;
+            ssv[e] = ss;
+          }
+          const float st = half_sum4(sv[0], sv[1], sv[2], sv[3], lb0, lb1);       // row 8g + 4lh + (li & 3)
+          const float sst = half_sum4(ssv[0], ssv[1], ssv[2], ssv[3], lb0, lb1);
+          if (li < 4) {
+            redA[(0 * NW + w) * 32 + 8 * g + 4 * lh + li] = st;
+            redA[(1 * NW + w) * 32 + 8 * g + 4 * lh + li] = sst;
+          }
+        }
+        __syncthreads();
+        {
+          float v = 0.f;
+#pragma unroll
+          for (int q = 0; q < NW; ++q) v += redA[((lane >> 5) * NW + q) * 32 + (lane & 31)];
+          totA[lane] = ROW1 ? ln_row_stats(v, lane, invH, rs_row) : v;      // ROW1: mean | 1 / std in the sums' place
+        }
       }
       if (BX && RLX_LF_DWSCALE && dw_scale == 0.f) {
         // scale of the dW1 operand (see the dW1 block below): gs / (largest 1 / std(z1) of this tile's 32 rows, as a power of
         // two) -- one value per lane from the wave's copy of the row statistics, a wave maximum, and the result lives in an SGPR
         float rs;
-        if (ROW1) {
+        if (HAND) {
+          rs = totA[32 + (lane & 31)];
+        } else if (ROW1) {
           rs = rs_row;
         } else {
           const float mean = totA[lane & 31] * invH;
@@ -455,7 +493,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
         dw_scale = a.gs * x_pow2_inv(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(rs))));
       }
     }
-    LF_STAMP()      // first reduction: partials, barrier, fold (+ ROW1: the row statistics, + first tile: dw_scale)
+    LF_STAMP()      // first reduction: partials, barrier, fold (+ ROW1: the row statistics, + first tile: dw_scale); HAND: the first tile's dw_scale only
     // dy = dH1 * act'(h);  z <- xhat;  acc <- d xhat;  row sums m1, m2
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -611,6 +649,17 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1F
       out[(int64_t)(O + 2) * H1 + col] = v2;
     }
   }
+}
+
+template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN = false, bool ROW1 = false>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1FusedArgs a2) {
+  lf_dx_l1bwd<NT, NW, ACT, LN, BX, TWIN, ROW1, false>(a, a2);
+}
+
+// the HAND form of the split-operand LayerNorm kernel (an entry of its own name: the forms above keep theirs)
+template <int NT, int NW, int ACT, bool TWIN>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd_stats(L1FusedArgs a, L1FusedArgs a2) {
+  lf_dx_l1bwd<NT, NW, ACT, true, true, TWIN, true, true>(a, a2);
 }
 
 // ---- first-layer FORWARD on the matrix pipe ---------------------------------------------------------------------
@@ -779,7 +828,8 @@ struct L12Args {
   const float* b2;
   float* H1;             // [M, 512] out (read by the layer-2 weight gradient), or NULL: that kernel recomputes it (gemm_bx.hip)
   float* H2;             // [M, N2] out
-  float* stats;          // optional [2][M]: LayerNorm mean and 1 / std of every row
+  float* stats;          // optional [2][M]: LayerNorm mean (stats[row]) and 1 / std (stats[M + row]) of every row < M, M the launch's row count -- THE
+                         // definition of the layout; readers: the recomputing weight-gradient producers (gemm_bx.hip) and k_dx_l1bwd_stats
   const uint32_t* xmax;  // optional: bit pattern of max |X| (scale of the observation planes; common.h)
   unsigned long long* stamps;   // tuning aid (rlx_dbg_set_stamps): clock64() of thread 0 of workgroup 0 at the phase boundaries of its first two tiles
   int64_t M;
@@ -796,6 +846,12 @@ __device__ __forceinline__ void l12_xa_stage(char* __restrict__ img, int r, int 
 }
 
 // ROW1 (option ln_row_once): as in k_dx_l1bwd -- mean and 1 / std once per wave and row (ln_row_stats); false: the earlier form
+// a.stats (optional, [2][M]): wave 0 also stores the tile's 32 means and 32 1 / std there -- 64 floats per tile next to its 64 KB of
+// h1.  Readers: the layer-2 weight gradient that rebuilds h1 (dw_recompute: a.H1 is NULL then, h1 is not stored) and, option
+// l1_stats_handover (default 1), the fused first-layer backward of the SAME minibatch pass (k_dx_l1bwd_stats), which loads them instead
+// of rebuilding them from its own z1 -- this kernel's z1 product, partial sums, fold and ln_row_stats are that kernel's code, so the
+// words are the same.  The handover is inactive -- no array, nothing changes here -- with ln_row_once = 0, gemm_bx = 0, without the
+// fused backward, and in any caller outside the PPO minibatch pass (ppo.hip hands the array over per pass).
 template <int ACT, int NT2, bool TWIN, bool NTS = false, bool ROW1 = false>
 __global__ __launch_bounds__(512, NT2 == 1 ? 4 : 2) void k_l12fwd(L12Args a, L12Args a2) {
   if (TWIN && blockIdx.y) a = a2;
@@ -1058,18 +1114,22 @@ int launch_l12fwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const
   const LayerOff &o0 = L.layer[0], &o1 = L.layer[1];
   L12Args a;
   a.X = x; a.W1x = w1x; a.b1 = params + o0.b; a.g = params + o0.g; a.be = params + o0.be; a.W2x = w2x; a.b2 = params + o1.b;
-  a.H1 = stats ? nullptr : h1; a.H2 = h2; a.stats = stats; a.xmax = ctx->l1_xmax; a.M = M; a.O = o0.in;
+  a.H1 = h1; a.H2 = h2; a.stats = stats; a.xmax = ctx->l1_xmax; a.M = M; a.O = o0.in;
   a.stamps = (unsigned long long*)ctx->dbg_stamps;
   L12Args a2 = a;
   if (tw) {
     a2.W1x = tw->w1x; a2.b1 = tw->params + o0.b; a2.g = tw->params + o0.g; a2.be = tw->params + o0.be; a2.W2x = tw->w2x;
-    a2.b2 = tw->params + o1.b; a2.H1 = stats ? nullptr : tw->h1; a2.H2 = tw->h2; a2.stats = tw->stats;
+    a2.b2 = tw->params + o1.b; a2.H1 = tw->h1; a2.H2 = tw->h2; a2.stats = tw->stats;
   }
+  // option l1_stats_handover: what this forward leaves for the fused first-layer backward of the SAME pass (cleared by the pass's scope,
+  // ppo.hip).  Only the ROW1 form's values are the words k_dx_l1bwd<ROW1> computes (ln_row_stats, pinned roundings).
+  ctx->l1_hand[0] = row1 ? a.stats : nullptr;
+  ctx->l1_hand[1] = (row1 && tw) ? a2.stats : nullptr;
   const int N2 = o1.out;
   const double nets = tw ? 2.0 : 1.0;
   // algorithmic: the layer-2 product (the K = O first layer rides along); X in, h1 and h2 out, both weight matrices
   ProfScope prof(ctx, PK_L12FWD, nets * 2.0 * (double)M * L12_H1 * (N2 + o0.in), st,
-                 nets * 4.0 * ((double)M * (o0.in + (stats ? 2 : L12_H1) + N2) + (double)L12_H1 * (N2 + o0.in)), M, N2, L12_H1, 1);
+                 nets * 4.0 * ((double)M * (o0.in + (stats ? 2 : 0) + (h1 ? L12_H1 : 0) + N2) + (double)L12_H1 * (N2 + o0.in)), M, N2, L12_H1, 1);
   const int64_t nt = (M + LF_ROWS - 1) / LF_ROWS;
   const int per = tw ? ctx->num_cus : 2 * ctx->num_cus;
   const int grid = (int)(nt < per ? nt : per);
@@ -1202,23 +1262,29 @@ int launch_l1fused(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, cons
   a.gso = X_WINV / a.gs;
   a.xmax = ctx->l1_xmax;
   a.stamps = RLX_LF_STAMPS ? (unsigned long long*)ctx->dbg_stamps : nullptr;
+  // option l1_stats_handover: the statistics this pass's k_l12fwd<ROW1> left for these rows and this network (never another launch's:
+  // launch_l12fwd sets l1_hand, the pass's scope clears it)
+  const bool row1k = H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first && bxk && ctx->ln_row_once;
+  const bool hand = row1k && ctx->l1_stats_handover && ctx->l1_hand[0] && (!tw || ctx->l1_hand[1]) && M < ((int64_t)1 << 30);
+  a.stats = hand ? ctx->l1_hand[0] : nullptr;
   L1FusedArgs a2 = a;
   if (tw) {
     a2.dZ2 = tw->dZ2; a2.W1 = tw->params + o0.W; a2.b1 = tw->params + o0.b;
     a2.g = o0.g >= 0 ? tw->params + o0.g : nullptr;
     a2.be = o0.be >= 0 ? tw->params + o0.be : nullptr;
     a2.partials = tw->arena; a2.W2x = tw->w2x; a2.W1x = tw->w1x;
+    a2.stats = hand ? ctx->l1_hand[1] : nullptr;
   }
   const int OP = (O + 1) & ~1;
   const size_t a_img = bxk ? (size_t)X_NP * LF_ROWS * N2 / 2 : (size_t)LF_ROWS * (N2 + 4);
-  const size_t lds = bxk ? ((N2 == LFP_N2 ? 2 : 1) * (a_img + LF_XIMG / 4) + 2048) * sizeof(float)
-                         : ((size_t)OP * H1 + (N2 == LFP_N2 ? 2 : 1) * (a_img + LF_ROWS * LF_XS) + 2048) * sizeof(float);
+  const size_t lds = bxk ? ((N2 == LFP_N2 ? 2 : 1) * (a_img + LF_XIMG / 4) + (hand ? LF_RED_HAND : LF_RED)) * sizeof(float)
+                         : ((size_t)OP * H1 + (N2 == LFP_N2 ? 2 : 1) * (a_img + LF_ROWS * LF_XS) + LF_RED) * sizeof(float);
   RLX_REQUIRE(lds <= 160 * 1024, RLX_EUNSUP, "l1fused: tile image exceeds the LDS");
   {
     // main GEMM + z recompute + dW1 on the matrix pipe
     const double ntw = tw ? 2.0 : 1.0;
     ProfScope prof(ctx, PK_DX_L1BWD, ntw * 2.0 * (double)M * H1 * (N2 + O), st,                  // algorithmic: dX + dW1
-                   ntw * 4.0 * ((double)M * N2 + (double)H1 * N2 + (double)M * O + 2.0 * O * H1), M, H1, N2, bxk ? 1 : 0);
+                   ntw * 4.0 * ((double)M * (N2 + (hand ? 2 : 0)) + (double)H1 * N2 + (double)M * O + 2.0 * O * H1), M, H1, N2, bxk ? 1 : 0);
 #define RLX_LF_ATTR(KERNEL)                                                                                    \
   {                                                                                                            \
     static AttrOnce attr_set;                                                                                    \
@@ -1246,12 +1312,22 @@ int launch_l1fused(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, cons
     if (tw) { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, true, true, true, true>), dim3(grid, 2), dim3(64 * NWV), lds, st, a, a2); } \
     else { RLX_PLAUNCH((k_dx_l1bwd<NTV, NWV, ACTV, true, true, false, true>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
   }
-    if (H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first && bxk && ctx->ln_row_once) RLX_LF_LAUNCH_ROW1(2, 8, RLX_ACT_ELU)
+    // option l1_stats_handover (again a template parameter chosen here): the ROW1 form that loads the statistics this pass's forward left
+#define RLX_LF_LAUNCH_HAND(NTV, NWV, ACTV)                                                                      \
+  {                                                                                                            \
+    RLX_LF_ATTR((k_dx_l1bwd_stats<NTV, NWV, ACTV, false>))                                                     \
+    RLX_LF_ATTR((k_dx_l1bwd_stats<NTV, NWV, ACTV, true>))                                                      \
+    if (tw) { RLX_PLAUNCH((k_dx_l1bwd_stats<NTV, NWV, ACTV, true>), dim3(grid, 2), dim3(64 * NWV), lds, st, a, a2); } \
+    else { RLX_PLAUNCH((k_dx_l1bwd_stats<NTV, NWV, ACTV, false>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
+  }
+    if (hand) RLX_LF_LAUNCH_HAND(2, 8, RLX_ACT_ELU)
+    else if (row1k) RLX_LF_LAUNCH_ROW1(2, 8, RLX_ACT_ELU)
     else
     if (H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first) RLX_LF_LAUNCH(2, 8, RLX_ACT_ELU, true)
     else if (H1 == 256 && d.act == RLX_ACT_TANH && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_TANH, false)
     else if (H1 == 256 && d.act == RLX_ACT_RELU && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_RELU, false)
     else RLX_REQUIRE(false, RLX_EUNSUP, "l1fused: unsupported (hidden[0], act, ln) combination");
+#undef RLX_LF_LAUNCH_HAND
 #undef RLX_LF_LAUNCH_ROW1
 #undef RLX_LF_LAUNCH
 #undef RLX_LF_ATTR

@@ -108,8 +108,9 @@ struct L12Twin {
   float* stats = nullptr;
 };
 bool l12fwd_supported(const rlx_mlp_desc& d);
-// stats (optional, [2][M]; twin: tw->stats too): the rows' LayerNorm mean and 1 / std go there and h1 is NOT stored -- the layer-2
-// weight gradient then rebuilds it (BxDwRecompute below)
+// stats (optional, [2][M], L12Args::stats; twin: tw->stats too): the rows' LayerNorm mean and 1 / std go there -- for the fused first-layer
+// backward of the same pass (option l1_stats_handover) and, where h1 (twin: tw->h1) is NULL and so NOT stored, for the layer-2 weight
+// gradient that then rebuilds it (BxDwRecompute below)
 int launch_l12fwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const float* params, const float* x, float* h1, float* h2,
                   const void* w1x, const void* w2x, int64_t M, hipStream_t st, const L12Twin* tw = nullptr, float* stats = nullptr);
 // whole forward of a 256-256 network incl. its head in one launch (fwd2h.hip); needs the forward split images of both layers

@@ -1091,7 +1091,9 @@ int mlp_trunk_fwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const
     const void* w1x = bx_lookup(ctx, params + o0.W, 0, o0.in, o0.out);
     const void* w2x = w1x ? bx_lookup(ctx, params + o1.W, 0, o1.in, o1.out) : nullptr;
     if (w1x && w2x) {
-      rc = launch_l12fwd(ctx, d, L, params, x, acts[0], acts[1], w1x, w2x, M, st, nullptr, ctx->l12_stats);
+      // dw_recompute: the statistics instead of h1; l1_stats_handover: the statistics next to h1 (one array serves both readers)
+      rc = launch_l12fwd(ctx, d, L, params, x, ctx->l12_stats ? nullptr : acts[0], acts[1], w1x, w2x, M, st, nullptr,
+                         ctx->l12_stats ? ctx->l12_stats : ctx->l1_hand_req);
       if (rc) return rc;
       l_next = 2;
       ctx->l12_ran = ctx->l12_stats != nullptr;

@@ -1559,6 +1559,12 @@ static int launch_head_loss(float* H, const float* W, const float* b, const floa
   return RLX_OK;
 }
 
+// option l1_stats_handover: could this pass run k_l12fwd<ROW1> and the split-operand LayerNorm form of k_dx_l1bwd<ROW1> on mb rows?
+static bool l1_handover_wanted(const rlx_ctx* ctx, const rlx_mlp_desc& d, int64_t mb) {
+  return ctx->l1_stats_handover && ctx->ln_row_once && ctx->gemm_bx && ctx->l12_fused && !ctx->disable_l1fused && mb >= 4096 &&
+         l12fwd_supported(d) && l1fused_supported(d);
+}
+
 template <bool POLICY>
 static int net_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const float* params, float* grads, float* metrics,
                        const MbScratch& s, int64_t mb, int mb_global, const rlx_ppo_hparams& hp, float* sumsq,
@@ -1592,13 +1598,23 @@ static int net_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const float* params,
   XmaxScope xscope(ctx, ctx->xmax_slot[(!POLICY && s.mb_xc) ? 1 : 0]);   // scale of the raw-observation operand (k_l12fwd, k_dx_l1bwd)
   // first-layer activations never stored: k_l12fwd leaves the rows' LayerNorm statistics, the merged weight-gradient launch
   // rebuilds its operand (needs the tail's dZ pair -> the two-job launch, and the fused two-layer forward)
-  struct L12Scope { rlx_ctx* c; ~L12Scope() { c->l12_stats = nullptr; c->l12_ran = false; } } l12scope{ctx};
+  struct L12Scope {
+    rlx_ctx* c;
+    ~L12Scope() { c->l12_stats = nullptr; c->l12_ran = false; c->l1_hand_req = nullptr; c->l1_hand[0] = c->l1_hand[1] = nullptr; }
+  } l12scope{ctx};
   ctx->l12_ran = false;
   ctx->l12_stats = nullptr;
+  ctx->l1_hand_req = nullptr;
+  ctx->l1_hand[0] = ctx->l1_hand[1] = nullptr;
   if (ctx->dw_recompute && tail && ctx->l12_fused && l12fwd_supported(d) && dw_merge_ok(ctx, d, L, mb) && d.hidden[0] == 512 &&
       d.act == RLX_ACT_ELU && grads) {
     ctx->l12_stats = (float*)scratch(ctx, SL_LN_P, (size_t)2 * mb * sizeof(float));
     if (!ctx->l12_stats) return RLX_ENOMEM;
+  } else if (l1_handover_wanted(ctx, d, mb) && grads) {
+    // option l1_stats_handover: k_l12fwd leaves the statistics NEXT to h1 for this pass's k_dx_l1bwd (8 bytes per row, this bank's slot --
+    // the two chains run side by side); whether the pair really runs is decided where it is launched (launch_l12fwd / launch_l1fused)
+    ctx->l1_hand_req = (float*)scratch(ctx, SL_LN_P, (size_t)2 * mb * sizeof(float));
+    if (!ctx->l1_hand_req) return RLX_ENOMEM;
   }
   rc = mlp_trunk_fwd(ctx, d, L, params, x_in, s.acts, mb, st, 0, false, nullptr, tail ? d.n_hidden - 1 : -1);
   if (rc) return rc;
@@ -1742,8 +1758,12 @@ static int twin_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& pd, const MlpLayout& L
   int l_first = 1;
   float* stats2[2] = {nullptr, nullptr};     // [2][mb] LayerNorm statistics per network when the first-layer activations are not stored
   const bool l12 = ctx->l12_fused && l12fwd_supported(pd) && im.w1x[0] && im.w1x[1];
-  if (l12 && ctx->dw_recompute && ctx->dw_merge && nh == 3 && tail_shape_ok(ctx, pd, mb, hp) && pd.hidden[0] == 512 &&
-      pd.act == RLX_ACT_ELU) {
+  struct HandScope { rlx_ctx* c; ~HandScope() { c->l1_hand[0] = c->l1_hand[1] = nullptr; } } hand_scope{ctx};
+  ctx->l1_hand[0] = ctx->l1_hand[1] = nullptr;
+  const bool no_h1 = l12 && ctx->dw_recompute && ctx->dw_merge && nh == 3 && tail_shape_ok(ctx, pd, mb, hp) && pd.hidden[0] == 512 &&
+                     pd.act == RLX_ACT_ELU;
+  // ... or next to them, for this pass's fused first-layer backward (option l1_stats_handover; with dw_recompute one array serves both)
+  if (no_h1 || (l12 && l1_handover_wanted(ctx, pd, mb))) {
     const int b0 = ctx->bank;
     for (int q = 0; q < 2; ++q) {
       ctx->bank = q;
@@ -1754,9 +1774,9 @@ static int twin_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& pd, const MlpLayout& L
   }
   if (l12) {
     // first + second layer of both networks in one launch
-    L12Twin tw{cparams, sc.acts[0], sc.acts[1], im.w1x[1], im.f[1][1]};
+    L12Twin tw{cparams, no_h1 ? nullptr : sc.acts[0], sc.acts[1], im.w1x[1], im.f[1][1]};
     tw.stats = stats2[1];
-    rc = launch_l12fwd(ctx, pd, LP, pparams, sp.mb_x, sp.acts[0], sp.acts[1], im.w1x[0], im.f[1][0], mb, st, &tw, stats2[0]);
+    rc = launch_l12fwd(ctx, pd, LP, pparams, sp.mb_x, no_h1 ? nullptr : sp.acts[0], sp.acts[1], im.w1x[0], im.f[1][0], mb, st, &tw, stats2[0]);
     l_first = 2;
   } else {
     rc = launch_l1fwd_mfma(pd, LP, pparams, sp.mb_x, sp.acts[0], mb, ctx->num_cus, st, nullptr, ctx, cparams, sc.acts[0]);
@@ -1850,7 +1870,7 @@ static int twin_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& pd, const MlpLayout& L
         const LayerOff& o3 = LP.layer[2];
         BxDwJob j2{sp.acts[0], dzb[1][0], pW[1][0], pB[1][0], o.in, o.in, o.out, Mc[1], S[1], div_up(o.in, G_BM), div_up(o.out, G_BN)};
         BxDwRecompute rcd;
-        if (stats2[0]) {       // the first-layer activations were not stored: the layer-2 job rebuilds them
+        if (no_h1) {           // the first-layer activations were not stored: the layer-2 job rebuilds them
           const LayerOff& o0 = LP.layer[0];
           rcd.X = sp.mb_x; rcd.W1x = im.w1x[0]; rcd.b1 = pparams + o0.b; rcd.g = pparams + o0.g; rcd.be = pparams + o0.be;
           rcd.stats = stats2[0]; rcd.xmax = ctx->l1_xmax; rcd.W1x1 = im.w1x[1]; rcd.stats1 = stats2[1];
