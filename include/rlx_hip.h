@@ -186,6 +186,11 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   them instead of rebuilding them from its recomputed z1.  Active only with "ln_row_once" = 1 on the split-operand engine
  *   ("gemm_bx" = 1) where the pass's forward was k_l12fwd -- there both kernels run the same code on the same rows: bit-identical
  *   results (tests/test_gpu_l1_stats_handover.py); everywhere else, and with 0, the earlier kernels run unchanged.
+ * Round 10: "l1_wrap_refill" (1 default; 0 or 1, anything else is RLX_EINVAL): where "l1_stats_handover" selects the handover form
+ *   of the fused first-layer backward, 1 runs it with unconditional weight-fragment refills in its main loop that wrap into the
+ *   first-layer image (k_dx_l1bwd_stats_wrap: no drained wait in the K loop, no loads in the z1 recompute); the same operand words
+ *   into the same MFMAs in the same order: bit-identical results (tests/test_gpu_l1_wrap_refill.py); 0, and everywhere the
+ *   handover form is not selected, the earlier kernels run unchanged.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,
@@ -195,7 +200,8 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value);
 /* test hooks: "scratch_ptr:<bank>:<slot>" / "scratch_bytes:<bank>:<slot>" = device address / size of a library-owned scratch
  * arena (lets a test inspect intermediates); "allreduce_calls" = collectives this context has issued so far (through its RCCL
  * communicator or the all-reduce hook) -- bench.py's multi_gpu.collectives_per_step is the difference over the timed steps;
- * "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
+ * "dx_l1bwd_wrap_launches" = launches of k_dx_l1bwd_stats_wrap so far (option "l1_wrap_refill"; the profiler books both forms of
+ * the kernel under one row); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
  * the fp16 window of the split-operand engine -- and therefore ran their T steps on the exact-fp32 engine; "gemm_bx" = the
  * current value of that option                                                                                          */
 int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out);

@@ -138,6 +138,11 @@ struct rlx_ctx {
                                           // forward was k_l12fwd: there the two computations are the same code, so the results are bit-identical.
                                           // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 65.36 vs 67.12 ms per iteration at 32768-row
                                           // minibatches (block-to-block sd 0.15 / 0.17), 107.10 vs 108.91 at 4096 rows
+  int l1_wrap_refill = 1;                 // fused first-layer backward, handover form only: 1 k_dx_l1bwd_stats_wrap -- every 16-k block of the main product
+                                          // refills its fragment slot unconditionally (the last two refills of a row tile fetch the first-layer image's two
+                                          // blocks, which the z1 recompute then takes from registers), so no s_waitcnt vmcnt(0) is left in the K loop; 0
+                                          // k_dx_l1bwd_stats.  Same operand words into the same MFMAs: bit-identical.  
+  int64_t dx_l1bwd_wrap_launches = 0;     // launches of k_dx_l1bwd_stats_wrap since the context was created (the profiler row is k_dx_l1bwd's in both forms)
   float* l1_hand_req = nullptr;           // set by a minibatch pass that wants the handover: [2][M] scratch k_l12fwd fills when dw_recompute does not
                                           // already make it write l12_stats (then that array serves both readers)
   const float* l1_hand[2] = {nullptr, nullptr};   // set by launch_l12fwd<ROW1>: the arrays it filled (twin: [1] the second network's); cleared with

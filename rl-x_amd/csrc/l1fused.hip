@@ -148,11 +148,23 @@ __device__ __forceinline__ void lf_x_stage(char* __restrict__ img, int r, int k,
 // row sums and the dW1 operand is (+-0) x (a finite value) = +-0 under ANY finite pair, and x + (+-0) leaves every accumulator bit
 // (accumulators start at +0 and never become -0); the dW1 scale ignores such rows (rs = 0) as before.
 // The host selects this form only where this pass's forward was k_l12fwd<ROW1> with a statistics array (launch_l1fused).
-template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN, bool ROW1, bool HAND>
+// WRAP (option l1_wrap_refill, HAND only; the entry point is k_dx_l1bwd_stats_wrap): every 16-k block of the main product refills the
+// fragment slot it has just consumed, unconditionally, and a scheduling barrier keeps that refill behind ITS products.  With the refill
+// behind `if (q + u + PFX < nb16)` hipcc cannot count the loads in flight at the loop header and opens the second block of every pair
+// with s_waitcnt vmcnt(0): the fragments requested six MFMAs earlier are drained, one exposed L2 round trip per two blocks (the recipe
+// and its reason: fwd2h.hip, F2_L1_BLOCK).  The refills past the last block of W2's image wrap into the FIRST-layer image: its two 16-k
+// blocks (gemm_bx.hip, add_job: KB = 2 * ceil(K / 32), so the second exists -- all zero words -- for O <= 16 too) are exactly the
+// PFX = 2 slots, so the z1 recompute that follows finds its weight fragments in registers and issues no loads (it loaded them at the
+// point of use, the second block's behind the first block's MFMAs).  The same words into the same MFMAs in the same order:
+// bit-identical results (tests/test_gpu_l1_wrap_refill.py).
+template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN, bool ROW1, bool HAND, bool WRAP>
 __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2) {
   if (TWIN && blockIdx.y) a = a2;
   static_assert(!ROW1 || LN, "ROW1 is a form of the LayerNorm statistics");
   static_assert(!HAND || (ROW1 && BX), "HAND takes the statistics of k_l12fwd<ROW1>: the split-operand LayerNorm form only");
+  static_assert(!WRAP || HAND, "WRAP is a form of the handover kernel");
+  static_assert(!WRAP || RLX_LF_PFX == 2, "WRAP: the first-layer image has exactly two 16-k blocks, one per fragment slot");
+  static_assert(!WRAP || RLX_LF_ABL == 0, "the ablations are for the earlier forms");
   constexpr int H1 = 32 * NT * NW;
   constexpr int NTHREADS = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -331,6 +343,32 @@ __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2
       // split-fp32 operands on the half-precision pipe: three MFMAs per 16 k and column tile (gemm_bx.h)
       const char* img = reinterpret_cast<const char*>(As);
       const int plane = LF_ROWS * 2 * N2, nb16 = N2 >> 4;
+#define RLX_LF_BX_STEP(P, Q)                                                                                      \
+  _Pragma("unroll") for (int j = 0; j < NT; ++j)                                                                  \
+      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[P]),                           \
+                                                      __builtin_bit_cast(f16x8, bx[u][j][Q]), acc[j], 0, 0, 0);
+      // WRAP -- one 16-k block: A fragment from the dZ2 planes, three plane products per column tile, and the fragments PFX blocks
+      // ahead into the slot just consumed; past W2's last block they are the first layer's (block nb - nb16 is u: PFX divides nb16)
+#define RLX_LF_BX_BLOCK()                                                                                         \
+  {                                                                                                               \
+    u32x4 av[X_NP];                                                                                               \
+    const char* ab = img + lf_bx_off(li, 2 * (q + u) + lh, N2);                                                   \
+    _Pragma("unroll") for (int p = 0; p < X_NP; ++p) av[p] = *reinterpret_cast<const u32x4*>(ab + p * plane);     \
+    RLX_LF_BX_STEP(0, 1)                                                                                          \
+    RLX_LF_BX_STEP(1, 0)                                                                                          \
+    RLX_LF_BX_STEP(0, 0)                                                                                          \
+    const int nb = q + u + PFX;                                                                                   \
+    const u32x4* __restrict__ wn = nb < nb16 ? Wx + (int64_t)nb * wx_step : W1x + (int64_t)(nb - nb16) * wx_step; \
+    _Pragma("unroll") for (int j = 0; j < NT; ++j)                                                                \
+      _Pragma("unroll") for (int p = 0; p < X_NP; ++p) bx[u][j][p] = wn[(j * X_NP + p) * 64];                     \
+    __builtin_amdgcn_sched_barrier(0);   /* without it hipcc sinks both refills to the end of the pair and waits vmcnt(0) at its top */ \
+  }
+      if constexpr (WRAP) {
+        for (int q = 0; q < nb16; q += PFX) {
+#pragma unroll
+          for (int u = 0; u < PFX; ++u) RLX_LF_BX_BLOCK()
+        }
+      } else
       for (int q = 0; q < nb16; q += PFX) {
 #pragma unroll
         for (int u = 0; u < PFX; ++u) {
@@ -338,14 +376,9 @@ __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2
           const char* ab = img + lf_bx_off(li, 2 * (q + u) + lh, N2);
 #pragma unroll
           for (int p = 0; p < X_NP; ++p) av[p] = *reinterpret_cast<const u32x4*>(ab + p * plane);
-#define RLX_LF_BX_STEP(P, Q)                                                                                      \
-  _Pragma("unroll") for (int j = 0; j < NT; ++j)                                                                  \
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[P]),                           \
-                                                      __builtin_bit_cast(f16x8, bx[u][j][Q]), acc[j], 0, 0, 0);
           RLX_LF_BX_STEP(0, 1)
           RLX_LF_BX_STEP(1, 0)
           RLX_LF_BX_STEP(0, 0)
-#undef RLX_LF_BX_STEP
           if (q + u + PFX < nb16) {
 #pragma unroll
             for (int j = 0; j < NT; ++j)
@@ -354,6 +387,8 @@ __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2
           }
         }
       }
+#undef RLX_LF_BX_BLOCK
+#undef RLX_LF_BX_STEP
     } else
     for (int q = 0; q < nq; q += PF) {
 #pragma unroll
@@ -397,6 +432,25 @@ __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2
         for (int r = 0; r < 16; ++r) z[j][r] = bias[j] * (xs * X_WSCALE);
       const char* xa = reinterpret_cast<const char*>(Xs);
       const int nks = O > 16 ? 2 : 1;           // (uniform) obs indices >= 16 live in the second 16-k block
+      if constexpr (WRAP) {
+        // the two blocks' weight fragments are in bx[0] / bx[1] (the main loop's wrapped refills): no loads here; with O <= 16 the
+        // second block (all zero words) was fetched and is not multiplied
+#pragma unroll
+        for (int s_ = 0; s_ < 2; ++s_) {
+          u32x4 xf[X_NP];
+#pragma unroll
+          for (int p = 0; p < X_NP; ++p) xf[p] = *reinterpret_cast<const u32x4*>(xa + p * LF_XPLANE + bx_off(li, 2 * s_ + lh));
+          if (s_ < nks) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+              const u32x4 w0 = bx[s_][j][0], w1 = bx[s_][j][1];
+              z[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xf[0]), __builtin_bit_cast(f16x8, w1), z[j], 0, 0, 0);
+              z[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xf[1]), __builtin_bit_cast(f16x8, w0), z[j], 0, 0, 0);
+              z[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, xf[0]), __builtin_bit_cast(f16x8, w0), z[j], 0, 0, 0);
+            }
+          }
+        }
+      } else
       for (int s_ = 0; s_ < ((RLX_LF_ABL & 8) ? 0 : nks); ++s_) {
         u32x4 xf[X_NP];
 #pragma unroll
@@ -653,13 +707,18 @@ __device__ __forceinline__ void lf_dx_l1bwd(L1FusedArgs a, const L1FusedArgs& a2
 
 template <int NT, int NW, int ACT, bool LN, bool BX, bool TWIN = false, bool ROW1 = false>
 __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd(L1FusedArgs a, L1FusedArgs a2) {
-  lf_dx_l1bwd<NT, NW, ACT, LN, BX, TWIN, ROW1, false>(a, a2);
+  lf_dx_l1bwd<NT, NW, ACT, LN, BX, TWIN, ROW1, false, false>(a, a2);
 }
 
 // the HAND form of the split-operand LayerNorm kernel (an entry of its own name: the forms above keep theirs)
 template <int NT, int NW, int ACT, bool TWIN>
 __global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd_stats(L1FusedArgs a, L1FusedArgs a2) {
-  lf_dx_l1bwd<NT, NW, ACT, true, true, TWIN, true, true>(a, a2);
+  lf_dx_l1bwd<NT, NW, ACT, true, true, TWIN, true, true, false>(a, a2);
+}
+// option l1_wrap_refill: the handover form with unconditional, wrapping fragment refills (WRAP)
+template <int NT, int NW, int ACT, bool TWIN>
+__global__ __launch_bounds__(64 * NW, NW / 4) void k_dx_l1bwd_stats_wrap(L1FusedArgs a, L1FusedArgs a2) {
+  lf_dx_l1bwd<NT, NW, ACT, true, true, TWIN, true, true, true>(a, a2);
 }
 
 // ---- first-layer FORWARD on the matrix pipe ---------------------------------------------------------------------
@@ -1320,13 +1379,25 @@ int launch_l1fused(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, cons
     if (tw) { RLX_PLAUNCH((k_dx_l1bwd_stats<NTV, NWV, ACTV, true>), dim3(grid, 2), dim3(64 * NWV), lds, st, a, a2); } \
     else { RLX_PLAUNCH((k_dx_l1bwd_stats<NTV, NWV, ACTV, false>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
   }
-    if (hand) RLX_LF_LAUNCH_HAND(2, 8, RLX_ACT_ELU)
+    // option l1_wrap_refill: the handover form whose main loop keeps both fragment slots in flight and prefetches the z1 operand; the same
+    // bytes, LDS, grid and profiler row (rlx_dbg_get_counter "dx_l1bwd_wrap_launches" tells the forms apart)
+#define RLX_LF_LAUNCH_WRAP(NTV, NWV, ACTV)                                                                      \
+  {                                                                                                            \
+    RLX_LF_ATTR((k_dx_l1bwd_stats_wrap<NTV, NWV, ACTV, false>))                                                \
+    RLX_LF_ATTR((k_dx_l1bwd_stats_wrap<NTV, NWV, ACTV, true>))                                                 \
+    if (tw) { RLX_PLAUNCH((k_dx_l1bwd_stats_wrap<NTV, NWV, ACTV, true>), dim3(grid, 2), dim3(64 * NWV), lds, st, a, a2); } \
+    else { RLX_PLAUNCH((k_dx_l1bwd_stats_wrap<NTV, NWV, ACTV, false>), dim3(grid), dim3(64 * NWV), lds, st, a, a2); } \
+    ++ctx->dx_l1bwd_wrap_launches;                                                                             \
+  }
+    if (hand && ctx->l1_wrap_refill) RLX_LF_LAUNCH_WRAP(2, 8, RLX_ACT_ELU)
+    else if (hand) RLX_LF_LAUNCH_HAND(2, 8, RLX_ACT_ELU)
     else if (row1k) RLX_LF_LAUNCH_ROW1(2, 8, RLX_ACT_ELU)
     else
     if (H1 == 512 && d.act == RLX_ACT_ELU && d.ln_first) RLX_LF_LAUNCH(2, 8, RLX_ACT_ELU, true)
     else if (H1 == 256 && d.act == RLX_ACT_TANH && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_TANH, false)
     else if (H1 == 256 && d.act == RLX_ACT_RELU && !d.ln_first) RLX_LF_LAUNCH(2, 4, RLX_ACT_RELU, false)
     else RLX_REQUIRE(false, RLX_EUNSUP, "l1fused: unsupported (hidden[0], act, ln) combination");
+#undef RLX_LF_LAUNCH_WRAP
 #undef RLX_LF_LAUNCH_HAND
 #undef RLX_LF_LAUNCH_ROW1
 #undef RLX_LF_LAUNCH

@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Tuning aid: phase stamps (clock64 of thread 0, workgroup 0) of k_dx_l1bwd<2, 8, ELU, LN, BX> at the bench minibatch, every kernel
 alone on the chip, in the two forms of a library option alternated twice in one process: by default l1_stats_handover = 0 (the
-LayerNorm row statistics rebuilt from the recomputed z1) and = 1 (loaded from the array k_l12fwd left: k_dx_l1bwd_stats).
+LayerNorm row statistics rebuilt from the recomputed z1) and = 1 (loaded from the array k_l12fwd left: k_dx_l1bwd_stats); with
+l1_wrap_refill the handover form's K loop with the conditional refill (0: k_dx_l1bwd_stats) and with unconditional refills that wrap
+into the first-layer image (1: k_dx_l1bwd_stats_wrap) -- the stamps sit at the same source positions in both.  A stamp does not wait
+for what was issued before it, so a boundary moves with the loads: read the whole tile and the sum of the first three phases.
 Needs a library built with the stamps compiled in: RLX_EXTRA_DEFINES=-DRLX_LF_STAMPS=1 python rl-x_amd/build.py --force
-    python tools/dx_phases.py [minibatch rows, default 32768] [option, default l1_stats_handover; e.g. ln_row_once]"""
+    python tools/dx_phases.py [minibatch rows, default 32768] [option, default l1_stats_handover; e.g. ln_row_once, l1_wrap_refill]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rl-x_amd")); sys.path.insert(0, ROOT)
@@ -29,7 +32,7 @@ REPS = 5
 for form in (0, 1, 0, 1):
     ctx.set_option(OPTION, form)
     names = ["tile start (top barrier, next tile's loads issued)", "K loop + rescale + next tile's stage store", "z1 recompute",
-             HAND1 if (OPTION == "l1_stats_handover" and form == 1) else RED1, "element-wise loop 1", "reduction 2 (barrier, fold)",
+             HAND1 if ((OPTION == "l1_stats_handover" and form == 1) or OPTION == "l1_wrap_refill") else RED1, "element-wise loop 1", "reduction 2 (barrier, fold)",
              "element-wise loop 2", "dW1 product (issue)"]
     for _ in range(3):
         ctx.ppo_minibatch_fwd_bwd(pd, P, pg, cd, C, cg, met, states, actions, logp, ret, adv, idx, hp)
@@ -50,4 +53,4 @@ for form in (0, 1, 0, 1):
     print(f"{OPTION} = {form}: k_dx_l1bwd workgroup 0 (the critic's launch), mb {mb}, mean of {REPS} launches: two tiles = {sum(d):.0f} clock64 ticks at {ghz / REPS:.2f} GHz")
     for t in range(2):
         print(f"  tile {t}: " + ", ".join(f"{n} {v:.0f}" for n, v in zip(names, d[8 * t:8 * t + 8])))
-    print(f"  tile 1, element-wise phases (reduction 1 .. loop 2): {sum(d[11:15]):.0f} ticks; whole tile {sum(d[8:16]):.0f}")
+    print(f"  tile 1, tile start + K loop + z1 recompute: {sum(d[8:11]):.0f} ticks; element-wise phases (reduction 1 .. loop 2): {sum(d[11:15]):.0f} ticks; whole tile {sum(d[8:16]):.0f}")
