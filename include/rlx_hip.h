@@ -191,6 +191,13 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   first-layer image (k_dx_l1bwd_stats_wrap: no drained wait in the K loop, no loads in the z1 recompute); the same operand words
  *   into the same MFMAs in the same order: bit-identical results (tests/test_gpu_l1_wrap_refill.py); 0, and everywhere the
  *   handover form is not selected, the earlier kernels run unchanged.
+ * Round 11: "l12_prefetch" (1 default; 0 or 1, anything else is RLX_EINVAL): where k_l12fwd runs in its "ln_row_once" form with
+ *   hidden[1] = 256, 1 runs k_l12fwd_pf: a row tile's z1 product takes its first-layer weight fragments from registers (the
+ *   previous tile's layer-2 K loop refills its last two fragment slots from the first-layer image and requests the rest behind its
+ *   last product; a workgroup's first tile requests all eight before anything else), the next tile's observation loads follow
+ *   them and are staged behind the K loop, and no spilled register is reloaded at the tile top.  The same operand words into the
+ *   same MFMAs in the same order, the same stores: bit-identical results (tests/test_gpu_l12_prefetch.py); 0, hidden[1] = 512,
+ *   "ln_row_once" = 0 and every caller that does not take the k_l12fwd path run the earlier kernels unchanged.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,
@@ -201,7 +208,8 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value);
  * arena (lets a test inspect intermediates); "allreduce_calls" = collectives this context has issued so far (through its RCCL
  * communicator or the all-reduce hook) -- bench.py's multi_gpu.collectives_per_step is the difference over the timed steps;
  * "dx_l1bwd_wrap_launches" = launches of k_dx_l1bwd_stats_wrap so far (option "l1_wrap_refill"; the profiler books both forms of
- * the kernel under one row); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
+ * the kernel under one row); "l12fwd_pf_launches" = launches of k_l12fwd_pf so far (option "l12_prefetch"; the profiler books both
+ * forms of k_l12fwd under one row); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
  * the fp16 window of the split-operand engine -- and therefore ran their T steps on the exact-fp32 engine; "gemm_bx" = the
  * current value of that option                                                                                          */
 int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out);

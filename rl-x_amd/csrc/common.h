@@ -143,6 +143,14 @@ struct rlx_ctx {
                                           // blocks, which the z1 recompute then takes from registers), so no s_waitcnt vmcnt(0) is left in the K loop; 0
                                           // k_dx_l1bwd_stats.  Same operand words into the same MFMAs: bit-identical.  
   int64_t dx_l1bwd_wrap_launches = 0;     // launches of k_dx_l1bwd_stats_wrap since the context was created (the profiler row is k_dx_l1bwd's in both forms)
+  int l12_prefetch = 1;                   // k_l12fwd, ln_row_once form at hidden[1] = 256 only: 1 k_l12fwd_pf -- the first-layer weight fragments of a row tile's z1
+                                          // product are in registers when the tile starts (requested by the previous tile's layer-2 K loop and behind it; first
+                                          // tile: at the top of the kernel), the next tile's observations are requested behind them and staged behind the K
+                                          // loop, and nothing is reloaded from scratch at the tile top; 0 k_l12fwd.  Same operand words into the same MFMAs,
+                                          // same stores: bit-identical.  
+                                          // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 62.52 vs 63.36 ms per iteration at 32768-row
+                                          // minibatches (block-to-block sd 0.08 / 0.10); at 4096 rows 104.9 vs 106.2 in a drifting process (sd 0.7): not claimed
+  int64_t l12fwd_pf_launches = 0;         // launches of k_l12fwd_pf since the context was created (the profiler row is k_l12fwd's in both forms)
   float* l1_hand_req = nullptr;           // set by a minibatch pass that wants the handover: [2][M] scratch k_l12fwd fills when dw_recompute does not
                                           // already make it write l12_stats (then that array serves both readers)
   const float* l1_hand[2] = {nullptr, nullptr};   // set by launch_l12fwd<ROW1>: the arrays it filled (twin: [1] the second network's); cleared with

@@ -256,6 +256,11 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
     ctx->l1_wrap_refill = value;
     return RLX_OK;
   }
+  if (std::string(name) == "l12_prefetch") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: l12_prefetch is 0 or 1");
+    ctx->l12_prefetch = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "bx_force_mi") { ctx->bx_force_mi = value; return RLX_OK; }
   if (std::string(name) == "adam_emit") { ctx->adam_emit = value != 0; return RLX_OK; }
   if (std::string(name) == "bx_debug") { ctx->bx_debug = value; return RLX_OK; }
@@ -280,6 +285,7 @@ int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out) {
   }
   if (std::string(name) == "allreduce_calls") { *out = ctx->ar_calls; return RLX_OK; }
   if (std::string(name) == "dx_l1bwd_wrap_launches") { *out = ctx->dx_l1bwd_wrap_launches; return RLX_OK; }
+  if (std::string(name) == "l12fwd_pf_launches") { *out = ctx->l12fwd_pf_launches; return RLX_OK; }
   if (std::string(name) == "bx_window_fallbacks") { *out = ctx->bx_window_fallbacks; return RLX_OK; }
   if (std::string(name) == "gemm_bx") { *out = ctx->gemm_bx ? 1 : 0; return RLX_OK; }
   RLX_REQUIRE(false, RLX_EINVAL, "rlx_dbg_get_counter: unknown counter");
