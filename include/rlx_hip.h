@@ -302,7 +302,9 @@ int rlx_actor_critic_fwd_sample_discrete_f32(rlx_ctx*, const rlx_mlp_desc* pdesc
  * Observations are double buffered by the caller: obs_in = Batch.states[t] (read only),
  * obs_out = Batch.states[t+1] (post-reset next observation, written when fuse_env).
  * rlx_ppo_rollout_step_supported() tells whether the network shapes fit the fused kernel
- * (in_dim <= 32, hidden[0] % 64 == 0 and <= 512, later hidden layers 128 or 256 wide).      */
+ * (1 <= in_dim <= 32, one to three hidden layers, hidden[0] % 64 == 0 and in [64, 512], later hidden layers 128 or 256 wide,
+ * 1 <= out_dim <= 32 -- a single hidden layer of 512 with 32 outputs included: its head is staged across the two LDS regions
+ * that are free then -- the same in_dim for both nets, a policy with logstd, a critic with one output).                      */
 int rlx_ppo_rollout_step_supported(const rlx_mlp_desc* pdesc, const rlx_mlp_desc* cdesc);
 /* Optional bracket around the T acting steps of one rollout: rlx_ppo_rollout_begin lays out the split-fp16 weight images of the
  * hidden layers l >= 1 of both nets (one small launch; gemm_bx option), and the rlx_ppo_rollout_step_f32 calls that follow with

@@ -56,10 +56,13 @@ class RandomObsEnvOracle:
         self.last_len = np.zeros(self.N, np.float32)
         return self.obs.copy()
 
+    def target_cols(self):
+        """the observation column action dim j is scored against: j % O (wraps when A > O)"""
+        return np.arange(self.A) % self.O
+
     def step(self, action):
         a = np.clip(action.astype(np.float32), -1, 1)
-        j = np.arange(self.A)
-        target = np.tanh(self.obs[:, j % self.O]).astype(np.float32)
+        target = np.tanh(self.obs[:, self.target_cols()]).astype(np.float32)
         w0, w1 = prng.threefry2x32(U32(self.seed), self.ids, U32(self.t), U32(STREAM_MISC))
         zr = _normal_from_bits(w0)
         ut = prng._bits_to_unit_float(w1)

@@ -597,10 +597,14 @@ __global__ __launch_bounds__(RO_THREADS, 1) void k_rollout_step(RolloutArgs a) {
   {
     const int r = t & 31;
     const int OD = out_dim;
-    // head weights [hk, OD] staged in LDS (the weight stage is free now): the dot products then run on LDS reads only
-    // (reading W from global inside the k loop cost ~8 us per step)
-    float* Whs = Bs;
-    for (int i = t; i < hk * OD; i += RO_THREADS) Whs[i] = Pg[oHW + i];      // (<= 1536 floats: six loads in flight per thread)
+    // head weights [hk, OD] staged in LDS: the dot products then run on LDS reads only (reading W from global inside the k loop
+    // cost ~8 us per step).  Behind hidden layers hk <= RO_MAXN and the weight stage holds them (hk * OD <= 256 * 32 = 8192 <=
+    // RO_BS; A1 or A0 is the head's input).  With ONE hidden layer hk = H0 <= 512: up to 512 * 32 = 16384 floats, twice the weight
+    // stage -- but then the input is A0 and A1 | Bs, contiguous and both free behind the barrier above (the VALU layer 0 has read
+    // its W0 copy, the matrix-pipe one its row sums), hold RO_A1 + RO_BS = 16544.
+    static_assert(RO_MAXN * 32 <= RO_BS && RO_MAXH * 32 <= RO_A1 + RO_BS, "head weights outgrow their LDS stage");
+    float* Whs = n_hidden == 1 ? A1 : Bs;
+    for (int i = t; i < hk * OD; i += RO_THREADS) Whs[i] = Pg[oHW + i];      // (1536 floats at 128 x 12: six loads in flight per thread)
     __syncthreads();
     for (int o = t >> 5; o < OD; o += 8) {
       float acc0 = 0.f, acc1 = 0.f;
@@ -728,8 +732,8 @@ static bool fill_net(const rlx_mlp_desc& d, const float* params, RolloutNet* n) 
   n->out_dim = d.out_dim;
   n->act = d.act;
   n->ln_first = d.ln_first;
-  if (d.n_hidden < 1 || d.n_hidden > 3 || d.in_dim > 32) return false;
-  if (d.hidden[0] % 64 != 0 || d.hidden[0] > RO_MAXH) return false;
+  if (d.n_hidden < 1 || d.n_hidden > 3 || d.in_dim < 1 || d.in_dim > 32 || d.out_dim < 1) return false;   // (the env indexes obs[j % in_dim])
+  if (d.hidden[0] < 64 || d.hidden[0] % 64 != 0 || d.hidden[0] > RO_MAXH) return false;
   for (int l = 0; l < d.n_hidden; ++l) {
     n->hidden[l] = d.hidden[l];
     n->W[l] = L.layer[l].W;
