@@ -736,6 +736,49 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pp
                                   const float* qparams, const float* states, const float* critic_states, int64_t B,
                                   int64_t* opt_count_io, const rlx_fasttd3_hparams* hp, float* metrics_out, void* stream);
 
+/* ---- TQC: truncated quantile critics (rl_x/algorithms/tqc/flax) ------------------------------------------------------------
+ * SAC's host-loop flavour (sac/flax/sac.py) with another critic: tqc/flax/policy.py and replay_buffer.py are sac/flax's files, so
+ * acting and sampling are rlx_sac_act_processed_f32 and rlx_sac_replay_sample_f32.  Networks: rlx_mlp_desc with act =
+ * RLX_ACT_RELU, ln_first = 0, has_logstd = 0 (policy.py:22-41: out_dim = 2 * act_dim, head columns [0, A) mean, [A, 2A) raw
+ * log_std; critic.py:17-55: ensemble_size independent networks on [critic obs | action], each nr_atoms_per_net outputs, BACK TO
+ * BACK in one flat vector like rlx_sac_update_f32's two).  FLAT LAYOUT of a network: FastTD3's (above).  Envelope: 1..3 hidden
+ * layers, widths multiples of 64 up to 1024, act_dim <= 64, 1 <= ensemble_size <= 8, nr_atoms_per_net >= 1, total atoms T =
+ * ensemble_size * nr_atoms_per_net <= 128, 0 <= nr_dropped_atoms_per_net < nr_atoms_per_net, huber_kappa > 0, B > 0; a descriptor
+ * or size outside it is RLX_EUNSUP, every other bad argument RLX_EINVAL, rlx_last_error() names the argument.
+ * Flat atom index i = e * nr_atoms_per_net + n (q_atoms.reshape(nr_total_atoms), tqc.py:162); K = T - ensemble_size *
+ * nr_dropped_atoms_per_net target atoms (tqc.py:61).  Atoms that are NaN are outside the contract (the sort drops them).        */
+typedef struct rlx_tqc_hparams {              /* tqc/flax/default_config.py:9-28 */
+  float gamma, tau, target_entropy, log_std_min, log_std_max;
+  float lr_policy, lr_critic, lr_alpha;       /* host evaluates the schedule (tqc.py:85-93) */
+  float adam_b1, adam_b2, adam_eps;           /* optax.adam defaults 0.9, 0.999, 1e-8 (tqc.py:101,108,114) */
+  float huber_kappa;                          /* tqc.py:169-170 */
+  int32_t ensemble_size, nr_atoms_per_net, nr_dropped_atoms_per_net;   /* tqc.py:51-53, :60-61 */
+  const float *critic_states, *critic_next_states;   /* as in rlx_sac_hparams: the critics' own observation columns
+                                                      * (critic.py:11,23) of s / s', or NULL both (the policy's) */
+} rlx_tqc_hparams;
+
+/* the critic loss on given atoms (tqc.py:155-170), like rlx_c51_critic_loss_f32: q_atoms, next_atoms DEVICE [E, B, N]
+ * (critic-major, as E head GEMMs leave them); y[b, k] = r_b + gamma (1 - term_b) (sorted pooled next atoms[k] - exp(log_alpha)
+ * next_logp_b), k < K (tqc.py:156-158: the POOLED T atoms are sorted, not each network's); loss = mean over b, i, k of
+ * |tau_i - [y_k < q_i]| huber_kappa(y_k - q_i) / kappa, tau_i = (i + 0.5) / T (tqc.py:164-170); dq_out [E, B, N] = d loss / d q_atoms;
+ * loss_out DEVICE [1]; y_out NULL or DEVICE [B, K] */
+int rlx_tqc_quantile_loss_f32(rlx_ctx*, const float* q_atoms, const float* next_atoms, const float* rewards,
+                              const float* terminations, const float* next_logp, const float* log_alpha, int64_t B,
+                              const rlx_tqc_hparams* hp, float* dq_out, float* loss_out, float* y_out, void* stream);
+
+/* the whole jitted `update` (tqc.py:134-230): loss_fn meaned over the batch (:139-209), per-sample keys keys = split(key, 2B+1),
+ * key = keys[0], next-state noise keys[1::2], current-state noise keys[2::2] (:211-212; rlx_dbg_set_sac_noise(eps_next, eps_cur)
+ * injects the N(0, 1) draws [B, A] instead), three plain optax.adam steps without clipping (:218-220), Polyak of all critics
+ * (:223).  qparams / qm / qv / qtarget: [E * nq], the E critics back to back.  states / next_states: the policy's columns
+ * [B, pdesc->in_dim].  One call, no host synchronisation.  opt_count_io (HOST): optimizer steps so far, advanced by 1.
+ * metrics_out DEVICE float[10] in rlx_sac_update_f32's order (q_value = mean over all atoms, tqc.py:183; [9] = 0) */
+int rlx_tqc_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv,
+                       const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qtarget,
+                       float* log_alpha, float* am, float* av, const float* states, const float* next_states,
+                       const float* actions, const float* rewards, const float* terminations, int64_t B,
+                       uint32_t key_io[2], int scheme, int64_t* opt_count_io, const rlx_tqc_hparams* hp,
+                       float* metrics_out, void* stream);
+
 /* =================================== REPPO ===============================================
  * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
  * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust

@@ -1,4 +1,4 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip and espo.hip on the host side: the launchers of
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip and tqc.hip on the host side: the launchers of
 // dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
@@ -255,9 +255,11 @@ static inline size_t chain_stage_floats(const rlx_ctx* ctx, const Chain& L, int6
 // weight images of the hidden layers of several chains; bwd: the pass needs the transposed images too (input gradients).
 // The budget is the image builder's job table: BX_MAX_JOBS images in one launch, a forward image is one job and a transposed one
 // another.  Matrices are taken in the order listed (nets[0] first, layer 0 first) and the list ENDS at the first matrix whose
-// jobs no longer fit: that layer and everything after it run on the exact engine.  No descriptor its two callers (fastsac.hip,
-// fasttd3.hip) accept gets there -- the largest is FastSAC's critic update with four hidden layers: 4 + 2 * 4 + 2 * (4 + 3) = 26
-// jobs (FastTD3: 3 + 2 * 3 + 2 * (3 + 2) = 19).  mpo.hip registers its two matrices through net_images directly.
+// jobs no longer fit: that layer and everything after it run on the exact engine.  No descriptor fastsac.hip and fasttd3.hip
+// accept gets there -- the largest is FastSAC's critic update with four hidden layers: 4 + 2 * 4 + 2 * (4 + 3) = 26
+// jobs (FastTD3: 3 + 2 * 3 + 2 * (3 + 2) = 19).  tqc.hip does, from six critics with three hidden layers on (policy 5, E online
+// critics 5 each, E targets 3 each): it lists the nets in the order of their use.  mpo.hip registers its two matrices through
+// net_images directly.
 struct NetRef { const float* p; const Chain* L; bool bwd; };
 static inline int trunk_images(rlx_ctx* ctx, const NetRef* nets, int n, int64_t M, hipStream_t st) {
   BxMat mats[BX_MAX_JOBS];

@@ -69,6 +69,14 @@ class FastTd3Hparams(Structure):
         ("nr_atoms", c_int32), ("clipped_double_q", c_int32)]
 
 
+class TqcHparams(Structure):
+    """rlx_tqc_hparams (tqc/flax/default_config.py:9-28)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "tau", "target_entropy", "log_std_min", "log_std_max", "lr_policy", "lr_critic",
+                                       "lr_alpha", "adam_b1", "adam_b2", "adam_eps", "huber_kappa")] + [
+        ("ensemble_size", c_int32), ("nr_atoms_per_net", c_int32), ("nr_dropped_atoms_per_net", c_int32),
+        ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
+
+
 class ReppoDesc(Structure):
     """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
     _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
@@ -235,6 +243,9 @@ _SIGNATURES = {
                                           c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rlx_sac_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                            + [c_int64, _U32P, c_int, _I64P, _SACHPP, c_void_p, c_void_p]),
+    "rlx_tqc_quantile_loss_f32": (c_int, [c_void_p] * 7 + [c_int64, POINTER(TqcHparams), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rlx_tqc_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
+                           + [c_int64, _U32P, c_int, _I64P, POINTER(TqcHparams), c_void_p, c_void_p]),
     "rlx_lstm_policy_param_count": (c_int64, [_LDESCP]),
     "rlx_ppo_lstm_rollout_begin": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p]),
     "rlx_ppo_lstm_act_f32": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int,
@@ -769,6 +780,28 @@ class Ctx:
             _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
             *[_ptr(x, f, allow_none=i < 2) for i, x in enumerate(batch)], B, k, scheme, ctypes.byref(cnt), ctypes.byref(hp),
             _ptr(metrics_out, f), _stream()), "rlx_sac_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    # ---- TQC
+    def tqc_quantile_loss(self, q_atoms, next_atoms, rewards, terminations, next_logp, log_alpha, hp, dq_out, loss_out, y_out=None):
+        """TQC's critic loss on given atoms (include/rlx_hip.h): q_atoms / next_atoms / dq_out [E, B, N]; y_out None or [B, K]."""
+        f = self.torch.float32
+        _check(self.lib.rlx_tqc_quantile_loss_f32(self.h, _ptr(q_atoms, f, True), _ptr(next_atoms, f, True), _ptr(rewards, f),
+                                                  _ptr(terminations, f), _ptr(next_logp, f), _ptr(log_alpha, f), int(rewards.shape[0]),
+                                                  ctypes.byref(hp), _ptr(dq_out, f, True), _ptr(loss_out, f, True), _ptr(y_out, f, True),
+                                                  _stream()), "rlx_tqc_quantile_loss_f32")
+
+    def tqc_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, opt_count, hp,
+                   metrics_out, scheme=THREEFRY_PARTITIONABLE):
+        """batch = (states, next_states, actions, rewards, terminations).  Returns (new_key, new_opt_count)."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        cnt = c_int64(int(opt_count))
+        _check(self.lib.rlx_tqc_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
+            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
+            *[_ptr(x, f) for x in batch], int(batch[2].shape[0]), k, scheme, ctypes.byref(cnt), ctypes.byref(hp),
+            _ptr(metrics_out, f), _stream()), "rlx_tqc_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
 
     # ---- PPO + LSTM
