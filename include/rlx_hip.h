@@ -779,6 +779,58 @@ int rlx_tqc_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, floa
                        uint32_t key_io[2], int scheme, int64_t* opt_count_io, const rlx_tqc_hparams* hp,
                        float* metrics_out, void* stream);
 
+/* ---- REDQ: randomized ensembled double Q-learning (rl_x/algorithms/redq/flax) -------------------------------------------------
+ * SAC's policy, entropy coefficient, acting and replay ring (redq/flax/policy.py is sac/flax's) with ensemble_size scalar critics
+ * (critic.py:17-53: Dense(H) -> ReLU -> Dense(H) -> ReLU -> Dense(1), BACK TO BACK in one flat vector like rlx_tqc_update_f32's) and
+ * a high update-to-data `update` (redq.py:144-261): G = q_update_steps critic steps on G fresh batches, each followed by plain
+ * Adam of all critics and Polyak (:228-242), then ONE policy / entropy step on batch 0 with the critics from after the loop
+ * (:246-253).  Networks: rlx_mlp_desc with act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0; FLAT LAYOUT of a network: FastTD3's
+ * (above).  Q values are laid out [E, B], critic-major.  Envelope: 1..3 hidden layers, widths multiples of 64 up to 1024, act_dim
+ * <= 64, qdesc->out_dim = 1, 1 <= ensemble_size <= 16, 1 <= in_target_minimization_size <= ensemble_size, 1 <= q_update_steps <=
+ * 64, B > 0; a descriptor or size outside it is RLX_EUNSUP, every other bad argument RLX_EINVAL, rlx_last_error() names it.     */
+typedef struct rlx_redq_hparams {              /* redq/flax/default_config.py:9-27 */
+  float gamma, tau, target_entropy, log_std_min, log_std_max;
+  float lr_policy, lr_critic, lr_critic_delta, lr_alpha;   /* host evaluates the schedules (redq.py:82-98); critic step i of the
+                                                            * call runs at lr_critic + i * lr_critic_delta: q_linear_schedule is
+                                                            * linear in the critic step count (:82-86) */
+  float adam_b1, adam_b2, adam_eps;            /* optax.adam defaults 0.9, 0.999, 1e-8 (redq.py:110,117,123) */
+  int32_t ensemble_size, in_target_minimization_size, q_update_steps;   /* redq.py:51-53 */
+  const float *critic_states, *critic_next_states;   /* [G, B, Oc]: the critics' own observation columns (critic.py:11,23) of
+                                                      * s / s', or NULL both (the policy's) */
+} rlx_redq_hparams;
+
+/* host only, no context: the target subset REDQ draws from sample_key (redq.py:232-233): jax.random.choice(sample_key, arange(E),
+ * (M,), replace=False) = permutation(sample_key, E)[:M], i.e. ceil(3 ln E / ln(2^32 - 1)) rounds of {key, sub = split(key); stable
+ * sort by random_bits(sub, (E,))}: one round for 2 <= E <= 16, none (the identity) for E = 1.  1 <= M <= E <= 16. */
+int rlx_redq_subset_host(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out /*[M]*/);
+
+/* the two loss heads on given values; any output may be NULL except the one its inputs serve (dq_out; seed_out when qa is given).
+ * Critic (redq.py:163-169, meaned over batch and ensemble, :219): y_out [B] = r + gamma (1 - term) (min over the M rows of
+ * q_next_sel - exp(log_alpha) next_logp); dq_out [E, B] = 2 (q - y) / (B E); loss_out DEVICE [1] = mean (q - y)^2.
+ * Policy (redq.py:195-198), qa != NULL: minq_out [B] = min over ALL E rows of qa; seed_out [E, B] = d mean(-min) / d qa =
+ * -[qa == min] / (B n_ties): jnp.min's gradient, split evenly among exact ties. */
+int rlx_redq_losses_f32(rlx_ctx*, const float* q /*[E,B]*/, const float* q_next_sel /*[M,B]*/, const float* rewards,
+                        const float* terminations, const float* next_logp, const float* log_alpha, const float* qa /*[E,B] or NULL*/,
+                        int64_t B, const rlx_redq_hparams* hp, float* y_out, float* dq_out, float* loss_out,
+                        float* seed_out /*[E,B]*/, float* minq_out /*[B]*/, void* stream);
+
+/* the whole jitted `update` (redq.py:144-261) in one call on one stream, no host synchronisation.  Critic step i: keys =
+ * split(key, B + 2), key = keys[0], sample_key = keys[1] (the step's target subset), row b's next-action noise from keys[2 + b]
+ * (:229-236); policy step: keys = split(key, B + 1), key = keys[0], row b's noise from keys[1 + b] (:247-250).
+ * rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) draws instead: eps_next [G, B, A], eps_cur [B, A].
+ * states / next_states [G, B, pdesc->in_dim], actions [G, B, A], rewards / terminations [G, B]; the policy step reads batch 0.
+ * qparams / qm / qv / qtarget: [E * nq].  q_opt_count_io / pi_opt_count_io (HOST): the two optax counters (:107-124), advanced by
+ * G and by 1; critic step i is Adam step q_count + i + 1.  metrics_out DEVICE float[10] in rlx_sac_update_f32's order: [0] q_loss
+ * and [7] critic_grad_norm are the means over the G steps (:244), [5] q_value the mean of the min over all E critics, [9] = 0.
+ * subsets_out: NULL or HOST int32 [G, M], the target networks each step selected.  Nothing is written when a check fails. */
+int rlx_redq_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv,
+                        const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qtarget,
+                        float* log_alpha, float* am, float* av, const float* states /*[G,B,O]*/, const float* next_states,
+                        const float* actions, const float* rewards /*[G,B]*/, const float* terminations, int64_t B,
+                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io /* += G */, int64_t* pi_opt_count_io /* += 1 */,
+                        const rlx_redq_hparams* hp, float* metrics_out /*DEVICE [10]*/, int32_t* subsets_out /*HOST [G,M] or NULL*/,
+                        void* stream);
+
 /* =================================== REPPO ===============================================
  * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
  * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust

@@ -1,0 +1,492 @@
+// redq.hip -- REDQ, randomized ensembled double Q-learning (rl_x/algorithms/redq/flax/redq.py:144-261): SAC's tanh-Gaussian policy
+// and entropy coefficient with an ensemble of E scalar critics (redq/flax/critic.py:17-53) and a HIGH update-to-data `update`:
+// G = q_update_steps critic steps on G fresh batches, then ONE policy / entropy step.  What differs from sac.hip and tqc.hip:
+//   keys        critic step i: keys = split(key, B + 2), key = keys[0], sample_key = keys[1], row b's noise key keys[2 + b]
+//               (redq.py:229-230); policy step: keys = split(key, B + 1), key = keys[0], row b's keys[1 + b] (:247-248)
+//   target      m_indices = choice(sample_key, arange(E), (M,), replace=False) (:232-233) = permutation(sample_key, E)[:M]: one
+//               sort round for 2 <= E <= 16, none for E = 1; y = r + gamma (1 - term) (min over the M SELECTED targets - alpha logp')
+//   critic loss mean over batch AND ensemble of (q_e - y)^2 (:169, safe_mean at :219): d loss / d q[e, b] = 2 (q[e, b] - y_b) / (B E)
+//   loop        every critic step is followed by plain Adam on all E critics and Polyak (:238-239); step i + 1 sees the new
+//               parameters and targets; policy and alpha are untouched inside the loop; q_loss and critic_grad_norm are the means
+//               over the G steps (:244)
+//   policy loss alpha logp - min over ALL E critics (:195-198): the gradient goes to the minimising critic, split evenly among
+//               exact ties as jnp.min's gradient does
+//   counters    two: the critics' Adam counter advances by G per call, the policy's / alpha's by 1
+//
+// Networks: rlx_mlp_desc as tqc.hip takes them (ReLU, no LayerNorm; policy out_dim = 2 A; critics: E networks back to back, each
+// in_dim = Oc + A, out_dim = 1).  Q values are laid out [E][B], critic-major, as E head GEMMs with one output leave them.  A network
+// is net_pass.h's Chain; passes of >= 4096 rows take the split-operand images (trunk_images), which are REBUILT in front of every
+// critic step from the current parameters: the policy (forward), the M selected targets, the E online critics (both directions), in
+// the order of their use; what does not fit the image builder's job table runs on the exact engine (net_pass.h).  The image builder
+// registers one list per launch, so the policy's two forward images are part of every step's list.
+//
+// Schedule of one call (one stream, no host synchronisation): the key chain and the G subsets on the host; per critic step: policy
+// on s'_i -> k_redq_sample -> M target chains -> E online chains on (s_i, a_i) -> k_redq_critic_loss -> k_redq_mean (slot i) -> E
+// backward passes -> Adam + Polyak of all critics (norm to slot i); then the policy step: policy on s_0 -> k_redq_sample -> E
+// forward passes on (s_0, a~) into E kept buffer sets -> k_redq_policy_seed -> E input-gradient passes on the action columns ->
+// k_redq_policy_grad -> policy backward -> k_redq_finish (metrics, alpha's Adam step) -> Adam of the policy.
+// Every reduction runs in a fixed order without atomics: two identical calls give identical bits.
+// CPU twin: tests/redq_twin.py (float64).  The reference's REDQ is JAX only; see DESIGN.md 4.5e for what is pinned.
+#include "net_pass.h"
+#include "sac_sample.h"
+
+namespace rlx {
+
+constexpr int REDQ_MAXE = 16;
+constexpr int REDQ_MAXG = 64;
+
+// ---------------------------------------------------------------------------------------------------------------- kernels
+// tanh-Gaussian sample from the policy's head output [B, 2A] (sac_sample.h's per-row noise form): row i draws from
+// split(key, count)[base + i].  One thread per (row, action dim); a row's log-prob terms meet in LDS and one lane adds them in
+// index order.  Dynamic LDS: (256 / AP) A floats.
+__global__ __launch_bounds__(256) void k_redq_sample(const float* __restrict__ head, SacSampleArgs sa, int64_t B, int AP, uint32_t base,
+                                                     uint32_t count) {
+  extern __shared__ float s_term[];
+  const int A = sa.A;
+  const int rpb = 256 / AP;
+  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
+  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
+  if (i < B) {
+    uint32_t s0, s1;
+    split_key_at(sa.k0, sa.k1, base + (uint32_t)i, count, sa.scheme, s0, s1);
+    for (int j = jl; j < A; j += AP) s_term[rl * A + j] = sac_sample_elem(sa, s0, s1, i, j, head[i * 2 * A + j], head[i * 2 * A + A + j]);
+  }
+  __syncthreads();
+  if (i < B && jl == 0) {
+    float lp = 0.f;
+    for (int j = 0; j < A; ++j) lp += s_term[rl * A + j];
+    sa.logp[i] = lp;
+  }
+}
+
+// One thread per transition (redq.py:163-169): y_b = r_b + gamma (1 - term_b) (min_m qn[m, b] - alpha logp'_b) over the M selected
+// target rows; dq[e, b] = 2 (q[e, b] - y_b) / (B E); loss_row[b] = mean_e (q[e, b] - y_b)^2.  y / loss_row may be NULL.
+__global__ __launch_bounds__(256) void k_redq_critic_loss(const float* __restrict__ q, const float* __restrict__ qn, const float* __restrict__ rew,
+                                                          const float* __restrict__ term, const float* __restrict__ nlogp,
+                                                          const float* __restrict__ log_alpha, float* __restrict__ y, float* __restrict__ dq,
+                                                          float* __restrict__ loss_row, int64_t B, int E, int M, float gamma) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float mn = qn[b];
+  for (int m = 1; m < M; ++m) mn = fminf(mn, qn[(int64_t)m * B + b]);
+  const float yb = rew[b] + gamma * (1.0f - term[b]) * (mn - expf(log_alpha[0]) * nlogp[b]);
+  if (y) y[b] = yb;
+  const float gs = 2.0f / ((float)B * (float)E);
+  float loss = 0.f;
+  for (int e = 0; e < E; ++e) {
+    const float d = q[(int64_t)e * B + b] - yb;
+    dq[(int64_t)e * B + b] = gs * d;
+    loss = fmaf(d, d, loss);
+  }
+  if (loss_row) loss_row[b] = loss / (float)E;
+}
+
+// sum of v[0 .. n) over one workgroup: double accumulators, fixed order, no atomics
+__device__ __forceinline__ double redq_block_sum(const float* __restrict__ v, int64_t n, double* s_buf) {
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)v[i];
+  s_buf[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_buf[threadIdx.x] += s_buf[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = s_buf[0];
+  __syncthreads();
+  return r;
+}
+__global__ __launch_bounds__(256) void k_redq_mean(const float* __restrict__ v, int64_t n, float* __restrict__ out) {
+  __shared__ double s_buf[256];
+  const double s = redq_block_sum(v, n, s_buf);
+  if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
+}
+
+// One thread per transition (redq.py:195-198): minq_row[b] = min_e qa[e, b]; seed[e, b] = d mean_b(-min_e) / d qa[e, b] =
+// -[qa[e, b] == min] / (B n_ties), the even split jnp.min's gradient takes among exact ties.  minq_row may be NULL.
+__global__ __launch_bounds__(256) void k_redq_policy_seed(const float* __restrict__ qa, float* __restrict__ seed, float* __restrict__ minq_row,
+                                                          int64_t B, int E) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float mn = qa[b];
+  for (int e = 1; e < E; ++e) mn = fminf(mn, qa[(int64_t)e * B + b]);
+  int ties = 0;
+  for (int e = 0; e < E; ++e) ties += qa[(int64_t)e * B + b] == mn ? 1 : 0;
+  const float s = -1.0f / ((float)B * (float)(ties > 0 ? ties : 1));
+  for (int e = 0; e < E; ++e) seed[(int64_t)e * B + b] = qa[(int64_t)e * B + b] == mn ? s : 0.f;
+  if (minq_row) minq_row[b] = mn;
+}
+
+// d L / d(head output) of the policy (redq.py:183-198), k_tqc_policy_grad's arithmetic with the policy step's keys
+// (split(key, B + 1)[1 + i]).  da: E buffers of [B, ld_da], e_stride floats apart, action columns at col_off; each carries its
+// critic's seed (zero where the critic is not the row's minimum), so their sum is d(-min Q)/da / B:
+//   d_u = (alpha / B * 2a / (1 - a^2 + 1e-6) + sum_e da_e) (1 - a^2);  d_mean = d_u;
+//   d_logstd = [raw inside the clip] (d_u std eps - alpha / B)
+__global__ __launch_bounds__(256) void k_redq_policy_grad(const float* __restrict__ head, const float* __restrict__ xp, int ld, int col_off,
+                                                          const float* __restrict__ da, int ld_da, int64_t e_stride, int E,
+                                                          const float* __restrict__ log_alpha, uint32_t k0, uint32_t k1, int scheme,
+                                                          float* __restrict__ d_out, int64_t B, int A, int AP, float ls_min, float ls_max,
+                                                          const float* __restrict__ eps_inject) {
+  const int rpb = 256 / AP;
+  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
+  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
+  if (i >= B) return;
+  const float alpha = expf(log_alpha[0]);
+  uint32_t s0, s1;
+  split_key_at(k0, k1, 1u + (uint32_t)i, (uint32_t)(B + 1), scheme, s0, s1);
+  const float invB = 1.0f / (float)B;
+  for (int j = jl; j < A; j += AP) {
+    const float raw = head[i * 2 * A + A + j];
+    const float ls = fminf(fmaxf(raw, ls_min), ls_max);
+    const float eps = eps_inject ? eps_inject[i * A + j] : normal_from_bits(random_bits_at(s0, s1, (uint64_t)j, (uint64_t)A, scheme));
+    const float a = xp[i * ld + col_off + j];
+    const float om = 1.0f - a * a;
+    float dqa = 0.f;
+    for (int e = 0; e < E; ++e) dqa += da[e * e_stride + i * ld_da + col_off + j];
+    const float du = (alpha * invB * 2.0f * a / (om + 1e-6f) + dqa) * om;
+    d_out[i * 2 * A + j] = du;
+    const bool inside = raw > ls_min && raw < ls_max;
+    d_out[i * 2 * A + A + j] = inside ? du * expf(ls) * eps - alpha * invB : 0.f;
+  }
+}
+
+// metrics (rlx_sac_update_f32's order), the means over the G critic steps (redq.py:244; steps: [G] q_loss then [G] grad norm, added
+// in index order) and the entropy coefficient's gradient with its plain Adam step at the POLICY counter (redq.py:201, :253; the
+// arithmetic of adam_body.h's adam_element without clipping).  minq_row: per row the min over the E critics on (s, a~); lpc: logp.
+__global__ __launch_bounds__(256) void k_redq_finish(const float* __restrict__ minq_row, const float* __restrict__ lpc, int64_t B,
+                                                     const float* __restrict__ steps, int G, float* __restrict__ log_alpha,
+                                                     float* __restrict__ am, float* __restrict__ av, float* __restrict__ metrics,
+                                                     float target_entropy, float lr, float bc1, float bc2, float b1, float b2, float eps) {
+  __shared__ double s_buf[256];
+  const double sq = redq_block_sum(minq_row, B, s_buf);
+  const double sl = redq_block_sum(lpc, B, s_buf);
+  if (threadIdx.x != 0) return;
+  double ql = 0.0, gn = 0.0;
+  for (int i = 0; i < G; ++i) {
+    ql += (double)steps[i];
+    gn += (double)steps[G + i];
+  }
+  const float mean_q = (float)(sq / (double)B), mean_lp = (float)(sl / (double)B);
+  const float la = log_alpha[0];
+  const float alpha = expf(la);
+  const float entropy = -mean_lp;
+  const float ga = alpha * (entropy - target_entropy);      // d mean(alpha_g (entropy - target)) / d log_alpha
+  metrics[0] = (float)(ql / (double)G);                     // loss/q_loss: mean over the G steps
+  metrics[1] = alpha * mean_lp - mean_q;                    // loss/policy_loss
+  metrics[2] = ga;                                          // loss/entropy_loss
+  metrics[3] = entropy;                                     // entropy/entropy
+  metrics[4] = alpha;                                       // entropy/alpha
+  metrics[5] = mean_q;                                      // q_value/q_value: mean of the min over all E critics (redq.py:196)
+  metrics[7] = (float)(gn / (double)G);                     // gradients/critic_grad_norm: mean over the G steps
+  metrics[8] = sqrtf(ga * ga);                              // gradients/entropy_grad_norm
+  metrics[9] = 0.f;
+  const float mi = fmaf(b1, am[0], (1.f - b1) * ga);
+  const float vi = fmaf(b2, av[0], ((1.f - b2) * ga) * ga);
+  am[0] = mi;
+  av[0] = vi;
+  log_alpha[0] = fmaf(-lr, (mi / bc1) / (sqrtf(vi / bc2) + eps), la);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+static int redq_check_net(const rlx_mlp_desc& d, const char* which) {   // tqc.hip's descriptor rules
+  char msg[160];
+  snprintf(msg, sizeof msg, "redq: %s needs 1..3 hidden layers and positive widths", which);
+  RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL, msg);
+  snprintf(msg, sizeof msg, "redq: %s must be act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0", which);
+  RLX_REQUIRE(d.act == RLX_ACT_RELU && !d.ln_first && !d.has_logstd, RLX_EINVAL, msg);
+  snprintf(msg, sizeof msg, "redq: %s hidden widths must be multiples of 64, at most 1024", which);
+  for (int l = 0; l < d.n_hidden; ++l) RLX_REQUIRE(d.hidden[l] > 0 && d.hidden[l] % 64 == 0 && d.hidden[l] <= 1024, RLX_EUNSUP, msg);
+  return RLX_OK;
+}
+
+// ensemble_size E, in_target_minimization_size M, q_update_steps G (redq/flax/default_config.py:18-20)
+static int redq_check_hp(const rlx_redq_hparams& hp) {
+  RLX_REQUIRE(hp.ensemble_size >= 1, RLX_EINVAL, "redq: hp->ensemble_size must be at least 1");
+  RLX_REQUIRE(hp.ensemble_size <= REDQ_MAXE, RLX_EUNSUP, "redq: hp->ensemble_size at most 16");
+  RLX_REQUIRE(hp.in_target_minimization_size >= 1 && hp.in_target_minimization_size <= hp.ensemble_size, RLX_EINVAL,
+              "redq: hp->in_target_minimization_size must be in [1, ensemble_size]");
+  RLX_REQUIRE(hp.q_update_steps >= 1, RLX_EINVAL, "redq: hp->q_update_steps must be at least 1");
+  RLX_REQUIRE(hp.q_update_steps <= REDQ_MAXG, RLX_EUNSUP, "redq: hp->q_update_steps at most 64");
+  return RLX_OK;
+}
+
+static Chain redq_layout(const rlx_mlp_desc& d) { return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_NONE, RLX_ACT_RELU); }
+
+static inline int redq_lanes_per_row(int A) {
+  int ap = 1;
+  while (ap < A && ap < 64) ap <<= 1;
+  return ap;
+}
+
+// jax.random.split(key, num)[i] on the host (sac_sample.h's split_key_at is the device's)
+static inline void redq_split_at(const uint32_t key[2], uint32_t i, uint32_t num, int scheme, uint32_t out[2]) {
+  if (scheme == RLX_THREEFRY_PARTITIONABLE) {
+    uint32_t x0 = 0, x1 = i;
+    threefry2x32(key[0], key[1], x0, x1);
+    out[0] = x0;
+    out[1] = x1;
+  } else {
+    out[0] = random_bits_at(key[0], key[1], 2ull * i, 2ull * num, RLX_THREEFRY_LEGACY);
+    out[1] = random_bits_at(key[0], key[1], 2ull * i + 1, 2ull * num, RLX_THREEFRY_LEGACY);
+  }
+}
+
+// permutation(sample_key, E)[:M] (jax _shuffle): ceil(3 ln E / ln(2^32 - 1)) rounds of {key, sub = split(key); stable sort by
+// random_bits(sub, (E,))} -- one round for 2 <= E <= 16, none for E = 1
+static void redq_subset(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out) {
+  uint32_t key[2] = {sample_key[0], sample_key[1]};
+  int32_t idx[REDQ_MAXE];
+  for (int e = 0; e < E; ++e) idx[e] = e;
+  const int rounds = (int)ceil(3.0 * log((double)E) / log(4294967295.0));
+  for (int r = 0; r < rounds; ++r) {
+    uint32_t sub[2], nxt[2];
+    redq_split_at(key, 0, 2, scheme, nxt);
+    redq_split_at(key, 1, 2, scheme, sub);
+    key[0] = nxt[0];
+    key[1] = nxt[1];
+    uint32_t bits[REDQ_MAXE];
+    for (int e = 0; e < E; ++e) bits[e] = random_bits_at(sub[0], sub[1], (uint64_t)e, (uint64_t)E, scheme);
+    for (int a = 1; a < E; ++a) {   // insertion sort: stable
+      const uint32_t kb = bits[a];
+      const int32_t ki = idx[a];
+      int c = a - 1;
+      for (; c >= 0 && bits[c] > kb; --c) {
+        bits[c + 1] = bits[c];
+        idx[c + 1] = idx[c];
+      }
+      bits[c + 1] = kb;
+      idx[c + 1] = ki;
+    }
+  }
+  for (int m = 0; m < M; ++m) idx_out[m] = idx[m];
+}
+
+static int redq_critic_loss(const float* q, const float* qn, const float* rew, const float* term, const float* nlogp, const float* log_alpha,
+                            int64_t B, int E, int M, float gamma, float* y, float* dq, float* loss_row, float* loss_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_redq_critic_loss, dim3(div_up(B, 256)), dim3(256), 0, st, q, qn, rew, term, nlogp, log_alpha, y, dq, loss_row, B, E, M,
+                     gamma);
+  RLX_LAUNCH_CHECK();
+  if (loss_out) {
+    hipLaunchKernelGGL(k_redq_mean, dim3(1), dim3(256), 0, st, (const float*)loss_row, B, loss_out);
+    RLX_LAUNCH_CHECK();
+  }
+  return RLX_OK;
+}
+
+struct RedqAdamHp { float max_grad_norm, adam_b1, adam_b2, adam_eps; };   // what torch_clip_adam reads; max_grad_norm <= 0: plain Adam
+
+}  // namespace rlx
+
+using namespace rlx;
+
+extern "C" {
+
+int rlx_redq_subset_host(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out) {
+  RLX_REQUIRE(sample_key && idx_out, RLX_EINVAL, "rlx_redq_subset_host: NULL pointer");
+  RLX_REQUIRE(E >= 1 && E <= REDQ_MAXE, RLX_EINVAL, "rlx_redq_subset_host: E must be in [1, 16]");
+  RLX_REQUIRE(M >= 1 && M <= E, RLX_EINVAL, "rlx_redq_subset_host: M must be in [1, E]");
+  redq_subset(sample_key, E, M, scheme, idx_out);
+  return RLX_OK;
+}
+
+int rlx_redq_losses_f32(rlx_ctx* ctx, const float* q, const float* q_next_sel, const float* rewards, const float* terminations,
+                        const float* next_logp, const float* log_alpha, const float* qa, int64_t B, const rlx_redq_hparams* hp, float* y_out,
+                        float* dq_out, float* loss_out, float* seed_out, float* minq_out, void* stream) {
+  RLX_REQUIRE(ctx && hp, RLX_EINVAL, "rlx_redq_losses_f32: ctx / hp is NULL");
+  RLX_REQUIRE(q && q_next_sel && rewards && terminations && next_logp && log_alpha, RLX_EINVAL,
+              "rlx_redq_losses_f32: NULL input (q, q_next_sel, rewards, terminations, next_logp, log_alpha)");
+  RLX_REQUIRE(dq_out, RLX_EINVAL, "rlx_redq_losses_f32: dq_out is NULL");
+  RLX_REQUIRE(!qa || seed_out, RLX_EINVAL, "rlx_redq_losses_f32: qa needs seed_out");
+  RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_losses_f32: B must be positive");
+  const int rc = redq_check_hp(*hp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* loss_row = nullptr;
+  if (loss_out) {
+    loss_row = (float*)scratch(ctx, SL_STAGE, a64((size_t)B) * sizeof(float));
+    if (!loss_row) return RLX_ENOMEM;
+  }
+  const int E = hp->ensemble_size, M = hp->in_target_minimization_size;
+  const int rc2 = redq_critic_loss(q, q_next_sel, rewards, terminations, next_logp, log_alpha, B, E, M, hp->gamma, y_out, dq_out, loss_row,
+                                   loss_out, st);
+  if (rc2 || !qa) return rc2;
+  hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, qa, seed_out, minq_out, B, E);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* qdesc,
+                        float* qparams, float* qm, float* qv, float* qtarget, float* log_alpha, float* am, float* av, const float* states,
+                        const float* next_states, const float* actions, const float* rewards, const float* terminations, int64_t B,
+                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_redq_hparams* hp,
+                        float* metrics_out, int32_t* subsets_out, void* stream) {
+  RLX_REQUIRE(ctx && pdesc && pparams && pm && pv && qdesc && qparams && qm && qv && qtarget && log_alpha && am && av && states &&
+                  next_states && actions && rewards && terminations && key_io && q_opt_count_io && pi_opt_count_io && hp && metrics_out,
+              RLX_EINVAL, "rlx_redq_update_f32: NULL pointer");
+  RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_update_f32: B must be positive");
+  RLX_REQUIRE(B + 2 <= 0x7fffffffLL, RLX_EUNSUP, "rlx_redq_update_f32: B too large for the 32-bit key count B + 2");
+  int rc = redq_check_net(*pdesc, "pdesc");
+  if (rc) return rc;
+  rc = redq_check_net(*qdesc, "qdesc");
+  if (rc) return rc;
+  rc = redq_check_hp(*hp);
+  if (rc) return rc;
+  RLX_REQUIRE(pdesc->out_dim % 2 == 0, RLX_EINVAL, "rlx_redq_update_f32: pdesc->out_dim must be 2 * act_dim");
+  const int A = pdesc->out_dim / 2, E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps;
+  RLX_REQUIRE(A <= 64, RLX_EUNSUP, "rlx_redq_update_f32: act_dim (pdesc->out_dim / 2) at most 64");
+  RLX_REQUIRE(qdesc->out_dim == 1, RLX_EINVAL, "rlx_redq_update_f32: qdesc->out_dim must be 1");
+  RLX_REQUIRE(qdesc->in_dim > A, RLX_EINVAL, "rlx_redq_update_f32: qdesc->in_dim must be critic obs + act_dim");
+  const int Op = pdesc->in_dim, Oc = qdesc->in_dim - A;
+  const bool asym = hp->critic_states != nullptr;
+  RLX_REQUIRE((hp->critic_states != nullptr) == (hp->critic_next_states != nullptr) && (asym || Oc == Op), RLX_EINVAL,
+              "rlx_redq_update_f32: critic obs width != policy obs width needs hp->critic_states AND hp->critic_next_states");
+  const float* cs = asym ? hp->critic_states : states;
+  const float* cn = asym ? hp->critic_next_states : next_states;
+  hipStream_t st = (hipStream_t)stream;
+  bx_release_all(ctx);
+  const Chain LP = redq_layout(*pdesc), LQ = redq_layout(*qdesc);
+  const int64_t np_ = LP.n_params, nq = LQ.n_params;
+  const int ldc = (Oc + A + 3) & ~3, ldp = (Op + 3) & ~3;
+  const int AP = redq_lanes_per_row(A);
+  const int nb_rc = div_up(B, 256 / AP), nb_row = div_up(B, 256);
+  const size_t lds_rc = (size_t)(256 / AP) * A * sizeof(float);
+  // ---- arena: the policy's passes, one buffer set for the targets' inference passes, E sets for the online critics: their backward
+  // waits for the loss in a critic step and for the seed -- which needs all E values -- in the policy step
+  ChainBufs bpn, bpc, bi, bq[REDQ_MAXE];
+  float *xc, *xn, *xp, *xsn, *xsc, *hn, *hc, *dpi, *lpn, *lpc, *qn, *q, *dq, *qa, *seed, *da, *y, *loss_row, *minq_row, *gp, *gq, *steps;
+  rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
+    chain_carve(LP, B, a, &bpn);
+    chain_carve(LP, B, a, &bpc);
+    chain_carve(LQ, B, a, &bi);
+    for (int e = 0; e < E; ++e) chain_carve(LQ, B, a, &bq[e]);
+    for (float** x : {&xc, &xn, &xp}) *x = a.take((size_t)B * ldc);
+    for (float** x : {&xsn, &xsc}) *x = a.take((size_t)B * ldp);
+    for (float** x : {&hn, &hc, &dpi}) *x = a.take((size_t)B * 2 * A);
+    for (float** x : {&lpn, &lpc, &loss_row, &minq_row, &y}) *x = a.take(B);
+    qn = a.take((size_t)M * B);
+    for (float** x : {&q, &dq, &qa, &seed}) *x = a.take((size_t)E * B);
+    da = a.take((size_t)E * B * ldc);
+    gp = a.take(np_);
+    gq = a.take((size_t)E * nq);
+    steps = a.take(2 * (size_t)G);
+  });
+  float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
+  if (rc || !sq) return RLX_ENOMEM;
+  // ---- the key chain (redq.py:229-230, :247-248) and the G target subsets (:232-233), all on the host
+  uint32_t step_key[REDQ_MAXG + 1][2];                        // the key each step splits
+  int32_t subset[REDQ_MAXG][REDQ_MAXE];
+  uint32_t key[2] = {key_io[0], key_io[1]};
+  for (int i = 0; i < G; ++i) {
+    uint32_t nxt[2], sample_key[2];
+    step_key[i][0] = key[0];
+    step_key[i][1] = key[1];
+    redq_split_at(key, 0, (uint32_t)(B + 2), scheme, nxt);
+    redq_split_at(key, 1, (uint32_t)(B + 2), scheme, sample_key);
+    redq_subset(sample_key, E, M, scheme, subset[i]);
+    key[0] = nxt[0];
+    key[1] = nxt[1];
+  }
+  step_key[G][0] = key[0];
+  step_key[G][1] = key[1];
+  redq_split_at(step_key[G], 0, (uint32_t)(B + 1), scheme, key);
+  BxReleaseAll bx_all{ctx};
+  SacSampleArgs sa;
+  sa.scheme = scheme; sa.mode = 1; sa.ld_out = ldc; sa.col_off = Oc; sa.A = A;
+  sa.ls_min = hp->log_std_min; sa.ls_max = hp->log_std_max; sa.N_global = B;
+  const RedqAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
+  // ---- G critic steps (redq.py:228-242)
+  for (int i = 0; i < G; ++i) {
+    const float* s2_i = next_states + (size_t)i * B * Op;
+    const float* cs_i = cs + (size_t)i * B * Oc;
+    const float* cn_i = cn + (size_t)i * B * Oc;
+    const float* a_i = actions + (size_t)i * B * A;
+    {  // the images of this step's passes, from the parameters as the previous step left them
+      NetRef nets[1 + 2 * REDQ_MAXE];
+      int n = 0;
+      nets[n++] = NetRef{pparams, &LP, false};
+      for (int m = 0; m < M; ++m) nets[n++] = NetRef{qtarget + subset[i][m] * nq, &LQ, false};
+      for (int e = 0; e < E; ++e) nets[n++] = NetRef{qparams + e * nq, &LQ, true};
+      bx_release_all(ctx);
+      rc = trunk_images(ctx, nets, n, B, st);
+      if (rc) return rc;
+    }
+    // a', logp' from the policy on s'; the M selected targets on (s', a'); the E online critics on (s, a)
+    rc = fs_concat(cn_i, Oc, nullptr, A, xn, ldc, B, st);
+    if (!rc) rc = fs_concat(s2_i, Op, nullptr, 0, xsn, ldp, B, st);
+    if (!rc) rc = chain_fwd(ctx, LP, pparams, xsn, ldp, bpn, hn, B, st);
+    if (rc) return rc;
+    sa.k0 = step_key[i][0]; sa.k1 = step_key[i][1]; sa.act_out = xn; sa.logp = lpn;
+    sa.eps_inject = ctx->dbg_sac_eps[0] ? ctx->dbg_sac_eps[0] + (size_t)i * B * A : nullptr;
+    hipLaunchKernelGGL(k_redq_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hn, sa, B, AP, 2u, (uint32_t)(B + 2));
+    RLX_LAUNCH_CHECK();
+    for (int m = 0; m < M && !rc; ++m) rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + (size_t)m * B, B, st);
+    if (!rc) rc = fs_concat(cs_i, Oc, a_i, A, xc, ldc, B, st);
+    for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + (size_t)e * B, B, st);
+    if (!rc) rc = redq_critic_loss(q, qn, rewards + (size_t)i * B, terminations + (size_t)i * B, lpn, log_alpha, B, E, M, hp->gamma, y, dq,
+                                   loss_row, steps + i, st);
+    // one deferred reduction per critic; the split-operand gradient scale is that of B E rows: |d loss / d q| is ~ 2 |q - y| / (B E)
+    for (int e = 0; e < E && !rc; ++e) {
+      BwdPass bwd(ctx, B * E);
+      rc = bwd.begin(chain_stage_floats(ctx, LQ, B, true));
+      if (!rc) rc = chain_bwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], dq + (size_t)e * B, gq + e * nq, nullptr, 0, B, st);
+      if (!rc) rc = bwd.finish(st);
+    }
+    // plain Adam of all E critics with the Polyak step (redq.py:238-239), at this step's learning rate and count
+    if (!rc) rc = torch_clip_adam(qparams, gq, qm, qv, (int64_t)E * nq, sq, *q_opt_count_io + i + 1, hp->lr_critic + (float)i * hp->lr_critic_delta,
+                                  ahp, steps + G + i, st, qtarget, hp->tau);
+    if (rc) return rc;
+  }
+  // ---- policy / entropy step (redq.py:246-253) on batch 0, with the critics from after the G steps
+  {
+    NetRef nets[1 + REDQ_MAXE];
+    int n = 0;
+    nets[n++] = NetRef{pparams, &LP, true};
+    for (int e = 0; e < E; ++e) nets[n++] = NetRef{qparams + e * nq, &LQ, true};
+    bx_release_all(ctx);
+    rc = trunk_images(ctx, nets, n, B, st);
+    if (rc) return rc;
+  }
+  rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
+  if (!rc) rc = fs_concat(states, Op, nullptr, 0, xsc, ldp, B, st);
+  if (!rc) rc = chain_fwd(ctx, LP, pparams, xsc, ldp, bpc, hc, B, st);
+  if (rc) return rc;
+  sa.k0 = step_key[G][0]; sa.k1 = step_key[G][1]; sa.act_out = xp; sa.logp = lpc; sa.eps_inject = ctx->dbg_sac_eps[1];
+  hipLaunchKernelGGL(k_redq_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hc, sa, B, AP, 1u, (uint32_t)(B + 1));
+  RLX_LAUNCH_CHECK();
+  for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + (size_t)e * B, B, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_redq_policy_seed, dim3(nb_row), dim3(256), 0, st, (const float*)qa, seed, minq_row, B, E);
+  RLX_LAUNCH_CHECK();
+  {
+    BwdPass bwd(ctx, B);   // the critics' seeds are 0 or -1 / (B n_ties); the policy's head gradient is ~ 1 / B per sample
+    rc = bwd.begin(E * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
+    for (int e = 0; e < E && !rc; ++e)
+      rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + (size_t)e * B, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_redq_policy_grad, dim3(nb_rc), dim3(256), 0, st, (const float*)hc, (const float*)xp, ldc, Oc, (const float*)da, ldc,
+                       (int64_t)B * ldc, E, (const float*)log_alpha, step_key[G][0], step_key[G][1], scheme, dpi, B, A, AP, hp->log_std_min,
+                       hp->log_std_max, ctx->dbg_sac_eps[1]);
+    RLX_LAUNCH_CHECK();
+    rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
+    if (!rc) rc = bwd.finish(st);
+    if (rc) return rc;
+  }
+  // ---- metrics, alpha's and the policy's plain Adam steps at the policy counter (redq.py:252-253)
+  const int64_t pstep = *pi_opt_count_io + 1;
+  float sched[3];
+  adam_schedule_entry(sched, pstep, hp->lr_alpha, hp->adam_b1, hp->adam_b2);
+  hipLaunchKernelGGL(k_redq_finish, dim3(1), dim3(256), 0, st, (const float*)minq_row, (const float*)lpc, B, (const float*)steps, G, log_alpha, am,
+                     av, metrics_out, hp->target_entropy, sched[0], sched[1], sched[2], hp->adam_b1, hp->adam_b2, hp->adam_eps);
+  RLX_LAUNCH_CHECK();
+  rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, pstep, hp->lr_policy, ahp, metrics_out + 6, st);
+  if (rc) return rc;
+  key_io[0] = key[0];
+  key_io[1] = key[1];
+  *q_opt_count_io += G;
+  *pi_opt_count_io += 1;
+  if (subsets_out)
+    for (int i = 0; i < G; ++i)
+      for (int m = 0; m < M; ++m) subsets_out[i * M + m] = subset[i][m];
+  return RLX_OK;
+}
+
+}  // extern "C"

@@ -77,6 +77,14 @@ class TqcHparams(Structure):
         ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
 
 
+class RedqHparams(Structure):
+    """rlx_redq_hparams (redq/flax/default_config.py:9-27)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "tau", "target_entropy", "log_std_min", "log_std_max", "lr_policy", "lr_critic",
+                                       "lr_critic_delta", "lr_alpha", "adam_b1", "adam_b2", "adam_eps")] + [
+        ("ensemble_size", c_int32), ("in_target_minimization_size", c_int32), ("q_update_steps", c_int32),
+        ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
+
+
 class ReppoDesc(Structure):
     """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
     _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
@@ -246,6 +254,10 @@ _SIGNATURES = {
     "rlx_tqc_quantile_loss_f32": (c_int, [c_void_p] * 7 + [c_int64, POINTER(TqcHparams), c_void_p, c_void_p, c_void_p, c_void_p]),
     "rlx_tqc_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                            + [c_int64, _U32P, c_int, _I64P, POINTER(TqcHparams), c_void_p, c_void_p]),
+    "rlx_redq_subset_host": (c_int, [_U32P, c_int, c_int, c_int, POINTER(c_int32)]),
+    "rlx_redq_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(RedqHparams)] + [c_void_p] * 6),
+    "rlx_redq_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
+                            + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(RedqHparams), c_void_p, POINTER(c_int32), c_void_p]),
     "rlx_lstm_policy_param_count": (c_int64, [_LDESCP]),
     "rlx_ppo_lstm_rollout_begin": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p]),
     "rlx_ppo_lstm_act_f32": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int,
@@ -395,6 +407,13 @@ def threefry_split(key, num=2, scheme=THREEFRY_PARTITIONABLE):
     out = (c_uint32 * (2 * num))()
     _check(lib.rlx_threefry_split_host(_key_arr(key), out, num, scheme), "rlx_threefry_split_host")
     return np.ctypeslib.as_array(out).reshape(num, 2).copy()
+
+
+def redq_subset(sample_key, E, M, scheme=THREEFRY_PARTITIONABLE):
+    """REDQ's target subset (redq.py:232-233) on the host: permutation(sample_key, E)[:M] -> np.int32[M]."""
+    out = (c_int32 * max(int(M), 1))()
+    _check(load_library().rlx_redq_subset_host(_key_arr(sample_key), int(E), int(M), scheme, out), "rlx_redq_subset_host")
+    return np.ctypeslib.as_array(out)[:int(M)].copy()
 
 
 def prng_key(seed):
@@ -803,6 +822,34 @@ class Ctx:
             *[_ptr(x, f) for x in batch], int(batch[2].shape[0]), k, scheme, ctypes.byref(cnt), ctypes.byref(hp),
             _ptr(metrics_out, f), _stream()), "rlx_tqc_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    # ---- REDQ
+    def redq_losses(self, q, q_next_sel, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out=None, loss_out=None, qa=None,
+                    seed_out=None, minq_out=None):
+        """REDQ's two loss heads on given values (include/rlx_hip.h): q / dq_out / qa / seed_out [E, B], q_next_sel [M, B]."""
+        f = self.torch.float32
+        _check(self.lib.rlx_redq_losses_f32(self.h, _ptr(q, f, True), _ptr(q_next_sel, f, True), _ptr(rewards, f), _ptr(terminations, f),
+                                            _ptr(next_logp, f), _ptr(log_alpha, f), _ptr(qa, f, True), int(rewards.shape[0]),
+                                            ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True), _ptr(loss_out, f, True),
+                                            _ptr(seed_out, f, True), _ptr(minq_out, f, True), _stream()), "rlx_redq_losses_f32")
+
+    def redq_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
+                    metrics_out, scheme=THREEFRY_PARTITIONABLE, subsets=False):
+        """batch = (states [G, B, O], next_states, actions [G, B, A], rewards [G, B], terminations), G = hp.q_update_steps.
+        Returns (new_key, new_q_count, new_pi_count), and the [G, M] target subsets behind them when subsets is true."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
+        G, M = max(int(hp.q_update_steps), 0), max(int(hp.in_target_minimization_size), 0)
+        sub = (c_int32 * max(G * M, 1))() if subsets else None
+        B = int(batch[3].numel()) // max(G, 1)
+        _check(self.lib.rlx_redq_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
+            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
+            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
+            _ptr(metrics_out, f), sub, _stream()), "rlx_redq_update_f32")
+        out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
+        return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
 
     # ---- PPO + LSTM
     def lstm_policy_param_count(self, desc):
