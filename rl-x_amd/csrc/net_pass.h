@@ -1,5 +1,5 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip and redq.hip on the host side: the launchers of
-// dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip and redq.hip (the last two through
+// sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
 // of blocks, the streams, and what differs in the graph (REPPO's critic).

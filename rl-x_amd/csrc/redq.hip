@@ -21,14 +21,14 @@
 // registers one list per launch, so the policy's two forward images are part of every step's list.
 //
 // Schedule of one call (one stream, no host synchronisation): the key chain and the G subsets on the host; per critic step: policy
-// on s'_i -> k_redq_sample -> M target chains -> E online chains on (s_i, a_i) -> k_redq_critic_loss -> k_redq_mean (slot i) -> E
-// backward passes -> Adam + Polyak of all critics (norm to slot i); then the policy step: policy on s_0 -> k_redq_sample -> E
+// on s'_i -> k_ens_sample -> M target chains -> E online chains on (s_i, a_i) -> k_redq_critic_loss -> k_ens_mean (slot i) -> E
+// backward passes -> Adam + Polyak of all critics (norm to slot i); then the policy step: policy on s_0 -> k_ens_sample -> E
 // forward passes on (s_0, a~) into E kept buffer sets -> k_redq_policy_seed -> E input-gradient passes on the action columns ->
-// k_redq_policy_grad -> policy backward -> k_redq_finish (metrics, alpha's Adam step) -> Adam of the policy.
+// k_ens_policy_grad -> policy backward -> k_ens_finish (metrics, the means over the G steps, alpha's Adam step at the POLICY
+// counter) -> Adam of the policy.  The k_ens_* kernels are sac_ens.hip's, shared with tqc.hip.
 // Every reduction runs in a fixed order without atomics: two identical calls give identical bits.
 // CPU twin: tests/redq_twin.py (float64).  The reference's REDQ is JAX only; see DESIGN.md 4.5e for what is pinned.
-#include "net_pass.h"
-#include "sac_sample.h"
+#include "sac_ens.h"
 
 namespace rlx {
 
@@ -36,29 +36,6 @@ constexpr int REDQ_MAXE = 16;
 constexpr int REDQ_MAXG = 64;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-// tanh-Gaussian sample from the policy's head output [B, 2A] (sac_sample.h's per-row noise form): row i draws from
-// split(key, count)[base + i].  One thread per (row, action dim); a row's log-prob terms meet in LDS and one lane adds them in
-// index order.  Dynamic LDS: (256 / AP) A floats.
-__global__ __launch_bounds__(256) void k_redq_sample(const float* __restrict__ head, SacSampleArgs sa, int64_t B, int AP, uint32_t base,
-                                                     uint32_t count) {
-  extern __shared__ float s_term[];
-  const int A = sa.A;
-  const int rpb = 256 / AP;
-  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
-  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
-  if (i < B) {
-    uint32_t s0, s1;
-    split_key_at(sa.k0, sa.k1, base + (uint32_t)i, count, sa.scheme, s0, s1);
-    for (int j = jl; j < A; j += AP) s_term[rl * A + j] = sac_sample_elem(sa, s0, s1, i, j, head[i * 2 * A + j], head[i * 2 * A + A + j]);
-  }
-  __syncthreads();
-  if (i < B && jl == 0) {
-    float lp = 0.f;
-    for (int j = 0; j < A; ++j) lp += s_term[rl * A + j];
-    sa.logp[i] = lp;
-  }
-}
-
 // One thread per transition (redq.py:163-169): y_b = r_b + gamma (1 - term_b) (min_m qn[m, b] - alpha logp'_b) over the M selected
 // target rows; dq[e, b] = 2 (q[e, b] - y_b) / (B E); loss_row[b] = mean_e (q[e, b] - y_b)^2.  y / loss_row may be NULL.
 __global__ __launch_bounds__(256) void k_redq_critic_loss(const float* __restrict__ q, const float* __restrict__ qn, const float* __restrict__ rew,
@@ -81,26 +58,6 @@ __global__ __launch_bounds__(256) void k_redq_critic_loss(const float* __restric
   if (loss_row) loss_row[b] = loss / (float)E;
 }
 
-// sum of v[0 .. n) over one workgroup: double accumulators, fixed order, no atomics
-__device__ __forceinline__ double redq_block_sum(const float* __restrict__ v, int64_t n, double* s_buf) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)v[i];
-  s_buf[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_buf[threadIdx.x] += s_buf[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = s_buf[0];
-  __syncthreads();
-  return r;
-}
-__global__ __launch_bounds__(256) void k_redq_mean(const float* __restrict__ v, int64_t n, float* __restrict__ out) {
-  __shared__ double s_buf[256];
-  const double s = redq_block_sum(v, n, s_buf);
-  if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
-}
-
 // One thread per transition (redq.py:195-198): minq_row[b] = min_e qa[e, b]; seed[e, b] = d mean_b(-min_e) / d qa[e, b] =
 // -[qa[e, b] == min] / (B n_ties), the even split jnp.min's gradient takes among exact ties.  minq_row may be NULL.
 __global__ __launch_bounds__(256) void k_redq_policy_seed(const float* __restrict__ qa, float* __restrict__ seed, float* __restrict__ minq_row,
@@ -116,88 +73,7 @@ __global__ __launch_bounds__(256) void k_redq_policy_seed(const float* __restric
   if (minq_row) minq_row[b] = mn;
 }
 
-// d L / d(head output) of the policy (redq.py:183-198), k_tqc_policy_grad's arithmetic with the policy step's keys
-// (split(key, B + 1)[1 + i]).  da: E buffers of [B, ld_da], e_stride floats apart, action columns at col_off; each carries its
-// critic's seed (zero where the critic is not the row's minimum), so their sum is d(-min Q)/da / B:
-//   d_u = (alpha / B * 2a / (1 - a^2 + 1e-6) + sum_e da_e) (1 - a^2);  d_mean = d_u;
-//   d_logstd = [raw inside the clip] (d_u std eps - alpha / B)
-__global__ __launch_bounds__(256) void k_redq_policy_grad(const float* __restrict__ head, const float* __restrict__ xp, int ld, int col_off,
-                                                          const float* __restrict__ da, int ld_da, int64_t e_stride, int E,
-                                                          const float* __restrict__ log_alpha, uint32_t k0, uint32_t k1, int scheme,
-                                                          float* __restrict__ d_out, int64_t B, int A, int AP, float ls_min, float ls_max,
-                                                          const float* __restrict__ eps_inject) {
-  const int rpb = 256 / AP;
-  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
-  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
-  if (i >= B) return;
-  const float alpha = expf(log_alpha[0]);
-  uint32_t s0, s1;
-  split_key_at(k0, k1, 1u + (uint32_t)i, (uint32_t)(B + 1), scheme, s0, s1);
-  const float invB = 1.0f / (float)B;
-  for (int j = jl; j < A; j += AP) {
-    const float raw = head[i * 2 * A + A + j];
-    const float ls = fminf(fmaxf(raw, ls_min), ls_max);
-    const float eps = eps_inject ? eps_inject[i * A + j] : normal_from_bits(random_bits_at(s0, s1, (uint64_t)j, (uint64_t)A, scheme));
-    const float a = xp[i * ld + col_off + j];
-    const float om = 1.0f - a * a;
-    float dqa = 0.f;
-    for (int e = 0; e < E; ++e) dqa += da[e * e_stride + i * ld_da + col_off + j];
-    const float du = (alpha * invB * 2.0f * a / (om + 1e-6f) + dqa) * om;
-    d_out[i * 2 * A + j] = du;
-    const bool inside = raw > ls_min && raw < ls_max;
-    d_out[i * 2 * A + A + j] = inside ? du * expf(ls) * eps - alpha * invB : 0.f;
-  }
-}
-
-// metrics (rlx_sac_update_f32's order), the means over the G critic steps (redq.py:244; steps: [G] q_loss then [G] grad norm, added
-// in index order) and the entropy coefficient's gradient with its plain Adam step at the POLICY counter (redq.py:201, :253; the
-// arithmetic of adam_body.h's adam_element without clipping).  minq_row: per row the min over the E critics on (s, a~); lpc: logp.
-__global__ __launch_bounds__(256) void k_redq_finish(const float* __restrict__ minq_row, const float* __restrict__ lpc, int64_t B,
-                                                     const float* __restrict__ steps, int G, float* __restrict__ log_alpha,
-                                                     float* __restrict__ am, float* __restrict__ av, float* __restrict__ metrics,
-                                                     float target_entropy, float lr, float bc1, float bc2, float b1, float b2, float eps) {
-  __shared__ double s_buf[256];
-  const double sq = redq_block_sum(minq_row, B, s_buf);
-  const double sl = redq_block_sum(lpc, B, s_buf);
-  if (threadIdx.x != 0) return;
-  double ql = 0.0, gn = 0.0;
-  for (int i = 0; i < G; ++i) {
-    ql += (double)steps[i];
-    gn += (double)steps[G + i];
-  }
-  const float mean_q = (float)(sq / (double)B), mean_lp = (float)(sl / (double)B);
-  const float la = log_alpha[0];
-  const float alpha = expf(la);
-  const float entropy = -mean_lp;
-  const float ga = alpha * (entropy - target_entropy);      // d mean(alpha_g (entropy - target)) / d log_alpha
-  metrics[0] = (float)(ql / (double)G);                     // loss/q_loss: mean over the G steps
-  metrics[1] = alpha * mean_lp - mean_q;                    // loss/policy_loss
-  metrics[2] = ga;                                          // loss/entropy_loss
-  metrics[3] = entropy;                                     // entropy/entropy
-  metrics[4] = alpha;                                       // entropy/alpha
-  metrics[5] = mean_q;                                      // q_value/q_value: mean of the min over all E critics (redq.py:196)
-  metrics[7] = (float)(gn / (double)G);                     // gradients/critic_grad_norm: mean over the G steps
-  metrics[8] = sqrtf(ga * ga);                              // gradients/entropy_grad_norm
-  metrics[9] = 0.f;
-  const float mi = fmaf(b1, am[0], (1.f - b1) * ga);
-  const float vi = fmaf(b2, av[0], ((1.f - b2) * ga) * ga);
-  am[0] = mi;
-  av[0] = vi;
-  log_alpha[0] = fmaf(-lr, (mi / bc1) / (sqrtf(vi / bc2) + eps), la);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host
-static int redq_check_net(const rlx_mlp_desc& d, const char* which) {   // tqc.hip's descriptor rules
-  char msg[160];
-  snprintf(msg, sizeof msg, "redq: %s needs 1..3 hidden layers and positive widths", which);
-  RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL, msg);
-  snprintf(msg, sizeof msg, "redq: %s must be act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0", which);
-  RLX_REQUIRE(d.act == RLX_ACT_RELU && !d.ln_first && !d.has_logstd, RLX_EINVAL, msg);
-  snprintf(msg, sizeof msg, "redq: %s hidden widths must be multiples of 64, at most 1024", which);
-  for (int l = 0; l < d.n_hidden; ++l) RLX_REQUIRE(d.hidden[l] > 0 && d.hidden[l] % 64 == 0 && d.hidden[l] <= 1024, RLX_EUNSUP, msg);
-  return RLX_OK;
-}
-
 // ensemble_size E, in_target_minimization_size M, q_update_steps G (redq/flax/default_config.py:18-20)
 static int redq_check_hp(const rlx_redq_hparams& hp) {
   RLX_REQUIRE(hp.ensemble_size >= 1, RLX_EINVAL, "redq: hp->ensemble_size must be at least 1");
@@ -209,27 +85,6 @@ static int redq_check_hp(const rlx_redq_hparams& hp) {
   return RLX_OK;
 }
 
-static Chain redq_layout(const rlx_mlp_desc& d) { return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_NONE, RLX_ACT_RELU); }
-
-static inline int redq_lanes_per_row(int A) {
-  int ap = 1;
-  while (ap < A && ap < 64) ap <<= 1;
-  return ap;
-}
-
-// jax.random.split(key, num)[i] on the host (sac_sample.h's split_key_at is the device's)
-static inline void redq_split_at(const uint32_t key[2], uint32_t i, uint32_t num, int scheme, uint32_t out[2]) {
-  if (scheme == RLX_THREEFRY_PARTITIONABLE) {
-    uint32_t x0 = 0, x1 = i;
-    threefry2x32(key[0], key[1], x0, x1);
-    out[0] = x0;
-    out[1] = x1;
-  } else {
-    out[0] = random_bits_at(key[0], key[1], 2ull * i, 2ull * num, RLX_THREEFRY_LEGACY);
-    out[1] = random_bits_at(key[0], key[1], 2ull * i + 1, 2ull * num, RLX_THREEFRY_LEGACY);
-  }
-}
-
 // permutation(sample_key, E)[:M] (jax _shuffle): ceil(3 ln E / ln(2^32 - 1)) rounds of {key, sub = split(key); stable sort by
 // random_bits(sub, (E,))} -- one round for 2 <= E <= 16, none for E = 1
 static void redq_subset(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out) {
@@ -239,8 +94,8 @@ static void redq_subset(const uint32_t sample_key[2], int E, int M, int scheme, 
   const int rounds = (int)ceil(3.0 * log((double)E) / log(4294967295.0));
   for (int r = 0; r < rounds; ++r) {
     uint32_t sub[2], nxt[2];
-    redq_split_at(key, 0, 2, scheme, nxt);
-    redq_split_at(key, 1, 2, scheme, sub);
+    split_at_host(key, 0, 2, scheme, nxt);
+    split_at_host(key, 1, 2, scheme, sub);
     key[0] = nxt[0];
     key[1] = nxt[1];
     uint32_t bits[REDQ_MAXE];
@@ -265,14 +120,8 @@ static int redq_critic_loss(const float* q, const float* qn, const float* rew, c
   hipLaunchKernelGGL(k_redq_critic_loss, dim3(div_up(B, 256)), dim3(256), 0, st, q, qn, rew, term, nlogp, log_alpha, y, dq, loss_row, B, E, M,
                      gamma);
   RLX_LAUNCH_CHECK();
-  if (loss_out) {
-    hipLaunchKernelGGL(k_redq_mean, dim3(1), dim3(256), 0, st, (const float*)loss_row, B, loss_out);
-    RLX_LAUNCH_CHECK();
-  }
-  return RLX_OK;
+  return loss_out ? ens_mean(loss_row, B, loss_out, st) : RLX_OK;
 }
-
-struct RedqAdamHp { float max_grad_norm, adam_b1, adam_b2, adam_eps; };   // what torch_clip_adam reads; max_grad_norm <= 0: plain Adam
 
 }  // namespace rlx
 
@@ -324,31 +173,21 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
               RLX_EINVAL, "rlx_redq_update_f32: NULL pointer");
   RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_update_f32: B must be positive");
   RLX_REQUIRE(B + 2 <= 0x7fffffffLL, RLX_EUNSUP, "rlx_redq_update_f32: B too large for the 32-bit key count B + 2");
-  int rc = redq_check_net(*pdesc, "pdesc");
+  int rc = ens_check_net(*pdesc, "redq", "pdesc");
   if (rc) return rc;
-  rc = redq_check_net(*qdesc, "qdesc");
+  rc = ens_check_net(*qdesc, "redq", "qdesc");
   if (rc) return rc;
   rc = redq_check_hp(*hp);
   if (rc) return rc;
-  RLX_REQUIRE(pdesc->out_dim % 2 == 0, RLX_EINVAL, "rlx_redq_update_f32: pdesc->out_dim must be 2 * act_dim");
-  const int A = pdesc->out_dim / 2, E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps;
-  RLX_REQUIRE(A <= 64, RLX_EUNSUP, "rlx_redq_update_f32: act_dim (pdesc->out_dim / 2) at most 64");
-  RLX_REQUIRE(qdesc->out_dim == 1, RLX_EINVAL, "rlx_redq_update_f32: qdesc->out_dim must be 1");
-  RLX_REQUIRE(qdesc->in_dim > A, RLX_EINVAL, "rlx_redq_update_f32: qdesc->in_dim must be critic obs + act_dim");
-  const int Op = pdesc->in_dim, Oc = qdesc->in_dim - A;
-  const bool asym = hp->critic_states != nullptr;
-  RLX_REQUIRE((hp->critic_states != nullptr) == (hp->critic_next_states != nullptr) && (asym || Oc == Op), RLX_EINVAL,
-              "rlx_redq_update_f32: critic obs width != policy obs width needs hp->critic_states AND hp->critic_next_states");
-  const float* cs = asym ? hp->critic_states : states;
-  const float* cn = asym ? hp->critic_next_states : next_states;
+  const int E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps;
+  EnsDims d;
+  rc = ens_prologue("rlx_redq_update_f32", *pdesc, *qdesc, 1, "must be 1", states, next_states, hp->critic_states, hp->critic_next_states, &d);
+  if (rc) return rc;
+  const int A = d.A, Op = d.Op, Oc = d.Oc, ldc = d.ldc, ldp = d.ldp;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const Chain LP = redq_layout(*pdesc), LQ = redq_layout(*qdesc);
+  const Chain LP = ens_layout(*pdesc), LQ = ens_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
-  const int ldc = (Oc + A + 3) & ~3, ldp = (Op + 3) & ~3;
-  const int AP = redq_lanes_per_row(A);
-  const int nb_rc = div_up(B, 256 / AP), nb_row = div_up(B, 256);
-  const size_t lds_rc = (size_t)(256 / AP) * A * sizeof(float);
   // ---- arena: the policy's passes, one buffer set for the targets' inference passes, E sets for the online critics: their backward
   // waits for the loss in a critic step and for the seed -- which needs all E values -- in the policy step
   ChainBufs bpn, bpc, bi, bq[REDQ_MAXE];
@@ -379,25 +218,23 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     uint32_t nxt[2], sample_key[2];
     step_key[i][0] = key[0];
     step_key[i][1] = key[1];
-    redq_split_at(key, 0, (uint32_t)(B + 2), scheme, nxt);
-    redq_split_at(key, 1, (uint32_t)(B + 2), scheme, sample_key);
+    split_at_host(key, 0, (uint32_t)(B + 2), scheme, nxt);
+    split_at_host(key, 1, (uint32_t)(B + 2), scheme, sample_key);
     redq_subset(sample_key, E, M, scheme, subset[i]);
     key[0] = nxt[0];
     key[1] = nxt[1];
   }
   step_key[G][0] = key[0];
   step_key[G][1] = key[1];
-  redq_split_at(step_key[G], 0, (uint32_t)(B + 1), scheme, key);
+  split_at_host(step_key[G], 0, (uint32_t)(B + 1), scheme, key);
   BxReleaseAll bx_all{ctx};
-  SacSampleArgs sa;
-  sa.scheme = scheme; sa.mode = 1; sa.ld_out = ldc; sa.col_off = Oc; sa.A = A;
-  sa.ls_min = hp->log_std_min; sa.ls_max = hp->log_std_max; sa.N_global = B;
-  const RedqAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
+  const SacSampleArgs sa = ens_sample_args(d, hp->log_std_min, hp->log_std_max, B);
+  const PlainAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
   // ---- G critic steps (redq.py:228-242)
   for (int i = 0; i < G; ++i) {
     const float* s2_i = next_states + (size_t)i * B * Op;
-    const float* cs_i = cs + (size_t)i * B * Oc;
-    const float* cn_i = cn + (size_t)i * B * Oc;
+    const float* cs_i = d.cs + (size_t)i * B * Oc;
+    const float* cn_i = d.cn + (size_t)i * B * Oc;
     const float* a_i = actions + (size_t)i * B * A;
     {  // the images of this step's passes, from the parameters as the previous step left them
       NetRef nets[1 + 2 * REDQ_MAXE];
@@ -410,14 +247,9 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
       if (rc) return rc;
     }
     // a', logp' from the policy on s'; the M selected targets on (s', a'); the E online critics on (s, a)
-    rc = fs_concat(cn_i, Oc, nullptr, A, xn, ldc, B, st);
-    if (!rc) rc = fs_concat(s2_i, Op, nullptr, 0, xsn, ldp, B, st);
-    if (!rc) rc = chain_fwd(ctx, LP, pparams, xsn, ldp, bpn, hn, B, st);
-    if (rc) return rc;
-    sa.k0 = step_key[i][0]; sa.k1 = step_key[i][1]; sa.act_out = xn; sa.logp = lpn;
-    sa.eps_inject = ctx->dbg_sac_eps[0] ? ctx->dbg_sac_eps[0] + (size_t)i * B * A : nullptr;
-    hipLaunchKernelGGL(k_redq_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hn, sa, B, AP, 2u, (uint32_t)(B + 2));
-    RLX_LAUNCH_CHECK();
+    const EnsRowKeys ki{step_key[i][0], step_key[i][1], scheme, 2u, 1u, (uint32_t)(B + 2)};
+    rc = ens_policy_sample(ctx, d, LP, pparams, cn_i, s2_i, xn, xsn, bpn, hn, lpn, sa, ki,
+                           ctx->dbg_sac_eps[0] ? ctx->dbg_sac_eps[0] + (size_t)i * B * A : nullptr, B, st);
     for (int m = 0; m < M && !rc; ++m) rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + (size_t)m * B, B, st);
     if (!rc) rc = fs_concat(cs_i, Oc, a_i, A, xc, ldc, B, st);
     for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + (size_t)e * B, B, st);
@@ -445,16 +277,11 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     rc = trunk_images(ctx, nets, n, B, st);
     if (rc) return rc;
   }
-  rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
-  if (!rc) rc = fs_concat(states, Op, nullptr, 0, xsc, ldp, B, st);
-  if (!rc) rc = chain_fwd(ctx, LP, pparams, xsc, ldp, bpc, hc, B, st);
-  if (rc) return rc;
-  sa.k0 = step_key[G][0]; sa.k1 = step_key[G][1]; sa.act_out = xp; sa.logp = lpc; sa.eps_inject = ctx->dbg_sac_eps[1];
-  hipLaunchKernelGGL(k_redq_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hc, sa, B, AP, 1u, (uint32_t)(B + 1));
-  RLX_LAUNCH_CHECK();
+  const EnsRowKeys kp{step_key[G][0], step_key[G][1], scheme, 1u, 1u, (uint32_t)(B + 1)};
+  rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kp, ctx->dbg_sac_eps[1], B, st);
   for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + (size_t)e * B, B, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_redq_policy_seed, dim3(nb_row), dim3(256), 0, st, (const float*)qa, seed, minq_row, B, E);
+  hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, (const float*)qa, seed, minq_row, B, E);
   RLX_LAUNCH_CHECK();
   {
     BwdPass bwd(ctx, B);   // the critics' seeds are 0 or -1 / (B n_ties); the policy's head gradient is ~ 1 / B per sample
@@ -462,11 +289,9 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     for (int e = 0; e < E && !rc; ++e)
       rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + (size_t)e * B, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_redq_policy_grad, dim3(nb_rc), dim3(256), 0, st, (const float*)hc, (const float*)xp, ldc, Oc, (const float*)da, ldc,
-                       (int64_t)B * ldc, E, (const float*)log_alpha, step_key[G][0], step_key[G][1], scheme, dpi, B, A, AP, hp->log_std_min,
-                       hp->log_std_max, ctx->dbg_sac_eps[1]);
-    RLX_LAUNCH_CHECK();
-    rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
+    rc = ens_policy_grad(hc, xp, ldc, Oc, da, ldc, (int64_t)B * ldc, E, log_alpha, kp, dpi, B, A, hp->log_std_min, hp->log_std_max,
+                         ctx->dbg_sac_eps[1], st);
+    if (!rc) rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
     if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
@@ -474,10 +299,9 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
   const int64_t pstep = *pi_opt_count_io + 1;
   float sched[3];
   adam_schedule_entry(sched, pstep, hp->lr_alpha, hp->adam_b1, hp->adam_b2);
-  hipLaunchKernelGGL(k_redq_finish, dim3(1), dim3(256), 0, st, (const float*)minq_row, (const float*)lpc, B, (const float*)steps, G, log_alpha, am,
-                     av, metrics_out, hp->target_entropy, sched[0], sched[1], sched[2], hp->adam_b1, hp->adam_b2, hp->adam_eps);
-  RLX_LAUNCH_CHECK();
-  rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, pstep, hp->lr_policy, ahp, metrics_out + 6, st);
+  rc = ens_finish(minq_row, B, lpc, B, steps, G, log_alpha, am, av, metrics_out, hp->target_entropy, sched, hp->adam_b1, hp->adam_b2,
+                  hp->adam_eps, st);
+  if (!rc) rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, pstep, hp->lr_policy, ahp, metrics_out + 6, st);
   if (rc) return rc;
   key_io[0] = key[0];
   key_io[1] = key[1];

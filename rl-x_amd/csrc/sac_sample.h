@@ -16,8 +16,8 @@ __host__ __device__ __forceinline__ uint32_t sac_key_index(int which /*1 or 2*/,
 __host__ __device__ __forceinline__ uint32_t sac_key_count(int64_t B, int schedule) { return (uint32_t)(2 * B + 1 + (schedule ? 1 : 0)); }
 
 // keys = jax.random.split(key, num)[i]
-__device__ __forceinline__ void split_key_at(uint32_t k0, uint32_t k1, uint32_t i, uint32_t num, int scheme,
-                                             uint32_t& o0, uint32_t& o1) {
+__host__ __device__ __forceinline__ void split_key_at(uint32_t k0, uint32_t k1, uint32_t i, uint32_t num, int scheme,
+                                                      uint32_t& o0, uint32_t& o1) {
   if (scheme == RLX_THREEFRY_PARTITIONABLE) {
     uint32_t x0 = 0, x1 = i;
     threefry2x32(k0, k1, x0, x1);

@@ -16,15 +16,16 @@
 //
 // Schedule of one update (one stream, no host synchronisation): policy on s' -> sample a', logp' -> E target chains -> k_tqc_target;
 // E online chains on (s, a) -> k_tqc_qloss -> E backward passes; policy on s -> sample a~, logp -> per critic: forward on (s, a~),
-// input gradient on the action columns from the constant seed -1 / (B T) -> k_tqc_policy_grad -> policy backward; k_tqc_atom_rowsum, k_tqc_finish
+// input gradient on the action columns from the constant seed -1 / (B T) -> k_ens_policy_grad -> policy backward; k_tqc_atom_rowsum, k_ens_finish
 // (metrics, the entropy coefficient's Adam step); plain Adam of the policy; plain Adam of all E critics with the Polyak step.
-// Every reduction runs in a fixed order: two identical calls give identical bits.
+// The sample, the policy's head gradient, the means and the finish are sac_ens.hip's, shared with redq.hip; the noise keys are SAC's
+// schedule 0: keys = split(key, 2B+1), key = keys[0], next-state / current-state noise of row i from keys[1 + 2i] / keys[2 + 2i]
+// (tqc.py:211-212).  Every reduction runs in a fixed order: two identical calls give identical bits.
 //
 // Atoms that are NaN are outside the contract: the sort compares with fminf / fmaxf, which drop a NaN operand, so a row holding
 // one loses it (and duplicates a neighbour) instead of propagating it.  +-inf atoms sort as values.
 // CPU twin: tests/tqc_twin.py (float64).  The reference's TQC is JAX only; see DESIGN.md 4.5d for what is pinned.
-#include "net_pass.h"
-#include "sac_sample.h"
+#include "sac_ens.h"
 
 namespace rlx {
 
@@ -122,26 +123,6 @@ __global__ __launch_bounds__(256) void k_tqc_qloss(const float* __restrict__ q, 
   if (lane == 0) loss_row[b] = loss / kappa * inv_pairs;
 }
 
-// sum of v[0 .. n) over one workgroup: double accumulators, fixed order, no atomics
-__device__ __forceinline__ double tqc_block_sum(const float* __restrict__ v, int64_t n, double* s_buf) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)v[i];
-  s_buf[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_buf[threadIdx.x] += s_buf[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = s_buf[0];
-  __syncthreads();
-  return r;
-}
-__global__ __launch_bounds__(256) void k_tqc_loss_mean(const float* __restrict__ loss_row, int64_t B, float* __restrict__ out) {
-  __shared__ double s_buf[256];
-  const double s = tqc_block_sum(loss_row, B, s_buf);
-  if (threadIdx.x == 0) out[0] = (float)(s / (double)B);
-}
-
 // row_sum[b] = sum of the row's T atoms (one wave per transition): the policy loss's mean over all atoms, per row
 __global__ __launch_bounds__(256) void k_tqc_atom_rowsum(const float* __restrict__ atoms, float* __restrict__ row_sum, int64_t B, int N, int T) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -155,102 +136,7 @@ __global__ __launch_bounds__(256) void k_tqc_fill(float* __restrict__ out, int64
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = v;
 }
 
-// tanh-Gaussian sample of the update from the policy's head output [B, 2A], built from sac_sample.h as k_sac_sample is: mode 1 / 2
-// = next-state / current-state noise of SAC's schedule 0 (keys = split(key, 2B+1), keys[mode + 2i]; tqc.py:211-212).  One thread
-// per (row, action dim); a row's log-prob terms meet in LDS and one lane adds them in index order.  Dynamic LDS: (256 / AP) A floats.
-__global__ __launch_bounds__(256) void k_tqc_sample(const float* __restrict__ head, SacSampleArgs sa, int64_t B, int AP) {
-  extern __shared__ float s_term[];
-  const int A = sa.A;
-  const int rpb = 256 / AP;
-  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
-  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
-  if (i < B) {
-    uint32_t s0, s1;
-    sac_row_key(sa, sa.k0, sa.k1, i, s0, s1);
-    for (int j = jl; j < A; j += AP) s_term[rl * A + j] = sac_sample_elem(sa, s0, s1, i, j, head[i * 2 * A + j], head[i * 2 * A + A + j]);
-  }
-  __syncthreads();
-  if (i < B && jl == 0) {
-    float lp = 0.f;
-    for (int j = 0; j < A; ++j) lp += s_term[rl * A + j];
-    sa.logp[i] = lp;
-  }
-}
-
-// d L / d(head output) of the policy (tqc.py:173-185), SAC's gradient with dQ/da summed over the E critics (da: E buffers of
-// [B, ld_da], e_stride floats apart, action columns at col_off; each already carries the seed -1 / (B T)):
-//   d_u = (alpha / B * 2a / (1 - a^2 + 1e-6) + sum_e dQ_e/da) (1 - a^2);  d_mean = d_u;
-//   d_logstd = [raw inside the clip] (d_u std eps - alpha / B)
-__global__ __launch_bounds__(256) void k_tqc_policy_grad(const float* __restrict__ head, const float* __restrict__ xp, int ld, int col_off,
-                                                         const float* __restrict__ da, int ld_da, int64_t e_stride, int E,
-                                                         const float* __restrict__ log_alpha, uint32_t k0, uint32_t k1, int scheme,
-                                                         float* __restrict__ d_out, int64_t B, int A, int AP, float ls_min, float ls_max,
-                                                         const float* __restrict__ eps_inject) {
-  const int rpb = 256 / AP;
-  const int rl = threadIdx.x / AP, jl = threadIdx.x - rl * AP;
-  const int64_t i = (int64_t)blockIdx.x * rpb + rl;
-  if (i >= B) return;
-  const float alpha = expf(log_alpha[0]);
-  uint32_t s0, s1;
-  split_key_at(k0, k1, sac_key_index(2, i, B, 0), sac_key_count(B, 0), scheme, s0, s1);
-  const float invB = 1.0f / (float)B;
-  for (int j = jl; j < A; j += AP) {
-    const float raw = head[i * 2 * A + A + j];
-    const float ls = fminf(fmaxf(raw, ls_min), ls_max);
-    const float eps = eps_inject ? eps_inject[i * A + j] : normal_from_bits(random_bits_at(s0, s1, (uint64_t)j, (uint64_t)A, scheme));
-    const float a = xp[i * ld + col_off + j];
-    const float om = 1.0f - a * a;
-    float dqa = 0.f;
-    for (int e = 0; e < E; ++e) dqa += da[e * e_stride + i * ld_da + col_off + j];
-    const float du = (alpha * invB * 2.0f * a / (om + 1e-6f) + dqa) * om;
-    d_out[i * 2 * A + j] = du;
-    const bool inside = raw > ls_min && raw < ls_max;
-    d_out[i * 2 * A + A + j] = inside ? du * expf(ls) * eps - alpha * invB : 0.f;
-  }
-}
-
-// metrics (rlx_sac_update_f32's order) and the entropy coefficient's gradient with its plain Adam step (tqc.py:188, :220; the
-// arithmetic of adam_body.h's adam_element without clipping).  qa_row: per row the sum of the T atoms of the critics on (s, a~)
-// (k_tqc_atom_rowsum); lpc: logp [B].
-__global__ __launch_bounds__(256) void k_tqc_finish(const float* __restrict__ qa_row, int64_t n_atoms, const float* __restrict__ lpc, int64_t B,
-                                                    float* __restrict__ log_alpha, float* __restrict__ am, float* __restrict__ av,
-                                                    float* __restrict__ metrics, float target_entropy, float lr, float bc1, float bc2,
-                                                    float b1, float b2, float eps) {
-  __shared__ double s_buf[256];
-  const double sq = tqc_block_sum(qa_row, B, s_buf);
-  const double sl = tqc_block_sum(lpc, B, s_buf);
-  if (threadIdx.x != 0) return;
-  const float mean_q = (float)(sq / (double)n_atoms), mean_lp = (float)(sl / (double)B);
-  const float la = log_alpha[0];
-  const float alpha = expf(la);
-  const float entropy = -mean_lp;
-  const float ga = alpha * (entropy - target_entropy);      // d mean(alpha_g (entropy - target)) / d log_alpha
-  metrics[1] = alpha * mean_lp - mean_q;                    // loss/policy_loss
-  metrics[2] = ga;                                          // loss/entropy_loss
-  metrics[3] = entropy;                                     // entropy/entropy
-  metrics[4] = alpha;                                       // entropy/alpha
-  metrics[5] = mean_q;                                      // q_value/q_value: mean over all atoms (tqc.py:183)
-  metrics[8] = sqrtf(ga * ga);                              // gradients/entropy_grad_norm
-  metrics[9] = 0.f;
-  const float mi = fmaf(b1, am[0], (1.f - b1) * ga);
-  const float vi = fmaf(b2, av[0], ((1.f - b2) * ga) * ga);
-  am[0] = mi;
-  av[0] = vi;
-  log_alpha[0] = fmaf(-lr, (mi / bc1) / (sqrtf(vi / bc2) + eps), la);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host
-static int tqc_check_net(const rlx_mlp_desc& d, const char* which) {
-  char msg[160];
-  snprintf(msg, sizeof msg, "tqc: %s needs 1..3 hidden layers and positive widths", which);
-  RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL, msg);
-  snprintf(msg, sizeof msg, "tqc: %s must be act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0", which);
-  RLX_REQUIRE(d.act == RLX_ACT_RELU && !d.ln_first && !d.has_logstd, RLX_EINVAL, msg);
-  snprintf(msg, sizeof msg, "tqc: %s hidden widths must be multiples of 64, at most 1024", which);
-  for (int l = 0; l < d.n_hidden; ++l) RLX_REQUIRE(d.hidden[l] > 0 && d.hidden[l] % 64 == 0 && d.hidden[l] <= 1024, RLX_EUNSUP, msg);
-  return RLX_OK;
-}
-
 // ensemble_size E, nr_atoms_per_net N, nr_dropped_atoms_per_net, huber_kappa (tqc/flax/default_config.py:18-21)
 static int tqc_check_hp(const rlx_tqc_hparams& hp, int* T_out, int* K_out) {
   RLX_REQUIRE(hp.ensemble_size >= 1, RLX_EINVAL, "tqc: hp->ensemble_size must be at least 1");
@@ -266,14 +152,6 @@ static int tqc_check_hp(const rlx_tqc_hparams& hp, int* T_out, int* K_out) {
   return RLX_OK;
 }
 
-static Chain tqc_layout(const rlx_mlp_desc& d) { return make_chain(d.in_dim, d.hidden, d.n_hidden, d.out_dim, NORM_NONE, RLX_ACT_RELU); }
-
-static inline int tqc_lanes_per_row(int A) {
-  int ap = 1;
-  while (ap < A && ap < 64) ap <<= 1;
-  return ap;
-}
-
 // y (tqc.py:155-158), the pair loss and its gradient (tqc.py:161-170) on given atoms; loss_row: B floats of scratch
 static int tqc_loss(const float* q, const float* zt, const float* rew, const float* term, const float* nlogp, const float* log_alpha,
                     int64_t B, const rlx_tqc_hparams& hp, int T, int K, float* y, float* dq, float* loss_row, float* loss_out,
@@ -283,12 +161,8 @@ static int tqc_loss(const float* q, const float* zt, const float* rew, const flo
   RLX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_tqc_qloss, dim3(div_up(B, 4)), dim3(256), 0, st, q, (const float*)y, dq, loss_row, B, N, T, K, hp.huber_kappa);
   RLX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_tqc_loss_mean, dim3(1), dim3(256), 0, st, (const float*)loss_row, B, loss_out);
-  RLX_LAUNCH_CHECK();
-  return RLX_OK;
+  return ens_mean(loss_row, B, loss_out, st);
 }
-
-struct TqcAdamHp { float max_grad_norm, adam_b1, adam_b2, adam_eps; };   // what torch_clip_adam reads; max_grad_norm <= 0: plain Adam
 
 }  // namespace rlx
 
@@ -323,32 +197,23 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
               RLX_EINVAL, "rlx_tqc_update_f32: NULL pointer");
   RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_tqc_update_f32: B must be positive");
   RLX_REQUIRE(2 * B + 1 <= 0x7fffffffLL, RLX_EUNSUP, "rlx_tqc_update_f32: B too large for the 32-bit key count 2 B + 1");
-  int rc = tqc_check_net(*pdesc, "pdesc");
+  int rc = ens_check_net(*pdesc, "tqc", "pdesc");
   if (rc) return rc;
-  rc = tqc_check_net(*qdesc, "qdesc");
+  rc = ens_check_net(*qdesc, "tqc", "qdesc");
   if (rc) return rc;
   int T, K;
   rc = tqc_check_hp(*hp, &T, &K);
   if (rc) return rc;
-  RLX_REQUIRE(pdesc->out_dim % 2 == 0, RLX_EINVAL, "rlx_tqc_update_f32: pdesc->out_dim must be 2 * act_dim");
-  const int A = pdesc->out_dim / 2, E = hp->ensemble_size, N = hp->nr_atoms_per_net;
-  RLX_REQUIRE(A <= 64, RLX_EUNSUP, "rlx_tqc_update_f32: act_dim (pdesc->out_dim / 2) at most 64");
-  RLX_REQUIRE(qdesc->out_dim == N, RLX_EINVAL, "rlx_tqc_update_f32: qdesc->out_dim must equal hp->nr_atoms_per_net");
-  RLX_REQUIRE(qdesc->in_dim > A, RLX_EINVAL, "rlx_tqc_update_f32: qdesc->in_dim must be critic obs + act_dim");
-  const int Op = pdesc->in_dim, Oc = qdesc->in_dim - A;
-  const bool asym = hp->critic_states != nullptr;
-  RLX_REQUIRE((hp->critic_states != nullptr) == (hp->critic_next_states != nullptr) && (asym || Oc == Op), RLX_EINVAL,
-              "rlx_tqc_update_f32: critic obs width != policy obs width needs hp->critic_states AND hp->critic_next_states");
-  const float* cs = asym ? hp->critic_states : states;
-  const float* cn = asym ? hp->critic_next_states : next_states;
+  const int E = hp->ensemble_size, N = hp->nr_atoms_per_net;
+  EnsDims d;
+  rc = ens_prologue("rlx_tqc_update_f32", *pdesc, *qdesc, N, "must equal hp->nr_atoms_per_net", states, next_states, hp->critic_states,
+                    hp->critic_next_states, &d);
+  if (rc) return rc;
+  const int A = d.A, Oc = d.Oc, ldc = d.ldc, ldp = d.ldp;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const Chain LP = tqc_layout(*pdesc), LQ = tqc_layout(*qdesc);
+  const Chain LP = ens_layout(*pdesc), LQ = ens_layout(*qdesc);
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
-  const int ldc = (Oc + A + 3) & ~3, ldp = (Op + 3) & ~3;
-  const int AP = tqc_lanes_per_row(A);
-  const int nb_rc = div_up(B, 256 / AP);
-  const size_t lds_rc = (size_t)(256 / AP) * A * sizeof(float);
   const size_t BN = (size_t)B * N;
   // ---- arena: the policy's two passes, one buffer set for the inference passes of the critics (targets; online on (s, a~), whose
   // backward follows at once), E sets for the online critics on (s, a), whose backward waits for the loss
@@ -372,18 +237,9 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
   });
   float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
   if (rc || !sq) return RLX_ENOMEM;
-  // keys = split(key, 2B+1); key = keys[0] (tqc.py:211-212)
-  const uint32_t k0 = key_io[0], k1 = key_io[1];
-  if (scheme == RLX_THREEFRY_PARTITIONABLE) {
-    uint32_t x0 = 0, x1 = 0;
-    threefry2x32(k0, k1, x0, x1);
-    key_io[0] = x0;
-    key_io[1] = x1;
-  } else {
-    const uint64_t nkeys = sac_key_count(B, 0);
-    key_io[0] = random_bits_at(k0, k1, 0, 2ull * nkeys, RLX_THREEFRY_LEGACY);
-    key_io[1] = random_bits_at(k0, k1, 1, 2ull * nkeys, RLX_THREEFRY_LEGACY);
-  }
+  // keys = split(key, 2B+1); key = keys[0]; row i's noise from keys[1 + 2i] on s', keys[2 + 2i] on s (tqc.py:211-212: sac_key_index)
+  const EnsRowKeys kn{key_io[0], key_io[1], scheme, 1u, 2u, sac_key_count(B, 0)}, kc{kn.k0, kn.k1, scheme, 2u, 2u, kn.count};
+  split_at_host(key_io, 0, kn.count, scheme, key_io);
   // ---- split-operand images of the hidden layers (>= 4096 rows).  The image builder takes BX_MAX_JOBS jobs: the policy (both
   // directions), then the online critics (three passes each, both directions), then the targets (one pass each); what no longer
   // fits -- from six critics with three hidden layers on -- runs on the exact engine (trunk_images).
@@ -397,19 +253,11 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
     rc = trunk_images(ctx, nets, n, B, st);
     if (rc) return rc;
   }
-  SacSampleArgs sa;
-  sa.k0 = k0; sa.k1 = k1; sa.scheme = scheme; sa.ld_out = ldc; sa.col_off = Oc; sa.A = A;
-  sa.ls_min = hp->log_std_min; sa.ls_max = hp->log_std_max; sa.N_global = B;
+  const SacSampleArgs sa = ens_sample_args(d, hp->log_std_min, hp->log_std_max, B);
   // ---- critic loss (tqc.py:144-170): a', logp' from the policy on s'; the E target networks on (s', a'); the online ones on (s, a)
-  rc = fs_concat(cn, Oc, nullptr, A, xn, ldc, B, st);
-  if (!rc) rc = fs_concat(next_states, Op, nullptr, 0, xsn, ldp, B, st);
-  if (!rc) rc = chain_fwd(ctx, LP, pparams, xsn, ldp, bpn, hn, B, st);
-  if (rc) return rc;
-  sa.mode = 1; sa.act_out = xn; sa.logp = lpn; sa.eps_inject = ctx->dbg_sac_eps[0];
-  hipLaunchKernelGGL(k_tqc_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hn, sa, B, AP);
-  RLX_LAUNCH_CHECK();
+  rc = ens_policy_sample(ctx, d, LP, pparams, d.cn, next_states, xn, xsn, bpn, hn, lpn, sa, kn, ctx->dbg_sac_eps[0], B, st);
   for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qtarget + e * nq, xn, ldc, bi, zt + e * BN, B, st);
-  if (!rc) rc = fs_concat(cs, Oc, actions, A, xc, ldc, B, st);
+  if (!rc) rc = fs_concat(d.cs, Oc, actions, A, xc, ldc, B, st);
   for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + e * BN, B, st);
   if (!rc) rc = tqc_loss(q, zt, rewards, terminations, lpn, log_alpha, B, *hp, T, K, y, dq, loss_row, metrics_out, st);
   // one deferred reduction per critic: its table takes one network's segments, not eight networks'.  The split-operand gradient
@@ -423,13 +271,8 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
   if (rc) return rc;
   // ---- policy loss (tqc.py:173-185): a~, logp from the policy on s; per frozen critic the atoms on (s, a~) and, from the constant
   // seed d(-mean atoms) / d atom = -1 / (B T), the input gradient on the action columns
-  rc = fs_concat(cs, Oc, nullptr, A, xp, ldc, B, st);
-  if (!rc) rc = fs_concat(states, Op, nullptr, 0, xsc, ldp, B, st);
-  if (!rc) rc = chain_fwd(ctx, LP, pparams, xsc, ldp, bpc, hc, B, st);
+  rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kc, ctx->dbg_sac_eps[1], B, st);
   if (rc) return rc;
-  sa.mode = 2; sa.act_out = xp; sa.logp = lpc; sa.eps_inject = ctx->dbg_sac_eps[1];
-  hipLaunchKernelGGL(k_tqc_sample, dim3(nb_rc), dim3(256), lds_rc, st, (const float*)hc, sa, B, AP);
-  RLX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_tqc_fill, dim3(elem_grid((int64_t)BN)), dim3(256), 0, st, seed, (int64_t)BN, -1.0f / ((float)B * (float)T));
   RLX_LAUNCH_CHECK();
   {
@@ -443,11 +286,9 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
       }
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tqc_policy_grad, dim3(nb_rc), dim3(256), 0, st, (const float*)hc, (const float*)xp, ldc, Oc, (const float*)da, ldc,
-                       (int64_t)B * ldc, E, (const float*)log_alpha, k0, k1, scheme, dpi, B, A, AP, hp->log_std_min, hp->log_std_max,
-                       ctx->dbg_sac_eps[1]);
-    RLX_LAUNCH_CHECK();
-    rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
+    rc = ens_policy_grad(hc, xp, ldc, Oc, da, ldc, (int64_t)B * ldc, E, log_alpha, kc, dpi, B, A, hp->log_std_min, hp->log_std_max,
+                         ctx->dbg_sac_eps[1], st);
+    if (!rc) rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
     if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }
@@ -457,11 +298,10 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
   adam_schedule_entry(sched, step, hp->lr_alpha, hp->adam_b1, hp->adam_b2);
   hipLaunchKernelGGL(k_tqc_atom_rowsum, dim3(div_up(B, 4)), dim3(256), 0, st, (const float*)qa, qa_row, B, N, T);
   RLX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_tqc_finish, dim3(1), dim3(256), 0, st, (const float*)qa_row, (int64_t)E * (int64_t)BN, (const float*)lpc, B, log_alpha, am, av,
-                     metrics_out, hp->target_entropy, sched[0], sched[1], sched[2], hp->adam_b1, hp->adam_b2, hp->adam_eps);
-  RLX_LAUNCH_CHECK();
-  const TqcAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
-  rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, step, hp->lr_policy, ahp, metrics_out + 6, st);
+  rc = ens_finish(qa_row, (int64_t)E * (int64_t)BN, lpc, B, nullptr, 0, log_alpha, am, av, metrics_out, hp->target_entropy, sched, hp->adam_b1,
+                  hp->adam_b2, hp->adam_eps, st);
+  const PlainAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
+  if (!rc) rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, step, hp->lr_policy, ahp, metrics_out + 6, st);
   if (!rc) rc = torch_clip_adam(qparams, gq, qm, qv, (int64_t)E * nq, sq, step, hp->lr_critic, ahp, metrics_out + 7, st, qtarget, hp->tau);
   if (rc) return rc;
   *opt_count_io += 1;
