@@ -831,6 +831,52 @@ int rlx_redq_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, flo
                         const rlx_redq_hparams* hp, float* metrics_out /*DEVICE [10]*/, int32_t* subsets_out /*HOST [G,M] or NULL*/,
                         void* stream);
 
+/* ---- AQE: truncated-mean multi-head ensemble critics (rl_x/algorithms/aqe/flax) -------------------------------------------------
+ * REDQ's high update-to-data `update` (aqe.py:145-259: G = q_update_steps critic steps on G fresh batches, each followed by plain
+ * Adam of all critics and Polyak, :230-240; then ONE policy / entropy step on batch 0 with the critics from after the loop,
+ * :245-251) over ensemble_size critics with nr_heads_per_net outputs each (critic.py: Dense(H) -> ReLU -> Dense(H) -> ReLU ->
+ * Dense(nr_heads_per_net), BACK TO BACK in one flat vector like rlx_tqc_update_f32's).  Networks: rlx_mlp_desc with act =
+ * RLX_ACT_RELU, ln_first = 0, has_logstd = 0; FLAT LAYOUT of a network: FastTD3's (above).  Q values are laid out [E, B, H],
+ * critic-major; flat index i = e * nr_heads_per_net + h (reshape(nr_total_q_values), aqe.py:165); T = E * H values per transition,
+ * K = T - nr_dropped_q_values of them kept in the target (aqe.py:58-59: dropped from the POOL, not per net).  Envelope: 1..3 hidden
+ * layers, widths multiples of 64 up to 1024, act_dim <= 64, qdesc->out_dim = nr_heads_per_net >= 1, 1 <= ensemble_size <= 16, T <=
+ * 128, 0 <= nr_dropped_q_values < T, 1 <= q_update_steps <= 64, B > 0; a descriptor or size outside it is RLX_EUNSUP, every other
+ * bad argument RLX_EINVAL, rlx_last_error() names it.  Q values that are NaN are outside the contract (the sort drops them).       */
+typedef struct rlx_aqe_hparams {               /* aqe/flax/default_config.py:9-28 */
+  float gamma, tau, target_entropy, log_std_min, log_std_max;
+  float lr_policy, lr_critic, lr_critic_delta, lr_alpha;   /* host evaluates the schedules (aqe.py:83-99); critic step i of the call
+                                                            * runs at lr_critic + i * lr_critic_delta (q_linear_schedule, :83-87) */
+  float adam_b1, adam_b2, adam_eps;            /* optax.adam defaults 0.9, 0.999, 1e-8 (aqe.py:111,118,124) */
+  int32_t ensemble_size, nr_heads_per_net, nr_dropped_q_values, q_update_steps;   /* aqe.py:51-52, :58-59 */
+  const float *critic_states, *critic_next_states;   /* [G, B, Oc]: the critics' own observation columns of s / s', or NULL both
+                                                      * (the policy's) */
+} rlx_aqe_hparams;
+
+/* the two loss heads on given values; any output may be NULL except the one its inputs serve (dq_out; seed_out when qa is given).
+ * Critic (aqe.py:164-171, meaned over the batch, :221): y_out [B] = r + gamma (1 - term) (mean of the K lowest of the row's T
+ * POOLED values of q_next - exp(log_alpha) next_logp); dq_out [E, B, H] = 2 (q - y) / (B T); loss_out DEVICE [1] = mean (q - y)^2.
+ * Policy (aqe.py:197-200), qa != NULL: meanq_out [B] = the row's mean over all T values of qa; seed_out [E, B, H] =
+ * d mean(-mean_q) / d qa = -1 / (B T). */
+int rlx_aqe_losses_f32(rlx_ctx*, const float* q /*[E,B,H]*/, const float* q_next /*[E,B,H]*/, const float* rewards,
+                       const float* terminations, const float* next_logp, const float* log_alpha, const float* qa /*[E,B,H] or NULL*/,
+                       int64_t B, const rlx_aqe_hparams* hp, float* y_out, float* dq_out, float* loss_out,
+                       float* seed_out /*[E,B,H]*/, float* meanq_out /*[B]*/, void* stream);
+
+/* the whole jitted `update` (aqe.py:145-259) in one call on one stream, no host synchronisation.  Every step, critic or policy:
+ * keys = split(key, B + 1), key = keys[0], row b's noise from keys[1 + b] (:231-232, :245-246).
+ * rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) draws instead: eps_next [G, B, A], eps_cur [B, A].
+ * states / next_states [G, B, pdesc->in_dim], actions [G, B, A], rewards / terminations [G, B]; the policy step reads batch 0.
+ * qparams / qm / qv / qtarget: [E * nq].  q_opt_count_io / pi_opt_count_io (HOST): the two optax counters (:108-125), advanced by
+ * G and by 1; critic step i is Adam step q_count + i + 1.  metrics_out DEVICE float[10] in rlx_sac_update_f32's order: [0] q_loss
+ * and [7] critic_grad_norm are the means over the G steps (:242), [5] q_value the mean over batch and all T heads, [9] = 0.
+ * Nothing is written when a check fails. */
+int rlx_aqe_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv,
+                       const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qtarget,
+                       float* log_alpha, float* am, float* av, const float* states /*[G,B,O]*/, const float* next_states,
+                       const float* actions, const float* rewards /*[G,B]*/, const float* terminations, int64_t B,
+                       uint32_t key_io[2], int scheme, int64_t* q_opt_count_io /* += G */, int64_t* pi_opt_count_io /* += 1 */,
+                       const rlx_aqe_hparams* hp, float* metrics_out /*DEVICE [10]*/, void* stream);
+
 /* =================================== REPPO ===============================================
  * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
  * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust

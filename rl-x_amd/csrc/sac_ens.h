@@ -1,7 +1,8 @@
-// sac_ens.h -- what tqc.hip and redq.hip share: SAC's tanh-Gaussian policy and entropy coefficient over an ensemble of E plain-ReLU
-// critics on net_pass.h.  The kernels and their launchers are in sac_ens.hip; here are their declarations and the host helpers of an
-// entry point: the descriptor rules, the shapes of a call, host key splitting, and the policy pass that ends in a sample.  An
-// algorithm's file keeps its critic target and loss, its hyper-parameter check, its arena carve and its schedule.
+// sac_ens.h -- what tqc.hip, redq.hip and aqe.hip share: SAC's tanh-Gaussian policy and entropy coefficient over an ensemble of E
+// plain-ReLU critics on net_pass.h.  The kernels and their launchers are in sac_ens.hip; here are their declarations, the device
+// helpers of the multi-output critics (value indexing, the wave-level bitonic sort) and the host helpers of an entry point: the
+// descriptor rules, the shapes of a call, host key splitting, and the policy pass that ends in a sample.  An algorithm's file keeps
+// its critic target and loss, its hyper-parameter check, its arena carve and its schedule.
 #pragma once
 #include "net_pass.h"
 #include "sac_sample.h"
@@ -9,7 +10,7 @@
 namespace rlx {
 
 // the noise key of row i: split((k0, k1), count)[base + stride * i].  TQC is SAC's schedule 0 (sac_sample.h): (1 or 2, 2, 2B + 1);
-// REDQ: (2, 1, B + 2) in a critic step, (1, 1, B + 1) in the policy step.
+// REDQ: (2, 1, B + 2) in a critic step, (1, 1, B + 1) in the policy step.  AQE: (1, 1, B + 1) in every step.
 struct EnsRowKeys { uint32_t k0, k1; int scheme; uint32_t base, stride, count; };
 
 // ---- sac_ens.hip
@@ -28,9 +29,48 @@ int ens_mean(const float* v, int64_t n, float* out, hipStream_t st);
 // norm, whose means go to metrics[0] and [7]; NULL leaves those two alone.
 int ens_finish(const float* q_row, int64_t q_div, const float* lpc, int64_t B, const float* steps, int G, float* log_alpha, float* am,
                float* av, float* metrics, float target_entropy, const float sched[3], float b1, float b2, float eps, hipStream_t st);
+// row_sum[b] = sum of the row's T = E N values (atoms [E, B, N], T <= 128; one wave per transition, fixed order)
+int ens_atom_rowsum(const float* atoms, float* row_sum, int64_t B, int N, int T, hipStream_t st);
+// out[0 .. n) = v
+int ens_fill(float* out, int64_t n, float v, hipStream_t st);
+
+// ---- device helpers of the multi-output critics (tqc.hip's atoms, aqe.hip's heads)
+// Value i = e N + n of row b lives at atoms[(e B + b) N + n]: critic-major, as E head GEMMs leave them.
+__device__ __forceinline__ int64_t ens_atom_index(int64_t b, int i, int64_t B, int N) {
+  const int e = i / N;
+  return ((int64_t)e * B + b) * N + (i - e * N);
+}
+__device__ __forceinline__ float ens_atom(const float* __restrict__ atoms, int64_t b, int i, int64_t B, int N) {
+  return atoms[ens_atom_index(b, i, B, N)];
+}
+
+// Ascending bitonic sort of up to 128 values held two per lane: element index = lane + 64 slot.  Stages with a partner distance
+// below 64 exchange across lanes (__shfl_xor), the one stage at distance 64 exchanges the lane's own two slots.  Values only.
+template <int SLOTS>
+__device__ __forceinline__ void ens_sort(float (&v)[2], int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64 * SLOTS; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (j == 64) {   // (k == 128 only: every index has bit 7 clear, so the merge is ascending)
+        const float lo = fminf(v[0], v[1]), hi = fmaxf(v[0], v[1]);
+        v[0] = lo;
+        v[1] = hi;
+      } else {
+        const bool lower = (lane & j) == 0;
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+          const float o = __shfl_xor(v[s], j, 64);
+          const bool asc = ((lane + 64 * s) & k) == 0;
+          v[s] = (asc == lower) ? fminf(v[s], o) : fmaxf(v[s], o);
+        }
+      }
+    }
+  }
+}
 
 // ---- host helpers
-// the networks both algorithms take: 1..3 plain ReLU blocks; algo: "tqc" / "redq", which: "pdesc" / "qdesc"
+// the networks these algorithms take: 1..3 plain ReLU blocks; algo: "tqc" / "redq" / "aqe", which: "pdesc" / "qdesc"
 static inline int ens_check_net(const rlx_mlp_desc& d, const char* algo, const char* which) {
   const std::string who = std::string(algo) + ": " + which;
   RLX_REQUIRE(d.n_hidden >= 1 && d.n_hidden <= 3 && d.in_dim > 0 && d.out_dim > 0, RLX_EINVAL,

@@ -1,5 +1,6 @@
-// sac_ens.hip -- the kernels tqc.hip and redq.hip share (sac_ens.h declares their launchers): the tanh-Gaussian sample of the
-// update, the policy's head gradient, a fixed-order mean, and the metrics with the entropy coefficient's Adam step.
+// sac_ens.hip -- the kernels tqc.hip, redq.hip and aqe.hip share (sac_ens.h declares their launchers): the tanh-Gaussian sample of
+// the update, the policy's head gradient, a fixed-order mean, the metrics with the entropy coefficient's Adam step, and -- for the
+// critics with several outputs (tqc.hip, aqe.hip) -- the row sum over all of a transition's values and a constant fill.
 #include "sac_ens.h"
 
 namespace rlx {
@@ -83,8 +84,8 @@ __global__ __launch_bounds__(256) void k_ens_mean(const float* __restrict__ v, i
 
 // metrics (rlx_sac_update_f32's order) and the entropy coefficient's gradient with its plain Adam step (tqc.py:188, :220;
 // redq.py:201, :253; the arithmetic of adam_body.h's adam_element without clipping).  q_row: per row the sum of TQC's T atoms
-// (q_div = E B N) or REDQ's min over the E critics (q_div = B) on (s, a~); lpc: logp [B].  steps != NULL (REDQ): [G] q_loss then [G]
-// gradient norm of the critic steps, added in index order (redq.py:244).
+// (q_div = E B N), of AQE's T heads (q_div = B T) or REDQ's min over the E critics (q_div = B) on (s, a~); lpc: logp [B].
+// steps != NULL (REDQ, AQE): [G] q_loss then [G] gradient norm of the critic steps, added in index order (redq.py:244).
 __global__ __launch_bounds__(256) void k_ens_finish(const float* __restrict__ q_row, int64_t q_div, const float* __restrict__ lpc, int64_t B,
                                                     const float* __restrict__ steps, int G, float* __restrict__ log_alpha,
                                                     float* __restrict__ am, float* __restrict__ av, float* __restrict__ metrics,
@@ -121,7 +122,32 @@ __global__ __launch_bounds__(256) void k_ens_finish(const float* __restrict__ q_
   log_alpha[0] = fmaf(-lr, (mi / bc1) / (sqrtf(vi / bc2) + eps), la);
 }
 
+// row_sum[b] = sum of the row's T values (one wave per transition): the policy loss's mean over all atoms / heads, per row
+__global__ __launch_bounds__(256) void k_ens_atom_rowsum(const float* __restrict__ atoms, float* __restrict__ row_sum, int64_t B, int N, int T) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + w;
+  if (b >= B) return;                                   // (whole waves leave: no workgroup barrier below)
+  const float v = wave_sum((lane < T ? ens_atom(atoms, b, lane, B, N) : 0.f) + (lane + 64 < T ? ens_atom(atoms, b, lane + 64, B, N) : 0.f));
+  if (lane == 0) row_sum[b] = v;
+}
+
+__global__ __launch_bounds__(256) void k_ens_fill(float* __restrict__ out, int64_t n, float v) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = v;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
+int ens_atom_rowsum(const float* atoms, float* row_sum, int64_t B, int N, int T, hipStream_t st) {
+  hipLaunchKernelGGL(k_ens_atom_rowsum, dim3(div_up(B, 4)), dim3(256), 0, st, atoms, row_sum, B, N, T);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int ens_fill(float* out, int64_t n, float v, hipStream_t st) {
+  hipLaunchKernelGGL(k_ens_fill, dim3(elem_grid(n)), dim3(256), 0, st, out, n, v);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
 int ens_sample(const float* head, SacSampleArgs sa, const EnsRowKeys& keys, int64_t B, hipStream_t st) {
   const int AP = ens_lanes_per_row(sa.A);
   sa.k0 = keys.k0; sa.k1 = keys.k1; sa.scheme = keys.scheme;

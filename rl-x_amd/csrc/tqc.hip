@@ -16,7 +16,7 @@
 //
 // Schedule of one update (one stream, no host synchronisation): policy on s' -> sample a', logp' -> E target chains -> k_tqc_target;
 // E online chains on (s, a) -> k_tqc_qloss -> E backward passes; policy on s -> sample a~, logp -> per critic: forward on (s, a~),
-// input gradient on the action columns from the constant seed -1 / (B T) -> k_ens_policy_grad -> policy backward; k_tqc_atom_rowsum, k_ens_finish
+// input gradient on the action columns from the constant seed -1 / (B T) -> k_ens_policy_grad -> policy backward; k_ens_atom_rowsum, k_ens_finish
 // (metrics, the entropy coefficient's Adam step); plain Adam of the policy; plain Adam of all E critics with the Polyak step.
 // The sample, the policy's head gradient, the means and the finish are sac_ens.hip's, shared with redq.hip; the noise keys are SAC's
 // schedule 0: keys = split(key, 2B+1), key = keys[0], next-state / current-state noise of row i from keys[1 + 2i] / keys[2 + 2i]
@@ -33,37 +33,8 @@ constexpr int TQC_MAXT = 128;   // two atoms per lane of one wave (c51.hip's cap
 constexpr int TQC_MAXE = 8;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-// Atom i = e N + n of row b lives at atoms[(e B + b) N + n]: critic-major, as E head GEMMs leave them.
-__device__ __forceinline__ float tqc_atom(const float* __restrict__ atoms, int64_t b, int i, int64_t B, int N) {
-  const int e = i / N;
-  return atoms[((int64_t)e * B + b) * N + (i - e * N)];
-}
-
-// Ascending bitonic sort of up to 128 values held two per lane: element index = lane + 64 slot.  Stages with a partner distance
-// below 64 exchange across lanes (__shfl_xor), the one stage at distance 64 exchanges the lane's own two slots.  Values only.
-template <int SLOTS>
-__device__ __forceinline__ void tqc_sort(float (&v)[2], int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64 * SLOTS; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j == 64) {   // (k == 128 only: every index has bit 7 clear, so the merge is ascending)
-        const float lo = fminf(v[0], v[1]), hi = fmaxf(v[0], v[1]);
-        v[0] = lo;
-        v[1] = hi;
-      } else {
-        const bool lower = (lane & j) == 0;
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-          const float o = __shfl_xor(v[s], j, 64);
-          const bool asc = ((lane + 64 * s) & k) == 0;
-          v[s] = (asc == lower) ? fminf(v[s], o) : fmaxf(v[s], o);
-        }
-      }
-    }
-  }
-}
-
+// Atom i = e N + n of row b lives at atoms[(e B + b) N + n] (ens_atom); the wave-level bitonic sort is ens_sort: both in sac_ens.h,
+// shared with aqe.hip.
 // y[b, k] = r_b + gamma (1 - term_b) (z_(k) - alpha logp'_b), k < K: the K smallest of the row's pooled T target atoms
 // (tqc.py:155-158).  One wave per transition, four per workgroup; absent lanes hold +inf, which sorts behind every atom.
 __global__ __launch_bounds__(256) void k_tqc_target(const float* __restrict__ zt, const float* __restrict__ rew, const float* __restrict__ term,
@@ -73,10 +44,10 @@ __global__ __launch_bounds__(256) void k_tqc_target(const float* __restrict__ zt
   const int64_t b = (int64_t)blockIdx.x * 4 + w;
   if (b >= B) return;                                   // (whole waves leave: no workgroup barrier below)
   float v[2];
-  v[0] = lane < T ? tqc_atom(zt, b, lane, B, N) : INFINITY;
-  v[1] = lane + 64 < T ? tqc_atom(zt, b, lane + 64, B, N) : INFINITY;
-  if (T > 64) tqc_sort<2>(v, lane);
-  else tqc_sort<1>(v, lane);
+  v[0] = lane < T ? ens_atom(zt, b, lane, B, N) : INFINITY;
+  v[1] = lane + 64 < T ? ens_atom(zt, b, lane + 64, B, N) : INFINITY;
+  if (T > 64) ens_sort<2>(v, lane);
+  else ens_sort<1>(v, lane);
   const float disc = gamma * (1.0f - term[b]);
   const float ent = expf(log_alpha[0]) * nlogp[b];
   const float r = rew[b];
@@ -94,7 +65,7 @@ __global__ __launch_bounds__(256) void k_tqc_qloss(const float* __restrict__ q, 
   const int64_t b = (int64_t)blockIdx.x * 4 + w;
   if (b >= B) return;                                   // (whole waves leave: no workgroup barrier below)
   const bool h0 = lane < T, h1 = lane + 64 < T;
-  const float q0 = h0 ? tqc_atom(q, b, lane, B, N) : 0.f, q1 = h1 ? tqc_atom(q, b, lane + 64, B, N) : 0.f;
+  const float q0 = h0 ? ens_atom(q, b, lane, B, N) : 0.f, q1 = h1 ? ens_atom(q, b, lane + 64, B, N) : 0.f;
   const float y0 = lane < K ? y[b * K + lane] : 0.f, y1 = lane + 64 < K ? y[b * K + lane + 64] : 0.f;
   const float tau0 = ((float)lane + 0.5f) / (float)T, tau1 = ((float)(lane + 64) + 0.5f) / (float)T;
   float l0 = 0.f, l1 = 0.f, g0 = 0.f, g1 = 0.f;
@@ -121,19 +92,6 @@ __global__ __launch_bounds__(256) void k_tqc_qloss(const float* __restrict__ q, 
   if (h1) dq[((int64_t)((lane + 64) / N) * B + b) * N + (lane + 64) % N] = gs * g1;
   const float loss = wave_sum((h0 ? l0 : 0.f) + (h1 ? l1 : 0.f));
   if (lane == 0) loss_row[b] = loss / kappa * inv_pairs;
-}
-
-// row_sum[b] = sum of the row's T atoms (one wave per transition): the policy loss's mean over all atoms, per row
-__global__ __launch_bounds__(256) void k_tqc_atom_rowsum(const float* __restrict__ atoms, float* __restrict__ row_sum, int64_t B, int N, int T) {
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t b = (int64_t)blockIdx.x * 4 + w;
-  if (b >= B) return;                                   // (whole waves leave: no workgroup barrier below)
-  const float v = wave_sum((lane < T ? tqc_atom(atoms, b, lane, B, N) : 0.f) + (lane + 64 < T ? tqc_atom(atoms, b, lane + 64, B, N) : 0.f));
-  if (lane == 0) row_sum[b] = v;
-}
-
-__global__ __launch_bounds__(256) void k_tqc_fill(float* __restrict__ out, int64_t n, float v) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -273,8 +231,8 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
   // seed d(-mean atoms) / d atom = -1 / (B T), the input gradient on the action columns
   rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kc, ctx->dbg_sac_eps[1], B, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tqc_fill, dim3(elem_grid((int64_t)BN)), dim3(256), 0, st, seed, (int64_t)BN, -1.0f / ((float)B * (float)T));
-  RLX_LAUNCH_CHECK();
+  rc = ens_fill(seed, (int64_t)BN, -1.0f / ((float)B * (float)T), st);
+  if (rc) return rc;
   {
     BwdPass bwd(ctx, B);   // the policy's head gradient is ~ 1 / B per sample (up to ~ 2 e^log_std_max |eps| alpha / B)
     rc = bwd.begin(E * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
@@ -296,10 +254,9 @@ int rlx_tqc_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
   const int64_t step = *opt_count_io + 1;
   float sched[3];
   adam_schedule_entry(sched, step, hp->lr_alpha, hp->adam_b1, hp->adam_b2);
-  hipLaunchKernelGGL(k_tqc_atom_rowsum, dim3(div_up(B, 4)), dim3(256), 0, st, (const float*)qa, qa_row, B, N, T);
-  RLX_LAUNCH_CHECK();
-  rc = ens_finish(qa_row, (int64_t)E * (int64_t)BN, lpc, B, nullptr, 0, log_alpha, am, av, metrics_out, hp->target_entropy, sched, hp->adam_b1,
-                  hp->adam_b2, hp->adam_eps, st);
+  rc = ens_atom_rowsum(qa, qa_row, B, N, T, st);
+  if (!rc) rc = ens_finish(qa_row, (int64_t)E * (int64_t)BN, lpc, B, nullptr, 0, log_alpha, am, av, metrics_out, hp->target_entropy, sched,
+                           hp->adam_b1, hp->adam_b2, hp->adam_eps, st);
   const PlainAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
   if (!rc) rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, step, hp->lr_policy, ahp, metrics_out + 6, st);
   if (!rc) rc = torch_clip_adam(qparams, gq, qm, qv, (int64_t)E * nq, sq, step, hp->lr_critic, ahp, metrics_out + 7, st, qtarget, hp->tau);

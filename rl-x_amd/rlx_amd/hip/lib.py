@@ -85,6 +85,14 @@ class RedqHparams(Structure):
         ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
 
 
+class AqeHparams(Structure):
+    """rlx_aqe_hparams (aqe/flax/default_config.py:9-28)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "tau", "target_entropy", "log_std_min", "log_std_max", "lr_policy", "lr_critic",
+                                       "lr_critic_delta", "lr_alpha", "adam_b1", "adam_b2", "adam_eps")] + [
+        ("ensemble_size", c_int32), ("nr_heads_per_net", c_int32), ("nr_dropped_q_values", c_int32), ("q_update_steps", c_int32),
+        ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
+
+
 class ReppoDesc(Structure):
     """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
     _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
@@ -258,6 +266,9 @@ _SIGNATURES = {
     "rlx_redq_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(RedqHparams)] + [c_void_p] * 6),
     "rlx_redq_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                             + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(RedqHparams), c_void_p, POINTER(c_int32), c_void_p]),
+    "rlx_aqe_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(AqeHparams)] + [c_void_p] * 6),
+    "rlx_aqe_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
+                           + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(AqeHparams), c_void_p, c_void_p]),
     "rlx_lstm_policy_param_count": (c_int64, [_LDESCP]),
     "rlx_ppo_lstm_rollout_begin": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p]),
     "rlx_ppo_lstm_act_f32": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int,
@@ -850,6 +861,31 @@ class Ctx:
             _ptr(metrics_out, f), sub, _stream()), "rlx_redq_update_f32")
         out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
         return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
+
+    # ---- AQE
+    def aqe_losses(self, q, q_next, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out=None, loss_out=None, qa=None,
+                   seed_out=None, meanq_out=None):
+        """AQE's two loss heads on given values (include/rlx_hip.h): q / q_next / dq_out / qa / seed_out [E, B, H]."""
+        f = self.torch.float32
+        _check(self.lib.rlx_aqe_losses_f32(self.h, _ptr(q, f, True), _ptr(q_next, f, True), _ptr(rewards, f), _ptr(terminations, f),
+                                           _ptr(next_logp, f), _ptr(log_alpha, f), _ptr(qa, f, True), int(rewards.shape[0]),
+                                           ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True), _ptr(loss_out, f, True),
+                                           _ptr(seed_out, f, True), _ptr(meanq_out, f, True), _stream()), "rlx_aqe_losses_f32")
+
+    def aqe_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
+                   metrics_out, scheme=THREEFRY_PARTITIONABLE):
+        """batch = (states [G, B, O], next_states, actions [G, B, A], rewards [G, B], terminations), G = hp.q_update_steps.
+        Returns (new_key, new_q_count, new_pi_count)."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
+        B = int(batch[3].numel()) // max(int(hp.q_update_steps), 1)
+        _check(self.lib.rlx_aqe_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
+            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
+            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
+            _ptr(metrics_out, f), _stream()), "rlx_aqe_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value
 
     # ---- PPO + LSTM
     def lstm_policy_param_count(self, desc):
