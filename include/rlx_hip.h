@@ -877,6 +877,58 @@ int rlx_aqe_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, floa
                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io /* += G */, int64_t* pi_opt_count_io /* += 1 */,
                        const rlx_aqe_hparams* hp, float* metrics_out /*DEVICE [10]*/, void* stream);
 
+/* ---- DroQ: dropout Q-functions (rl_x/algorithms/droq/flax) -----------------------------------------------------------------------
+ * REDQ's `update` (droq.py:144-261 is redq.py:144-261 plus dropout keys) over ensemble_size critics -- two by default -- whose EVERY
+ * hidden block is Dense -> Dropout -> LayerNorm -> ReLU (droq/flax/critic.py:25-35; flax's LayerNorm: eps 1e-6, scale and bias).
+ * THE CRITIC OF THIS ENTRY POINT IS LayerNorm-IN-EVERY-HIDDEN-BLOCK: qdesc is a rlx_mlp_desc under REDQ's descriptor rules (act =
+ * RLX_ACT_RELU, ln_first = 0, has_logstd = 0, out_dim = 1), and the FLAT LAYOUT of one critic is per hidden block W[in, out], b[out],
+ * LN scale[out], LN bias[out], then the head W[in, 1], b[1]; E critics BACK TO BACK.  Dropout has no parameters.  The policy is
+ * REDQ's.  Dropout is active in every critic pass (critic.py:28, :32: deterministic=False): the online critics', the selected
+ * targets' and the policy step's, input-gradient passes included.
+ * THE MASK STREAM IS THE LIBRARY'S OWN (flax's make_rng folds hashed module paths into the dropout key, which cannot be restated):
+ * for row b, the j-th network evaluated in a pass (from 0; a target pass of M networks uses j = 0 .. M - 1), hidden layer l of L,
+ * unit u of D:  row_key = split(step_key, count)[base + stride b];  net_key = split(row_key, E)[j] (nn.vmap splits the dropout rng
+ * over axis_size = ensemble_size, critic.py:50-57);  layer_key = split(net_key, L)[l];  kept iff uniform(layer_key, (D,))[u] < keep,
+ * keep = 1 - dropout_rate in float32 (jax.random.bernoulli); kept units are divided by keep, the others are 0.
+ * Envelope: REDQ's, with the critics' hidden widths multiples of 64 up to 768, 0 <= dropout_rate < 1, 3 B + 2 <= 2^31 - 1; a
+ * descriptor or size outside it is RLX_EUNSUP, every other bad argument RLX_EINVAL, rlx_last_error() names it.                     */
+typedef struct rlx_droq_hparams {              /* droq/flax/default_config.py:9-28: rlx_redq_hparams, then dropout_rate */
+  float gamma, tau, target_entropy, log_std_min, log_std_max;
+  float lr_policy, lr_critic, lr_critic_delta, lr_alpha;   /* as rlx_redq_hparams (droq.py:82-98) */
+  float adam_b1, adam_b2, adam_eps;
+  int32_t ensemble_size, in_target_minimization_size, q_update_steps;   /* droq.py:51-53; defaults 2, 2, 20 */
+  const float *critic_states, *critic_next_states;   /* [G, B, Oc] or NULL both */
+  float dropout_rate;                          /* default_config.py:20 (0.01); 0: no draws, a plain LayerNorm + ReLU block */
+} rlx_droq_hparams;
+
+/* test entry point: DEVICE flags_out [B, D] = 1 where the unit is kept, of the mask stream above for one (key layout, j, E, l, L, D,
+ * rate); key: the step key (HOST).  D a multiple of 64 up to 768; base + stride (B - 1) < count <= 2^31 - 1. */
+int rlx_droq_mask_u8(rlx_ctx*, const uint32_t key[2], int scheme, uint32_t base, uint32_t stride, uint32_t count, int j, int E, int l,
+                     int L, int64_t B, int D, float rate, uint8_t* flags_out, void* stream);
+
+/* test entry point: the fused Dropout -> LayerNorm -> ReLU block (critic.py:28-30, :32-34) on given values.  Z [M, D]: the Dense
+ * output, never written.  scale_bias [2 D]: LN scale then LN bias.  backward == 0: H_io [M, D] = relu(LN(mask Z / keep) scale + bias).
+ * backward != 0: H_io holds d L / d H and receives d L / d Z = (mask / keep) LNbwd(dH relu'), the mask regenerated from the keys;
+ * dg_out / db_out DEVICE [D]: the summed scale / bias gradients.  Keys and sizes as rlx_droq_mask_u8; rate 0 makes no draws. */
+int rlx_droq_block_f32(rlx_ctx*, const float* Z, float* H_io, const float* scale_bias, const uint32_t key[2], int scheme, uint32_t base,
+                       uint32_t stride, uint32_t count, int j, int E, int l, int L, int64_t M, int D, float rate, int backward,
+                       float* dg_out, float* db_out, void* stream);
+
+/* the whole jitted `update` (droq.py:144-261) in one call on one stream, no host synchronisation: rlx_redq_update_f32's arguments,
+ * schedule and metrics.  Critic step i: keys = split(key, 3 B + 2), key = keys[0], sample_key = keys[1] (the step's target subset,
+ * rlx_redq_subset_host's rule); row b's next-action noise from keys[2 + 3 b], the online critics' dropout from keys[3 + 3 b], the
+ * selected targets' from keys[4 + 3 b] (:229-236).  Policy step: keys = split(key, 2 B + 1), key = keys[0], row b's noise from
+ * keys[1 + 2 b], the E critics' dropout on (s_0, a~) from keys[2 + 2 b] (:247-250).  rlx_dbg_set_sac_noise keeps REDQ's meaning (the
+ * N(0, 1) draws only; the masks always come from the keys).  Adam and Polyak run over the whole flat critic vector, LayerNorm
+ * parameters included.  Nothing is written when a check fails. */
+int rlx_droq_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv,
+                        const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qtarget,
+                        float* log_alpha, float* am, float* av, const float* states /*[G,B,O]*/, const float* next_states,
+                        const float* actions, const float* rewards /*[G,B]*/, const float* terminations, int64_t B,
+                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io /* += G */, int64_t* pi_opt_count_io /* += 1 */,
+                        const rlx_droq_hparams* hp, float* metrics_out /*DEVICE [10]*/, int32_t* subsets_out /*HOST [G,M] or NULL*/,
+                        void* stream);
+
 /* =================================== REPPO ===============================================
  * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
  * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust

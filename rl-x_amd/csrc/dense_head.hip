@@ -1,8 +1,10 @@
 // dense_head.hip -- the kernels every network pass of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip and espo.hip shares (net_pass.h
 // declares their launchers): the dense heads (forward, input gradient, weight / bias gradient partials), the [obs | action] row concat,
-// the N(0, 1) noise block, and the row norm + activation kernels of a Block with their one launcher (norm_act).
+// the N(0, 1) noise block, and the row norm + activation kernels of a Block with their one launcher (norm_act), among them the
+// fused Dropout -> LayerNorm -> ReLU block of droq.hip's critics (k_drop_ln_relu).
 #include "ln_kernels.h"
 #include "net_pass.h"
+#include "sac_sample.h"
 
 namespace rlx {
 
@@ -245,6 +247,118 @@ __global__ __launch_bounds__(256) void k_mpo_ln_tanh(const float* __restrict__ Z
   ln_act_body<BWD, 8, RLX_ACT_TANH>(Z, Y, g, be, partials, M, D, RLX_ACT_TANH, MPO_LN_EPS);
 }
 
+// Dropout -> LayerNorm (flax: eps 1e-6, "fast variance") -> ReLU, forward / backward, over [M, D] (droq/flax/critic.py:27-30 and
+// :31-34 in one launch; ln_act_body's layout: one wave per row, four rows per workgroup, D % 64 == 0, D <= 64 NJMAX).
+//   fwd: z' = kept ? z / keep : 0; Y = relu(LN(z') g + be).  Z stays pre-dropout and nothing else is written.
+//   bwd: dY (in Y) -> dZ = (kept / keep) LNbwd(dY relu'); the statistics are recomputed from Z and the regenerated mask;
+//        per-workgroup partials [grid][2 D] of [dg | db], as ln_act_body leaves them.
+// The mask is no buffer: the row's layer key (three dependent threefry blocks, wave-uniform, droq_layer_key) is taken once per row
+// and every lane draws its own units' bits, one threefry block per element; a lane's flags are the bits of one register.
+// DROP = false makes no draws: a plain LayerNorm + ReLU block with ln_act_body's arithmetic.
+struct DropArgs { uint32_t k0, k1; int scheme; uint32_t base, stride, count, j, E, l, L; float keep; };
+template <bool BWD, int NJMAX, bool DROP>
+__global__ __launch_bounds__(256) void k_drop_ln_relu(const float* __restrict__ Z, float* __restrict__ Y, const float* __restrict__ g,
+                                                      const float* __restrict__ be, float* __restrict__ partials, int64_t M, int D,
+                                                      DropArgs da) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // bwd: [4][2*D]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int NJ = D >> 6;
+  float gam[NJMAX], bet[NJMAX], dg[NJMAX], db[NJMAX];
+#pragma unroll
+  for (int j = 0; j < NJMAX; ++j) {
+    gam[j] = j < NJ ? g[lane + 64 * j] : 0.f;
+    bet[j] = j < NJ ? be[lane + 64 * j] : 0.f;
+    dg[j] = db[j] = 0.f;
+  }
+  const float invD = 1.0f / (float)D;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + w; row < M; row += (int64_t)gridDim.x * 4) {
+    uint32_t kept = 0xffffffffu;   // bit j: unit lane + 64 j is kept
+    if (DROP) {
+      uint32_t lk0, lk1;
+      droq_layer_key(da.k0, da.k1, da.scheme, da.base + da.stride * (uint32_t)row, da.count, da.j, da.E, da.l, da.L, lk0, lk1);
+      kept = 0u;
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ && droq_unit_kept(lk0, lk1, da.scheme, (uint32_t)(lane + 64 * j), (uint32_t)D, da.keep)) kept |= 1u << j;
+    }
+    float z[NJMAX], dy[NJMAX];
+    float s = 0.f, ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j) {
+      z[j] = j < NJ ? Z[row * D + lane + 64 * j] : 0.f;
+      if (DROP) z[j] = (kept >> j) & 1u ? z[j] / da.keep : 0.f;
+      if (BWD) dy[j] = j < NJ ? Y[row * D + lane + 64 * j] : 0.f;
+      s += z[j];
+      ss += z[j] * z[j];
+    }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
+    const float mean = s * invD;
+    const float rstd = rsqrtf(fmaxf(0.f, ss * invD - mean * mean) + 1e-6f);
+    if (!BWD) {
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) Y[row * D + lane + 64 * j] = fmaxf((z[j] - mean) * rstd * gam[j] + bet[j], 0.f);
+    } else {
+      float m1 = 0.f, m2 = 0.f, xh[NJMAX], dxh[NJMAX];
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j) {
+        xh[j] = (z[j] - mean) * rstd;
+        const float yv = xh[j] * gam[j] + bet[j];
+        const float d = (j < NJ && yv > 0.f) ? dy[j] : 0.f;
+        dg[j] += d * xh[j];
+        db[j] += d;
+        dxh[j] = d * gam[j];
+        m1 += dxh[j];
+        m2 += dxh[j] * xh[j];
+      }
+      m1 = wave_sum(m1) * invD;
+      m2 = wave_sum(m2) * invD;
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) {
+          const float dz = rstd * (dxh[j] - m1 - xh[j] * m2);
+          Y[row * D + lane + 64 * j] = DROP ? ((kept >> j) & 1u ? dz / da.keep : 0.f) : dz;
+        }
+    }
+  }
+  if (BWD) {
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j)
+      if (j < NJ) {
+        smem[w * 2 * D + lane + 64 * j] = dg[j];
+        smem[w * 2 * D + D + lane + 64 * j] = db[j];
+      }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * D; i += 256)
+      partials[(int64_t)blockIdx.x * 2 * D + i] = (smem[i] + smem[2 * D + i]) + (smem[4 * D + i] + smem[6 * D + i]);
+  }
+}
+// the lean form holds D <= 256 (the reference's default width, droq/flax/default_config.py), the wide one D <= 768
+template <bool BWD>
+static int launch_drop_ln_relu(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, size_t lds,
+                               hipStream_t st, const DropKeys* dk) {
+  RLX_REQUIRE(o.drop >= 0.f && o.drop < 1.f, RLX_EINVAL, "norm_act: a block's dropout rate must be in [0, 1)");
+  RLX_REQUIRE(o.drop == 0.f || dk, RLX_EINVAL, "norm_act: a block with dropout needs the pass's dropout keys");
+  const int D = o.out;
+  DropArgs da{};
+  if (o.drop > 0.f)
+    da = DropArgs{dk->k0, dk->k1, dk->scheme, dk->base, dk->stride, dk->count, (uint32_t)dk->j, (uint32_t)dk->E, (uint32_t)dk->l,
+                  (uint32_t)dk->L, 1.0f - o.drop};
+#define RLX_DROP_LN(NJMAX, DROP) \
+  hipLaunchKernelGGL((k_drop_ln_relu<BWD, NJMAX, DROP>), dim3(grid), dim3(256), lds, st, Z, Y, p + o.g, p + o.be, part, M, D, da)
+  if (D <= 256) {
+    if (o.drop > 0.f) RLX_DROP_LN(4, true);
+    else RLX_DROP_LN(4, false);
+  } else {
+    if (o.drop > 0.f) RLX_DROP_LN(12, true);
+    else RLX_DROP_LN(12, false);
+  }
+#undef RLX_DROP_LN
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
 int fs_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int N, hipStream_t st) {
   hipLaunchKernelGGL(k_fs_head_fwd, dim3(div_up(M, 8), div_up(N, 128)), dim3(128), 0, st, H, W, b, out, M, K, N);
   RLX_LAUNCH_CHECK();
@@ -310,11 +424,14 @@ int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int sch
 }
 
 template <bool BWD>
-static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st) {
+static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
+                      const DropKeys* dk) {
   const int D = o.out;
   const size_t row = BWD ? (size_t)D * sizeof(float) : 0;   // LDS: four waves of [dg | db] (LayerNorm) or [dg] (RMSNorm)
   const bool ln = o.norm == NORM_LAYER, th = o.act == RLX_ACT_TANH;
   RLX_REQUIRE(D % 64 == 0 && D <= (th ? 512 : 768), RLX_EUNSUP, "norm_act: the row-norm kernels hold a row in one wave");
+  if (ln && o.act == RLX_ACT_RELU && o.eps == 1e-6f) return launch_drop_ln_relu<BWD>(o, p, Z, Y, part, grid, M, 8 * row, st, dk);
+  RLX_REQUIRE(o.drop == 0.f, RLX_EUNSUP, "norm_act: dropout has a kernel in front of (LayerNorm eps 1e-6, ReLU) only");
   if (ln && o.act == RLX_ACT_SILU)      // (the activation as a run-time argument: k_ln_act_wide takes the switch once per launch)
     hipLaunchKernelGGL(k_ln_act_wide<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.act, o.eps);
   else if (ln && th && o.eps == MPO_LN_EPS)
@@ -325,8 +442,9 @@ static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, 
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }
-int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st) {
-  return part ? norm_act_t<true>(o, p, Z, Y, part, grid, M, st) : norm_act_t<false>(o, p, Z, Y, part, grid, M, st);
+int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
+             const DropKeys* dk) {
+  return part ? norm_act_t<true>(o, p, Z, Y, part, grid, M, st, dk) : norm_act_t<false>(o, p, Z, Y, part, grid, M, st, dk);
 }
 
 }  // namespace rlx

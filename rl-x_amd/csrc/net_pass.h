@@ -1,6 +1,6 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip and redq.hip (the last two through
-// sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
-// themselves -- a Block (Linear -> {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip and droq.hip (the
+// last four through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
+// themselves -- a Block (Linear -> [Dropout ->] {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
 // of blocks, the streams, and what differs in the graph (REPPO's critic).
 // The epilogue rule of every input gradient (block_dx, head_bwd): the buffer it writes holds the output H of the block below; a
@@ -29,18 +29,25 @@ int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int sch
 // offsets in the flat parameter vector (-1: absent), in that order.  The flat layouts are ABI: make_block only advances `off`.
 enum NormKind { NORM_NONE = 0, NORM_LAYER = 1, NORM_RMS = 2 };
 constexpr float MPO_LN_EPS = 1e-5f;   // torch.nn.LayerNorm default (k_mpo_ln_tanh has it compiled in)
-struct Block { int in, out; int64_t W, b, g, be; int norm, act; float eps; };
-static inline Block make_block(int64_t& off, int in, int out, int norm = NORM_NONE, int act = RLX_ACT_NONE, float eps = 0.f) {
-  Block o{in, out, off, 0, -1, -1, norm, act, eps};
+// drop: the rate of a Dropout between the Linear and the norm (droq/flax/critic.py:27-30; 0: none).  It has no parameters.
+struct Block { int in, out; int64_t W, b, g, be; int norm, act; float eps; float drop; };
+static inline Block make_block(int64_t& off, int in, int out, int norm = NORM_NONE, int act = RLX_ACT_NONE, float eps = 0.f, float drop = 0.f) {
+  Block o{in, out, off, 0, -1, -1, norm, act, eps, drop};
   off += (int64_t)in * out;
   o.b = off; off += out;
   if (norm != NORM_NONE) { o.g = off; off += out; }
   if (norm == NORM_LAYER) { o.be = off; off += out; }
   return o;
 }
+// The dropout keys of one pass (sac_sample.h: droq_layer_key): row i of the pass draws from split((k0, k1), count)[base + stride i]
+// -- EnsRowKeys' addressing -- then part j of a split over the E vmapped networks, then part l of a split over the L hidden layers.
+// A chain fills l and L in; a pass over a block with drop > 0 needs one, a block with drop == 0 never reads it.
+struct DropKeys { uint32_t k0, k1; int scheme; uint32_t base, stride, count; int j, E; int l = 0, L = 1; };
 // row norm + activation of a block over [M, out] (dense_head.hip).  part == NULL: forward Y = act(norm(Z)); else backward: dY (in
-// Y) -> dZ, per-workgroup partials [grid][norm_part_width].  RLX_EUNSUP for a (norm, act) pair without a kernel.
-int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st);
+// Y) -> dZ, per-workgroup partials [grid][norm_part_width].  RLX_EUNSUP for a (norm, act) pair without a kernel, and for dropout
+// in front of any other pair than (LayerNorm eps 1e-6, ReLU).  Z stays pre-dropout: both directions regenerate the mask from dk.
+int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
+             const DropKeys* dk = nullptr);
 static inline int norm_part_width(const Block& o) { return (o.be >= 0 ? 2 : 1) * o.out; }   // [d scale | d bias] or [d scale]
 
 // ---- sizes and grids
@@ -159,20 +166,20 @@ static inline int first_layer_dx(rlx_ctx* ctx, const float* dZ, const float* W, 
 
 // ---- a block's passes.  x: the block's input [M, in] at row stride ldx; Z: pre-norm values (normed blocks only); H: output
 static inline int block_fwd(rlx_ctx* ctx, const Block& o, const float* p, const float* x, int ldx, float* Z, float* H, int64_t M,
-                            hipStream_t st) {
+                            hipStream_t st, const DropKeys* dk = nullptr) {
   if (o.norm == NORM_NONE) return launch_gemm_fwd(ctx, x, p + o.W, p + o.b, H, M, o.out, o.in, o.act, st, ldx, nullptr);
   const int rc = launch_gemm_fwd(ctx, x, p + o.W, p + o.b, Z, M, o.out, o.in, RLX_ACT_NONE, st, ldx, nullptr);
-  return rc ? rc : norm_act(o, p, Z, H, nullptr, rows_grid(ctx, M), M, st);
+  return rc ? rc : norm_act(o, p, Z, H, nullptr, rows_grid(ctx, M), M, st, dk);
 }
 // H holds dH of a normed block (-> dZ, in place) or dZ of a plain one (act' was applied by whoever wrote it).  grads != NULL: the
 // block's parameter gradients (flat layout) through the deferred reduction; the norm partial is taken either way.
 static inline int block_bwd(rlx_ctx* ctx, const Block& o, const float* p, const float* x, int ldx, const float* Z, float* H, float* grads,
-                            int64_t M, hipStream_t st) {
+                            int64_t M, hipStream_t st, const DropKeys* dk = nullptr) {
   if (o.norm != NORM_NONE) {
     const int grid = bwd_rows_grid(ctx, M);
     float* part = stage_alloc(ctx, (size_t)grid * norm_part_width(o));
     if (!part) return RLX_ENOMEM;
-    int rc = norm_act(o, p, Z, H, part, grid, M, st);
+    int rc = norm_act(o, p, Z, H, part, grid, M, st, dk);
     if (!rc && grads) rc = norm_bwd_reduce(ctx, part, grid, o.out, grads + o.g, o.be >= 0 ? grads + o.be : nullptr, st);
     if (rc) return rc;
   }
@@ -202,12 +209,12 @@ static inline int head_bwd(rlx_ctx* ctx, const Block& head, const Block* below, 
 // ---- a chain of blocks and a dense head
 struct Chain { int n_hidden; Block layer[4]; Block head; int64_t n_params; };
 // n_hidden blocks of one kind with the widths hidden[], then the head
-static inline Chain make_chain(int in, const int* hidden, int n_hidden, int out, int norm, int act, float eps = 0.f) {
+static inline Chain make_chain(int in, const int* hidden, int n_hidden, int out, int norm, int act, float eps = 0.f, float drop = 0.f) {
   Chain L{};
   L.n_hidden = n_hidden;
   int64_t off = 0;
   for (int l = 0; l < n_hidden; ++l) {
-    L.layer[l] = make_block(off, in, hidden[l], norm, act, eps);
+    L.layer[l] = make_block(off, in, hidden[l], norm, act, eps, drop);
     in = hidden[l];
   }
   L.head = make_block(off, in, out);
@@ -221,24 +228,37 @@ static inline void chain_carve(const Chain& L, int64_t M, Arena& a, ChainBufs* b
     b->H[l] = a.take((size_t)M * L.layer[l].out);
   }
 }
-// x: [M, in] at row stride ldx (a multiple of four, zero padded); head_out == NULL: the trunk only
+// the pass's dropout keys for hidden layer l of the chain (NULL stays NULL)
+static inline const DropKeys* chain_drop_keys(const Chain& L, const DropKeys* dk, int l, DropKeys* at) {
+  if (!dk) return nullptr;
+  *at = *dk;
+  at->l = l;
+  at->L = L.n_hidden;
+  return at;
+}
+// x: [M, in] at row stride ldx (a multiple of four, zero padded); head_out == NULL: the trunk only; dk: the pass's dropout keys
 static inline int chain_fwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, float* head_out,
-                            int64_t M, hipStream_t st) {
+                            int64_t M, hipStream_t st, const DropKeys* dk = nullptr) {
+  DropKeys at;
   for (int l = 0; l < L.n_hidden; ++l) {
-    const int rc = block_fwd(ctx, L.layer[l], p, l ? b.H[l - 1] : x, l ? L.layer[l].in : ldx, b.Z[l], b.H[l], M, st);
+    const int rc = block_fwd(ctx, L.layer[l], p, l ? b.H[l - 1] : x, l ? L.layer[l].in : ldx, b.Z[l], b.H[l], M, st,
+                             chain_drop_keys(L, dk, l, &at));
     if (rc) return rc;
   }
   if (!head_out) return RLX_OK;
   return fs_head_fwd(b.H[L.n_hidden - 1], p + L.head.W, p + L.head.b, head_out, M, L.head.in, L.head.out, st);
 }
 // backward from d_head [M, head.out]: the head step, then per block from the last: [norm backward, norm reduce], dW, dX.  The
-// buffers are consumed.  dx != NULL: the input gradient (row stride lddx; the columns [dx_c0, dx_c0 + dx_nc) only when dx_nc > 0)
+// buffers are consumed.  dx != NULL: the input gradient (row stride lddx; the columns [dx_c0, dx_c0 + dx_nc) only when dx_nc > 0).
+// dk: the dropout keys of the forward pass this one answers
 static inline int chain_bwd(rlx_ctx* ctx, const Chain& L, const float* p, const float* x, int ldx, const ChainBufs& b, const float* d_head,
-                            float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0) {
+                            float* grads, float* dx, int lddx, int64_t M, hipStream_t st, int dx_c0 = 0, int dx_nc = 0,
+                            const DropKeys* dk = nullptr) {
   int rc = head_bwd(ctx, L.head, &L.layer[L.n_hidden - 1], p, b.H[L.n_hidden - 1], d_head, grads, M, st);
+  DropKeys at;
   for (int l = L.n_hidden - 1; l >= 0 && !rc; --l) {
     const Block& o = L.layer[l];
-    rc = block_bwd(ctx, o, p, l ? b.H[l - 1] : x, l ? o.in : ldx, b.Z[l], b.H[l], grads, M, st);
+    rc = block_bwd(ctx, o, p, l ? b.H[l - 1] : x, l ? o.in : ldx, b.Z[l], b.H[l], grads, M, st, chain_drop_keys(L, dk, l, &at));
     if (rc) return rc;
     if (l > 0) rc = block_dx(ctx, o, &L.layer[l - 1], p, b.H[l], b.H[l - 1], M, st);
     else if (dx) rc = first_layer_dx(ctx, b.H[l], p + o.W, dx, lddx, M, o.out, o.in, dx_c0, dx_nc, st);

@@ -28,12 +28,10 @@
 // counter) -> Adam of the policy.  The k_ens_* kernels are sac_ens.hip's, shared with tqc.hip.
 // Every reduction runs in a fixed order without atomics: two identical calls give identical bits.
 // CPU twin: tests/redq_twin.py (float64).  The reference's REDQ is JAX only; see DESIGN.md 4.5e for what is pinned.
-#include "sac_ens.h"
+// The update's body is redq_loop (redq_loop.h), which droq.hip calls too with LayerNorm / dropout critics and its own key layout.
+#include "redq_loop.h"
 
 namespace rlx {
-
-constexpr int REDQ_MAXE = 16;
-constexpr int REDQ_MAXG = 64;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
 // One thread per transition (redq.py:163-169): y_b = r_b + gamma (1 - term_b) (min_m qn[m, b] - alpha logp'_b) over the M selected
@@ -74,14 +72,14 @@ __global__ __launch_bounds__(256) void k_redq_policy_seed(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-// ensemble_size E, in_target_minimization_size M, q_update_steps G (redq/flax/default_config.py:18-20)
-static int redq_check_hp(const rlx_redq_hparams& hp) {
-  RLX_REQUIRE(hp.ensemble_size >= 1, RLX_EINVAL, "redq: hp->ensemble_size must be at least 1");
-  RLX_REQUIRE(hp.ensemble_size <= REDQ_MAXE, RLX_EUNSUP, "redq: hp->ensemble_size at most 16");
+int redq_check_hp(const rlx_redq_hparams& hp, const char* algo) {
+  const std::string a(algo);
+  RLX_REQUIRE(hp.ensemble_size >= 1, RLX_EINVAL, a + ": hp->ensemble_size must be at least 1");
+  RLX_REQUIRE(hp.ensemble_size <= REDQ_MAXE, RLX_EUNSUP, a + ": hp->ensemble_size at most 16");
   RLX_REQUIRE(hp.in_target_minimization_size >= 1 && hp.in_target_minimization_size <= hp.ensemble_size, RLX_EINVAL,
-              "redq: hp->in_target_minimization_size must be in [1, ensemble_size]");
-  RLX_REQUIRE(hp.q_update_steps >= 1, RLX_EINVAL, "redq: hp->q_update_steps must be at least 1");
-  RLX_REQUIRE(hp.q_update_steps <= REDQ_MAXG, RLX_EUNSUP, "redq: hp->q_update_steps at most 64");
+              a + ": hp->in_target_minimization_size must be in [1, ensemble_size]");
+  RLX_REQUIRE(hp.q_update_steps >= 1, RLX_EINVAL, a + ": hp->q_update_steps must be at least 1");
+  RLX_REQUIRE(hp.q_update_steps <= REDQ_MAXG, RLX_EUNSUP, a + ": hp->q_update_steps at most 64");
   return RLX_OK;
 }
 
@@ -123,70 +121,45 @@ static int redq_critic_loss(const float* q, const float* qn, const float* rew, c
   return loss_out ? ens_mean(loss_row, B, loss_out, st) : RLX_OK;
 }
 
-}  // namespace rlx
-
-using namespace rlx;
-
-extern "C" {
-
-int rlx_redq_subset_host(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out) {
-  RLX_REQUIRE(sample_key && idx_out, RLX_EINVAL, "rlx_redq_subset_host: NULL pointer");
-  RLX_REQUIRE(E >= 1 && E <= REDQ_MAXE, RLX_EINVAL, "rlx_redq_subset_host: E must be in [1, 16]");
-  RLX_REQUIRE(M >= 1 && M <= E, RLX_EINVAL, "rlx_redq_subset_host: M must be in [1, E]");
-  redq_subset(sample_key, E, M, scheme, idx_out);
-  return RLX_OK;
+// the dropout keys of network j's pass in a step (NULL without dropout: the chain then never reads them)
+static const DropKeys* redq_drop_keys(const RedqLoopSpec& spec, const uint32_t step_key[2], int scheme, RedqKeySlot slot, uint32_t count,
+                                      int j, int E, DropKeys* at) {
+  if (!(spec.critic_drop > 0.f)) return nullptr;
+  *at = DropKeys{step_key[0], step_key[1], scheme, slot.base, slot.stride, count, j, E};
+  return at;
 }
 
-int rlx_redq_losses_f32(rlx_ctx* ctx, const float* q, const float* q_next_sel, const float* rewards, const float* terminations,
-                        const float* next_logp, const float* log_alpha, const float* qa, int64_t B, const rlx_redq_hparams* hp, float* y_out,
-                        float* dq_out, float* loss_out, float* seed_out, float* minq_out, void* stream) {
-  RLX_REQUIRE(ctx && hp, RLX_EINVAL, "rlx_redq_losses_f32: ctx / hp is NULL");
-  RLX_REQUIRE(q && q_next_sel && rewards && terminations && next_logp && log_alpha, RLX_EINVAL,
-              "rlx_redq_losses_f32: NULL input (q, q_next_sel, rewards, terminations, next_logp, log_alpha)");
-  RLX_REQUIRE(dq_out, RLX_EINVAL, "rlx_redq_losses_f32: dq_out is NULL");
-  RLX_REQUIRE(!qa || seed_out, RLX_EINVAL, "rlx_redq_losses_f32: qa needs seed_out");
-  RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_losses_f32: B must be positive");
-  const int rc = redq_check_hp(*hp);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  float* loss_row = nullptr;
-  if (loss_out) {
-    loss_row = (float*)scratch(ctx, SL_STAGE, a64((size_t)B) * sizeof(float));
-    if (!loss_row) return RLX_ENOMEM;
-  }
-  const int E = hp->ensemble_size, M = hp->in_target_minimization_size;
-  const int rc2 = redq_critic_loss(q, q_next_sel, rewards, terminations, next_logp, log_alpha, B, E, M, hp->gamma, y_out, dq_out, loss_row,
-                                   loss_out, st);
-  if (rc2 || !qa) return rc2;
-  hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, qa, seed_out, minq_out, B, E);
-  RLX_LAUNCH_CHECK();
-  return RLX_OK;
-}
-
-int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* qdesc,
-                        float* qparams, float* qm, float* qv, float* qtarget, float* log_alpha, float* am, float* av, const float* states,
-                        const float* next_states, const float* actions, const float* rewards, const float* terminations, int64_t B,
-                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_redq_hparams* hp,
-                        float* metrics_out, int32_t* subsets_out, void* stream) {
+int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv,
+              const rlx_mlp_desc* qdesc, float* qparams, float* qm, float* qv, float* qtarget, float* log_alpha, float* am, float* av,
+              const float* states, const float* next_states, const float* actions, const float* rewards, const float* terminations,
+              int64_t B, uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_redq_hparams* hp,
+              float* metrics_out, int32_t* subsets_out, void* stream) {
+  const std::string fn(spec.fn);
   RLX_REQUIRE(ctx && pdesc && pparams && pm && pv && qdesc && qparams && qm && qv && qtarget && log_alpha && am && av && states &&
                   next_states && actions && rewards && terminations && key_io && q_opt_count_io && pi_opt_count_io && hp && metrics_out,
-              RLX_EINVAL, "rlx_redq_update_f32: NULL pointer");
-  RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_update_f32: B must be positive");
-  RLX_REQUIRE(B + 2 <= 0x7fffffffLL, RLX_EUNSUP, "rlx_redq_update_f32: B too large for the 32-bit key count B + 2");
-  int rc = ens_check_net(*pdesc, "redq", "pdesc");
+              RLX_EINVAL, fn + ": NULL pointer");
+  RLX_REQUIRE(B > 0, RLX_EINVAL, fn + ": B must be positive");
+  const int64_t kc = spec.critic_keys_per_row, kp = spec.policy_keys_per_row;
+  RLX_REQUIRE(B <= (0x7fffffffLL - 2) / kc, RLX_EUNSUP,
+              fn + ": B too large for the 32-bit key count " + (kc == 1 ? std::string("B + 2") : std::to_string(kc) + " B + 2"));
+  int rc = ens_check_net(*pdesc, spec.algo, "pdesc");
   if (rc) return rc;
-  rc = ens_check_net(*qdesc, "redq", "qdesc");
+  rc = ens_check_net(*qdesc, spec.algo, "qdesc");
   if (rc) return rc;
-  rc = redq_check_hp(*hp);
+  rc = redq_check_hp(*hp, spec.algo);
   if (rc) return rc;
   const int E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps;
   EnsDims d;
-  rc = ens_prologue("rlx_redq_update_f32", *pdesc, *qdesc, 1, "must be 1", states, next_states, hp->critic_states, hp->critic_next_states, &d);
+  rc = ens_prologue(spec.fn, *pdesc, *qdesc, 1, "must be 1", states, next_states, hp->critic_states, hp->critic_next_states, &d);
   if (rc) return rc;
   const int A = d.A, Op = d.Op, Oc = d.Oc, ldc = d.ldc, ldp = d.ldp;
   hipStream_t st = (hipStream_t)stream;
   bx_release_all(ctx);
-  const Chain LP = ens_layout(*pdesc), LQ = ens_layout(*qdesc);
+  const Chain LP = ens_layout(*pdesc);
+  const Chain LQ = make_chain(qdesc->in_dim, qdesc->hidden, qdesc->n_hidden, qdesc->out_dim, spec.critic_norm, RLX_ACT_RELU, spec.critic_eps,
+                              spec.critic_drop);
+  const uint32_t count_c = (uint32_t)(kc * B + 2), count_p = (uint32_t)(kp * B + 1);   // the split counts of a critic / the policy step
+  DropKeys dk;
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
   // ---- arena: the policy's passes, one buffer set for the targets' inference passes, E sets for the online critics: their backward
   // waits for the loss in a critic step and for the seed -- which needs all E values -- in the policy step
@@ -218,15 +191,15 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     uint32_t nxt[2], sample_key[2];
     step_key[i][0] = key[0];
     step_key[i][1] = key[1];
-    split_at_host(key, 0, (uint32_t)(B + 2), scheme, nxt);
-    split_at_host(key, 1, (uint32_t)(B + 2), scheme, sample_key);
+    split_at_host(key, 0, count_c, scheme, nxt);
+    split_at_host(key, 1, count_c, scheme, sample_key);
     redq_subset(sample_key, E, M, scheme, subset[i]);
     key[0] = nxt[0];
     key[1] = nxt[1];
   }
   step_key[G][0] = key[0];
   step_key[G][1] = key[1];
-  split_at_host(step_key[G], 0, (uint32_t)(B + 1), scheme, key);
+  split_at_host(step_key[G], 0, count_p, scheme, key);
   BxReleaseAll bx_all{ctx};
   const SacSampleArgs sa = ens_sample_args(d, hp->log_std_min, hp->log_std_max, B);
   const PlainAdamHp ahp{0.f, hp->adam_b1, hp->adam_b2, hp->adam_eps};
@@ -247,19 +220,24 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
       if (rc) return rc;
     }
     // a', logp' from the policy on s'; the M selected targets on (s', a'); the E online critics on (s, a)
-    const EnsRowKeys ki{step_key[i][0], step_key[i][1], scheme, 2u, 1u, (uint32_t)(B + 2)};
+    const EnsRowKeys ki{step_key[i][0], step_key[i][1], scheme, spec.next_noise.base, spec.next_noise.stride, count_c};
     rc = ens_policy_sample(ctx, d, LP, pparams, cn_i, s2_i, xn, xsn, bpn, hn, lpn, sa, ki,
                            ctx->dbg_sac_eps[0] ? ctx->dbg_sac_eps[0] + (size_t)i * B * A : nullptr, B, st);
-    for (int m = 0; m < M && !rc; ++m) rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + (size_t)m * B, B, st);
+    for (int m = 0; m < M && !rc; ++m)   // (the m-th selected target is network m of its vmapped pass)
+      rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + (size_t)m * B, B, st,
+                     redq_drop_keys(spec, step_key[i], scheme, spec.target_drop, count_c, m, E, &dk));
     if (!rc) rc = fs_concat(cs_i, Oc, a_i, A, xc, ldc, B, st);
-    for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + (size_t)e * B, B, st);
+    for (int e = 0; e < E && !rc; ++e)
+      rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + (size_t)e * B, B, st,
+                     redq_drop_keys(spec, step_key[i], scheme, spec.online_drop, count_c, e, E, &dk));
     if (!rc) rc = redq_critic_loss(q, qn, rewards + (size_t)i * B, terminations + (size_t)i * B, lpn, log_alpha, B, E, M, hp->gamma, y, dq,
                                    loss_row, steps + i, st);
     // one deferred reduction per critic; the split-operand gradient scale is that of B E rows: |d loss / d q| is ~ 2 |q - y| / (B E)
     for (int e = 0; e < E && !rc; ++e) {
       BwdPass bwd(ctx, B * E);
       rc = bwd.begin(chain_stage_floats(ctx, LQ, B, true));
-      if (!rc) rc = chain_bwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], dq + (size_t)e * B, gq + e * nq, nullptr, 0, B, st);
+      if (!rc) rc = chain_bwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], dq + (size_t)e * B, gq + e * nq, nullptr, 0, B, st, 0, 0,
+                              redq_drop_keys(spec, step_key[i], scheme, spec.online_drop, count_c, e, E, &dk));
       if (!rc) rc = bwd.finish(st);
     }
     // plain Adam of all E critics with the Polyak step (redq.py:238-239), at this step's learning rate and count
@@ -277,9 +255,11 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     rc = trunk_images(ctx, nets, n, B, st);
     if (rc) return rc;
   }
-  const EnsRowKeys kp{step_key[G][0], step_key[G][1], scheme, 1u, 1u, (uint32_t)(B + 1)};
-  rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kp, ctx->dbg_sac_eps[1], B, st);
-  for (int e = 0; e < E && !rc; ++e) rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + (size_t)e * B, B, st);
+  const EnsRowKeys kpol{step_key[G][0], step_key[G][1], scheme, spec.cur_noise.base, spec.cur_noise.stride, count_p};
+  rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kpol, ctx->dbg_sac_eps[1], B, st);
+  for (int e = 0; e < E && !rc; ++e)
+    rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + (size_t)e * B, B, st,
+                   redq_drop_keys(spec, step_key[G], scheme, spec.policy_drop, count_p, e, E, &dk));
   if (rc) return rc;
   hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, (const float*)qa, seed, minq_row, B, E);
   RLX_LAUNCH_CHECK();
@@ -287,9 +267,10 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     BwdPass bwd(ctx, B);   // the critics' seeds are 0 or -1 / (B n_ties); the policy's head gradient is ~ 1 / B per sample
     rc = bwd.begin(E * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
     for (int e = 0; e < E && !rc; ++e)
-      rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + (size_t)e * B, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A);
+      rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + (size_t)e * B, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A,
+                     redq_drop_keys(spec, step_key[G], scheme, spec.policy_drop, count_p, e, E, &dk));
     if (rc) return rc;
-    rc = ens_policy_grad(hc, xp, ldc, Oc, da, ldc, (int64_t)B * ldc, E, log_alpha, kp, dpi, B, A, hp->log_std_min, hp->log_std_max,
+    rc = ens_policy_grad(hc, xp, ldc, Oc, da, ldc, (int64_t)B * ldc, E, log_alpha, kpol, dpi, B, A, hp->log_std_min, hp->log_std_max,
                          ctx->dbg_sac_eps[1], st);
     if (!rc) rc = chain_bwd(ctx, LP, pparams, xsc, ldp, bpc, dpi, gp, nullptr, 0, B, st);
     if (!rc) rc = bwd.finish(st);
@@ -311,6 +292,57 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
     for (int i = 0; i < G; ++i)
       for (int m = 0; m < M; ++m) subsets_out[i * M + m] = subset[i][m];
   return RLX_OK;
+}
+
+}  // namespace rlx
+
+using namespace rlx;
+
+extern "C" {
+
+int rlx_redq_subset_host(const uint32_t sample_key[2], int E, int M, int scheme, int32_t* idx_out) {
+  RLX_REQUIRE(sample_key && idx_out, RLX_EINVAL, "rlx_redq_subset_host: NULL pointer");
+  RLX_REQUIRE(E >= 1 && E <= REDQ_MAXE, RLX_EINVAL, "rlx_redq_subset_host: E must be in [1, 16]");
+  RLX_REQUIRE(M >= 1 && M <= E, RLX_EINVAL, "rlx_redq_subset_host: M must be in [1, E]");
+  redq_subset(sample_key, E, M, scheme, idx_out);
+  return RLX_OK;
+}
+
+int rlx_redq_losses_f32(rlx_ctx* ctx, const float* q, const float* q_next_sel, const float* rewards, const float* terminations,
+                        const float* next_logp, const float* log_alpha, const float* qa, int64_t B, const rlx_redq_hparams* hp, float* y_out,
+                        float* dq_out, float* loss_out, float* seed_out, float* minq_out, void* stream) {
+  RLX_REQUIRE(ctx && hp, RLX_EINVAL, "rlx_redq_losses_f32: ctx / hp is NULL");
+  RLX_REQUIRE(q && q_next_sel && rewards && terminations && next_logp && log_alpha, RLX_EINVAL,
+              "rlx_redq_losses_f32: NULL input (q, q_next_sel, rewards, terminations, next_logp, log_alpha)");
+  RLX_REQUIRE(dq_out, RLX_EINVAL, "rlx_redq_losses_f32: dq_out is NULL");
+  RLX_REQUIRE(!qa || seed_out, RLX_EINVAL, "rlx_redq_losses_f32: qa needs seed_out");
+  RLX_REQUIRE(B > 0, RLX_EINVAL, "rlx_redq_losses_f32: B must be positive");
+  const int rc = redq_check_hp(*hp, "redq");
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* loss_row = nullptr;
+  if (loss_out) {
+    loss_row = (float*)scratch(ctx, SL_STAGE, a64((size_t)B) * sizeof(float));
+    if (!loss_row) return RLX_ENOMEM;
+  }
+  const int E = hp->ensemble_size, M = hp->in_target_minimization_size;
+  const int rc2 = redq_critic_loss(q, q_next_sel, rewards, terminations, next_logp, log_alpha, B, E, M, hp->gamma, y_out, dq_out, loss_row,
+                                   loss_out, st);
+  if (rc2 || !qa) return rc2;
+  hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, qa, seed_out, minq_out, B, E);
+  RLX_LAUNCH_CHECK();
+  return RLX_OK;
+}
+
+int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* qdesc,
+                        float* qparams, float* qm, float* qv, float* qtarget, float* log_alpha, float* am, float* av, const float* states,
+                        const float* next_states, const float* actions, const float* rewards, const float* terminations, int64_t B,
+                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_redq_hparams* hp,
+                        float* metrics_out, int32_t* subsets_out, void* stream) {
+  // one key per row: keys[2 + b] of B + 2 in a critic step, keys[1 + b] of B + 1 in the policy step; plain ReLU critics, no dropout
+  const RedqLoopSpec spec{"rlx_redq_update_f32", "redq", NORM_NONE, 0.f, 0.f, 1u, 1u, {2u, 1u}, {0u, 0u}, {0u, 0u}, {1u, 1u}, {0u, 0u}};
+  return redq_loop(ctx, spec, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, states, next_states, actions,
+                   rewards, terminations, B, key_io, scheme, q_opt_count_io, pi_opt_count_io, hp, metrics_out, subsets_out, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// sac_ens.h -- what tqc.hip, redq.hip and aqe.hip share: SAC's tanh-Gaussian policy and entropy coefficient over an ensemble of E
-// plain-ReLU critics on net_pass.h.  The kernels and their launchers are in sac_ens.hip; here are their declarations, the device
+// sac_ens.h -- what tqc.hip, redq.hip, aqe.hip and droq.hip share: SAC's tanh-Gaussian policy and entropy coefficient over an ensemble of E
+// ReLU critics (plain; droq.hip's with Dropout and LayerNorm in every hidden block) on net_pass.h.  The kernels and their launchers are in sac_ens.hip; here are their declarations, the device
 // helpers of the multi-output critics (value indexing, the wave-level bitonic sort) and the host helpers of an entry point: the
 // descriptor rules, the shapes of a call, host key splitting, and the policy pass that ends in a sample.  An algorithm's file keeps
 // its critic target and loss, its hyper-parameter check, its arena carve and its schedule.
@@ -10,7 +10,8 @@
 namespace rlx {
 
 // the noise key of row i: split((k0, k1), count)[base + stride * i].  TQC is SAC's schedule 0 (sac_sample.h): (1 or 2, 2, 2B + 1);
-// REDQ: (2, 1, B + 2) in a critic step, (1, 1, B + 1) in the policy step.  AQE: (1, 1, B + 1) in every step.
+// REDQ: (2, 1, B + 2) in a critic step, (1, 1, B + 1) in the policy step.  AQE: (1, 1, B + 1) in every step.  DroQ: (2, 3, 3B + 2)
+// and (1, 2, 2B + 1); its dropout keys sit beside them (redq_loop.h, net_pass.h: DropKeys).
 struct EnsRowKeys { uint32_t k0, k1; int scheme; uint32_t base, stride, count; };
 
 // ---- sac_ens.hip

@@ -29,6 +29,29 @@ __host__ __device__ __forceinline__ void split_key_at(uint32_t k0, uint32_t k1, 
   }
 }
 
+// ---- DroQ's dropout masks (droq.hip; the project's own stream).  The reference hands every row of a critic pass
+// its own dropout key (droq.py:229-230, :247-248: the EnsRowKeys addressing), flax's nn.vmap splits it over the ensemble_size
+// critics (droq/flax/critic.py:50-57) and nn.Dropout keeps a unit iff uniform < keep (jax.random.bernoulli).  What flax does
+// between those two -- make_rng folds hashed module paths in -- is replaced by one more split, over the hidden layers:
+//   row_key = split(step_key, count)[idx]; net_key = split(row_key, E)[j]; layer_key = split(net_key, L)[l]
+//   unit u of D is kept iff bits_to_unit(random_bits(layer_key, (D,))[u]) < keep
+__host__ __device__ __forceinline__ void droq_layer_key(uint32_t k0, uint32_t k1, int scheme, uint32_t idx, uint32_t count, uint32_t j,
+                                                        uint32_t E, uint32_t l, uint32_t L, uint32_t& o0, uint32_t& o1) {
+  uint32_t r0, r1, n0, n1;
+  split_key_at(k0, k1, idx, count, scheme, r0, r1);
+  split_key_at(r0, r1, j, E, scheme, n0, n1);
+  split_key_at(n0, n1, l, L, scheme, o0, o1);
+}
+__host__ __device__ __forceinline__ bool droq_unit_kept(uint32_t lk0, uint32_t lk1, int scheme, uint32_t u, uint32_t D, float keep) {
+  return bits_to_unit(random_bits_at(lk0, lk1, (uint64_t)u, (uint64_t)D, scheme)) < keep;
+}
+// the whole mask stream for one unit (k_droq_mask); k_drop_ln_relu takes the layer key once per row and asks droq_unit_kept
+__host__ __device__ __forceinline__ bool droq_keep_at(uint32_t k0, uint32_t k1, int scheme, uint32_t idx, uint32_t count, uint32_t j,
+                                                      uint32_t E, uint32_t l, uint32_t L, uint32_t u, uint32_t D, float keep) {
+  uint32_t a, b;
+  droq_layer_key(k0, k1, scheme, idx, count, j, E, l, L, a, b);
+  return droq_unit_kept(a, b, scheme, u, D, keep);
+}
 
 // everything k_sac_sample needs besides the head output (see its comment in sac.hip for the modes)
 struct SacSampleArgs {

@@ -93,6 +93,11 @@ class AqeHparams(Structure):
         ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
 
 
+class DroqHparams(Structure):
+    """rlx_droq_hparams (droq/flax/default_config.py:9-28): RedqHparams' fields, then dropout_rate"""
+    _fields_ = RedqHparams._fields_ + [("dropout_rate", c_float)]
+
+
 class ReppoDesc(Structure):
     """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
     _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
@@ -269,6 +274,12 @@ _SIGNATURES = {
     "rlx_aqe_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(AqeHparams)] + [c_void_p] * 6),
     "rlx_aqe_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                            + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(AqeHparams), c_void_p, c_void_p]),
+    "rlx_droq_mask_u8": (c_int, [c_void_p, _U32P, c_int, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_int, c_int64, c_int, c_float,
+                                 c_void_p, c_void_p]),
+    "rlx_droq_block_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int,
+                                   c_int, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "rlx_droq_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
+                            + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(DroqHparams), c_void_p, POINTER(c_int32), c_void_p]),
     "rlx_lstm_policy_param_count": (c_int64, [_LDESCP]),
     "rlx_ppo_lstm_rollout_begin": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p]),
     "rlx_ppo_lstm_act_f32": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int,
@@ -886,6 +897,43 @@ class Ctx:
             *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
             _ptr(metrics_out, f), _stream()), "rlx_aqe_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value
+
+    # ---- DroQ
+    def droq_mask(self, key, layout, j, E, l, L, B, D, rate, scheme=THREEFRY_PARTITIONABLE):
+        """The dropout keep flags (include/rlx_hip.h: the mask stream) of B rows under layout = (base, stride, count) of the step key
+        `key`, for the j-th of E networks and hidden layer l of L with D units -> torch.uint8 [B, D] on the device."""
+        out = self.torch.zeros(int(B), int(D), dtype=self.torch.uint8, device=self.device)
+        base, stride, count = (int(x) for x in layout)
+        _check(self.lib.rlx_droq_mask_u8(self.h, _key_arr(key), scheme, base, stride, count, int(j), int(E), int(l), int(L), int(B), int(D),
+                                         float(rate), _ptr(out, self.torch.uint8), _stream()), "rlx_droq_mask_u8")
+        return out
+
+    def droq_block(self, Z, H_io, scale_bias, key, layout, j, E, l, L, rate, scheme=THREEFRY_PARTITIONABLE, dg_out=None, db_out=None):
+        """The fused Dropout -> LayerNorm -> ReLU block on Z [M, D] (never written).  Forward (dg_out is None): H_io receives the block's
+        output.  Backward: H_io holds dH and receives dZ, dg_out / db_out [D] the scale / bias gradients."""
+        f = self.torch.float32
+        base, stride, count = (int(x) for x in layout)
+        M, D = (int(x) for x in Z.shape)
+        _check(self.lib.rlx_droq_block_f32(self.h, _ptr(Z, f), _ptr(H_io, f), _ptr(scale_bias, f), _key_arr(key), scheme, base, stride, count,
+                                           int(j), int(E), int(l), int(L), M, D, float(rate), 0 if dg_out is None else 1,
+                                           _ptr(dg_out, f, True), _ptr(db_out, f, True), _stream()), "rlx_droq_block_f32")
+
+    def droq_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
+                    metrics_out, scheme=THREEFRY_PARTITIONABLE, subsets=False):
+        """redq_update's arguments and results; the critics' flat layout has LayerNorm scale and bias in every hidden block."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
+        G, M = max(int(hp.q_update_steps), 0), max(int(hp.in_target_minimization_size), 0)
+        sub = (c_int32 * max(G * M, 1))() if subsets else None
+        B = int(batch[3].numel()) // max(G, 1)
+        _check(self.lib.rlx_droq_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
+            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
+            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
+            _ptr(metrics_out, f), sub, _stream()), "rlx_droq_update_f32")
+        out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
+        return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
 
     # ---- PPO + LSTM
     def lstm_policy_param_count(self, desc):
