@@ -1,6 +1,6 @@
 // droq.hip -- DroQ, dropout Q-functions (rl_x/algorithms/droq/flax/droq.py:144-261): REDQ's high update-to-data `update` over critics
 // whose hidden blocks are Dense -> Dropout -> LayerNorm -> ReLU (droq/flax/critic.py:25-35), by default two of them.  The update is
-// redq.hip's redq_loop (redq_loop.h) -- target min over the M selected networks, the loss mean over batch and ensemble, plain Adam and
+// redq.hip's redq_loop (redq_loop.h; redq.hip's header describes the schedule) -- target min over the M selected networks, the loss mean over batch and ensemble, plain Adam and
 // Polyak per step over the whole flat critic vector (LayerNorm parameters included), the policy loss on the min over all E with
 // the tie split, two counters, metrics [10] -- with what differs stated as a RedqLoopSpec:
 //   critic   make_chain(..., NORM_LAYER, RLX_ACT_RELU, 1e-6f, dropout_rate): per hidden block W, b, LN scale, LN bias, then the head W,
@@ -93,8 +93,8 @@ int rlx_droq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
                              hp->lr_critic_delta, hp->lr_alpha, hp->adam_b1, hp->adam_b2, hp->adam_eps, hp->ensemble_size,
                              hp->in_target_minimization_size, hp->q_update_steps, hp->critic_states, hp->critic_next_states};
   // three keys per row in a critic step (noise, online dropout, target dropout), two in the policy step (noise, dropout)
-  const RedqLoopSpec spec{"rlx_droq_update_f32", "droq", NORM_LAYER, 1e-6f, hp->dropout_rate, 3u, 2u,
-                          {2u, 3u}, {3u, 3u}, {4u, 3u}, {1u, 2u}, {2u, 2u}};
+  const RedqLoopSpec spec{"rlx_droq_update_f32", "droq", NORM_LAYER, 1e-6f, hp->dropout_rate, 1, "must be 1", 0, true, true, redq_check_hp_of,
+                          redq_critic_loss, 3u, 2u, {2u, 3u}, {3u, 3u}, {4u, 3u}, {1u, 2u}, {2u, 2u}};
   return redq_loop(ctx, spec, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, states, next_states, actions,
                    rewards, terminations, B, key_io, scheme, q_opt_count_io, pi_opt_count_io, &rhp, metrics_out, subsets_out, stream);
 }

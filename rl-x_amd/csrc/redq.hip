@@ -28,7 +28,10 @@
 // counter) -> Adam of the policy.  The k_ens_* kernels are sac_ens.hip's, shared with tqc.hip.
 // Every reduction runs in a fixed order without atomics: two identical calls give identical bits.
 // CPU twin: tests/redq_twin.py (float64).  The reference's REDQ is JAX only; see DESIGN.md 4.5e for what is pinned.
-// The update's body is redq_loop (redq_loop.h), which droq.hip calls too with LayerNorm / dropout critics and its own key layout.
+// The update's body is redq_loop, which serves three entry points under a RedqLoopSpec (redq_loop.h); this schedule is theirs too.
+// droq.hip: LayerNorm / dropout critics and its own key layout.  aqe.hip: H values per critic (q, dq, qa, seed are [E][B][H]), M = E
+// targets in index order and no sample_key, k_aqe_target_loss for k_redq_critic_loss, and k_ens_fill + k_ens_atom_rowsum for
+// k_redq_policy_seed.
 #include "redq_loop.h"
 
 namespace rlx {
@@ -113,10 +116,10 @@ static void redq_subset(const uint32_t sample_key[2], int E, int M, int scheme, 
   for (int m = 0; m < M; ++m) idx_out[m] = idx[m];
 }
 
-static int redq_critic_loss(const float* q, const float* qn, const float* rew, const float* term, const float* nlogp, const float* log_alpha,
-                            int64_t B, int E, int M, float gamma, float* y, float* dq, float* loss_row, float* loss_out, hipStream_t st) {
-  hipLaunchKernelGGL(k_redq_critic_loss, dim3(div_up(B, 256)), dim3(256), 0, st, q, qn, rew, term, nlogp, log_alpha, y, dq, loss_row, B, E, M,
-                     gamma);
+int redq_critic_loss(const float* q, const float* qn, const float* rew, const float* term, const float* nlogp, const float* log_alpha,
+                     int64_t B, const RedqLossDims& n, float gamma, float* y, float* dq, float* loss_row, float* loss_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_redq_critic_loss, dim3(div_up(B, 256)), dim3(256), 0, st, q, qn, rew, term, nlogp, log_alpha, y, dq, loss_row, B, n.E,
+                     n.M, gamma);
   RLX_LAUNCH_CHECK();
   return loss_out ? ens_mean(loss_row, B, loss_out, st) : RLX_OK;
 }
@@ -140,17 +143,19 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
               RLX_EINVAL, fn + ": NULL pointer");
   RLX_REQUIRE(B > 0, RLX_EINVAL, fn + ": B must be positive");
   const int64_t kc = spec.critic_keys_per_row, kp = spec.policy_keys_per_row;
-  RLX_REQUIRE(B <= (0x7fffffffLL - 2) / kc, RLX_EUNSUP,
-              fn + ": B too large for the 32-bit key count " + (kc == 1 ? std::string("B + 2") : std::to_string(kc) + " B + 2"));
+  const int64_t own = spec.target_subset ? 2 : 1;   // a critic step's keys in front of the rows': key, and sample_key with a subset
+  RLX_REQUIRE(B <= (0x7fffffffLL - own) / kc, RLX_EUNSUP,
+              fn + ": B too large for the 32-bit key count " + (kc == 1 ? "B" : std::to_string(kc) + " B") + " + " + std::to_string(own));
   int rc = ens_check_net(*pdesc, spec.algo, "pdesc");
   if (rc) return rc;
   rc = ens_check_net(*qdesc, spec.algo, "qdesc");
   if (rc) return rc;
-  rc = redq_check_hp(*hp, spec.algo);
+  rc = spec.check_hp(*hp, spec);
   if (rc) return rc;
-  const int E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps;
+  const int E = hp->ensemble_size, M = hp->in_target_minimization_size, G = hp->q_update_steps, H = spec.heads, T = E * H;
+  const RedqLossDims dims{E, H, M, M * H - spec.dropped};
   EnsDims d;
-  rc = ens_prologue(spec.fn, *pdesc, *qdesc, 1, "must be 1", states, next_states, hp->critic_states, hp->critic_next_states, &d);
+  rc = ens_prologue(spec.fn, *pdesc, *qdesc, H, spec.heads_rule, states, next_states, hp->critic_states, hp->critic_next_states, &d);
   if (rc) return rc;
   const int A = d.A, Op = d.Op, Oc = d.Oc, ldc = d.ldc, ldp = d.ldp;
   hipStream_t st = (hipStream_t)stream;
@@ -158,13 +163,14 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
   const Chain LP = ens_layout(*pdesc);
   const Chain LQ = make_chain(qdesc->in_dim, qdesc->hidden, qdesc->n_hidden, qdesc->out_dim, spec.critic_norm, RLX_ACT_RELU, spec.critic_eps,
                               spec.critic_drop);
-  const uint32_t count_c = (uint32_t)(kc * B + 2), count_p = (uint32_t)(kp * B + 1);   // the split counts of a critic / the policy step
+  const uint32_t count_c = (uint32_t)(kc * B + own), count_p = (uint32_t)(kp * B + 1);   // the split counts of a critic / the policy step
   DropKeys dk;
   const int64_t np_ = LP.n_params, nq = LQ.n_params;
+  const size_t BH = (size_t)B * H;
   // ---- arena: the policy's passes, one buffer set for the targets' inference passes, E sets for the online critics: their backward
   // waits for the loss in a critic step and for the seed -- which needs all E values -- in the policy step
   ChainBufs bpn, bpc, bi, bq[REDQ_MAXE];
-  float *xc, *xn, *xp, *xsn, *xsc, *hn, *hc, *dpi, *lpn, *lpc, *qn, *q, *dq, *qa, *seed, *da, *y, *loss_row, *minq_row, *gp, *gq, *steps;
+  float *xc, *xn, *xp, *xsn, *xsc, *hn, *hc, *dpi, *lpn, *lpc, *qn, *q, *dq, *qa, *seed, *da, *y, *loss_row, *q_row, *gp, *gq, *steps;
   rc = arena_carve(ctx, SL_SAC, [&](Arena& a) {
     chain_carve(LP, B, a, &bpn);
     chain_carve(LP, B, a, &bpc);
@@ -173,9 +179,9 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
     for (float** x : {&xc, &xn, &xp}) *x = a.take((size_t)B * ldc);
     for (float** x : {&xsn, &xsc}) *x = a.take((size_t)B * ldp);
     for (float** x : {&hn, &hc, &dpi}) *x = a.take((size_t)B * 2 * A);
-    for (float** x : {&lpn, &lpc, &loss_row, &minq_row, &y}) *x = a.take(B);
-    qn = a.take((size_t)M * B);
-    for (float** x : {&q, &dq, &qa, &seed}) *x = a.take((size_t)E * B);
+    for (float** x : {&lpn, &lpc, &loss_row, &q_row, &y}) *x = a.take(B);
+    qn = a.take((size_t)M * BH);
+    for (float** x : {&q, &dq, &qa, &seed}) *x = a.take((size_t)E * BH);
     da = a.take((size_t)E * B * ldc);
     gp = a.take(np_);
     gq = a.take((size_t)E * nq);
@@ -183,17 +189,23 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
   });
   float* sq = (float*)scratch(ctx, SL_NORM, REDUCE_MAX_BLOCKS * sizeof(float));
   if (rc || !sq) return RLX_ENOMEM;
-  // ---- the key chain (redq.py:229-230, :247-248) and the G target subsets (:232-233), all on the host
+  // ---- the key chain (redq.py:229-230, :247-248) and the G target subsets (:232-233; without one, every target in index order), all
+  // on the host
   uint32_t step_key[REDQ_MAXG + 1][2];                        // the key each step splits
   int32_t subset[REDQ_MAXG][REDQ_MAXE];
   uint32_t key[2] = {key_io[0], key_io[1]};
   for (int i = 0; i < G; ++i) {
-    uint32_t nxt[2], sample_key[2];
+    uint32_t nxt[2];
     step_key[i][0] = key[0];
     step_key[i][1] = key[1];
     split_at_host(key, 0, count_c, scheme, nxt);
-    split_at_host(key, 1, count_c, scheme, sample_key);
-    redq_subset(sample_key, E, M, scheme, subset[i]);
+    if (spec.target_subset) {
+      uint32_t sample_key[2];
+      split_at_host(key, 1, count_c, scheme, sample_key);
+      redq_subset(sample_key, E, M, scheme, subset[i]);
+    } else {
+      for (int m = 0; m < M; ++m) subset[i][m] = m;
+    }
     key[0] = nxt[0];
     key[1] = nxt[1];
   }
@@ -224,19 +236,19 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
     rc = ens_policy_sample(ctx, d, LP, pparams, cn_i, s2_i, xn, xsn, bpn, hn, lpn, sa, ki,
                            ctx->dbg_sac_eps[0] ? ctx->dbg_sac_eps[0] + (size_t)i * B * A : nullptr, B, st);
     for (int m = 0; m < M && !rc; ++m)   // (the m-th selected target is network m of its vmapped pass)
-      rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + (size_t)m * B, B, st,
+      rc = chain_fwd(ctx, LQ, qtarget + subset[i][m] * nq, xn, ldc, bi, qn + m * BH, B, st,
                      redq_drop_keys(spec, step_key[i], scheme, spec.target_drop, count_c, m, E, &dk));
     if (!rc) rc = fs_concat(cs_i, Oc, a_i, A, xc, ldc, B, st);
     for (int e = 0; e < E && !rc; ++e)
-      rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + (size_t)e * B, B, st,
+      rc = chain_fwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], q + e * BH, B, st,
                      redq_drop_keys(spec, step_key[i], scheme, spec.online_drop, count_c, e, E, &dk));
-    if (!rc) rc = redq_critic_loss(q, qn, rewards + (size_t)i * B, terminations + (size_t)i * B, lpn, log_alpha, B, E, M, hp->gamma, y, dq,
+    if (!rc) rc = spec.critic_loss(q, qn, rewards + (size_t)i * B, terminations + (size_t)i * B, lpn, log_alpha, B, dims, hp->gamma, y, dq,
                                    loss_row, steps + i, st);
-    // one deferred reduction per critic; the split-operand gradient scale is that of B E rows: |d loss / d q| is ~ 2 |q - y| / (B E)
+    // one deferred reduction per critic; the split-operand gradient scale is that of B T rows: |d loss / d q| is ~ 2 |q - y| / (B T)
     for (int e = 0; e < E && !rc; ++e) {
-      BwdPass bwd(ctx, B * E);
+      BwdPass bwd(ctx, B * T);
       rc = bwd.begin(chain_stage_floats(ctx, LQ, B, true));
-      if (!rc) rc = chain_bwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], dq + (size_t)e * B, gq + e * nq, nullptr, 0, B, st, 0, 0,
+      if (!rc) rc = chain_bwd(ctx, LQ, qparams + e * nq, xc, ldc, bq[e], dq + e * BH, gq + e * nq, nullptr, 0, B, st, 0, 0,
                               redq_drop_keys(spec, step_key[i], scheme, spec.online_drop, count_c, e, E, &dk));
       if (!rc) rc = bwd.finish(st);
     }
@@ -258,17 +270,26 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
   const EnsRowKeys kpol{step_key[G][0], step_key[G][1], scheme, spec.cur_noise.base, spec.cur_noise.stride, count_p};
   rc = ens_policy_sample(ctx, d, LP, pparams, d.cs, states, xp, xsc, bpc, hc, lpc, sa, kpol, ctx->dbg_sac_eps[1], B, st);
   for (int e = 0; e < E && !rc; ++e)
-    rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + (size_t)e * B, B, st,
+    rc = chain_fwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], qa + e * BH, B, st,
                    redq_drop_keys(spec, step_key[G], scheme, spec.policy_drop, count_p, e, E, &dk));
   if (rc) return rc;
-  hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, (const float*)qa, seed, minq_row, B, E);
-  RLX_LAUNCH_CHECK();
+  if (spec.policy_min) {
+    hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, (const float*)qa, seed, q_row, B, E);
+    RLX_LAUNCH_CHECK();
+  } else {
+    rc = ens_fill(seed, (int64_t)E * BH, -1.0f / ((float)B * (float)T), st);
+    if (!rc) rc = ens_atom_rowsum(qa, q_row, B, H, T, st);
+    if (rc) return rc;
+  }
   {
-    BwdPass bwd(ctx, B);   // the critics' seeds are 0 or -1 / (B n_ties); the policy's head gradient is ~ 1 / B per sample
+    BwdPass bwd(ctx, B);   // the policy's head gradient is ~ 1 / B per sample
     rc = bwd.begin(E * chain_stage_floats(ctx, LQ, B, false) + chain_stage_floats(ctx, LP, B, true));
-    for (int e = 0; e < E && !rc; ++e)
-      rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + (size_t)e * B, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A,
-                     redq_drop_keys(spec, step_key[G], scheme, spec.policy_drop, count_p, e, E, &dk));
+    {  // the critics' passes: seeds of 0 or -1 / (B n_ties) under the minimum, of exactly -1 / (B T) under the mean
+      GradScaleScope seeds(ctx, bx_grad_scale(spec.policy_min ? B : B * T));
+      for (int e = 0; e < E && !rc; ++e)
+        rc = chain_bwd(ctx, LQ, qparams + e * nq, xp, ldc, bq[e], seed + e * BH, nullptr, da + (size_t)e * B * ldc, ldc, B, st, Oc, A,
+                       redq_drop_keys(spec, step_key[G], scheme, spec.policy_drop, count_p, e, E, &dk));
+    }
     if (rc) return rc;
     rc = ens_policy_grad(hc, xp, ldc, Oc, da, ldc, (int64_t)B * ldc, E, log_alpha, kpol, dpi, B, A, hp->log_std_min, hp->log_std_max,
                          ctx->dbg_sac_eps[1], st);
@@ -280,8 +301,8 @@ int redq_loop(rlx_ctx* ctx, const RedqLoopSpec& spec, const rlx_mlp_desc* pdesc,
   const int64_t pstep = *pi_opt_count_io + 1;
   float sched[3];
   adam_schedule_entry(sched, pstep, hp->lr_alpha, hp->adam_b1, hp->adam_b2);
-  rc = ens_finish(minq_row, B, lpc, B, steps, G, log_alpha, am, av, metrics_out, hp->target_entropy, sched, hp->adam_b1, hp->adam_b2,
-                  hp->adam_eps, st);
+  rc = ens_finish(q_row, spec.policy_min ? B : B * T, lpc, B, steps, G, log_alpha, am, av, metrics_out, hp->target_entropy, sched,
+                  hp->adam_b1, hp->adam_b2, hp->adam_eps, st);
   if (!rc) rc = torch_clip_adam(pparams, gp, pm, pv, np_, sq, pstep, hp->lr_policy, ahp, metrics_out + 6, st);
   if (rc) return rc;
   key_io[0] = key[0];
@@ -326,8 +347,8 @@ int rlx_redq_losses_f32(rlx_ctx* ctx, const float* q, const float* q_next_sel, c
     if (!loss_row) return RLX_ENOMEM;
   }
   const int E = hp->ensemble_size, M = hp->in_target_minimization_size;
-  const int rc2 = redq_critic_loss(q, q_next_sel, rewards, terminations, next_logp, log_alpha, B, E, M, hp->gamma, y_out, dq_out, loss_row,
-                                   loss_out, st);
+  const int rc2 = redq_critic_loss(q, q_next_sel, rewards, terminations, next_logp, log_alpha, B, RedqLossDims{E, 1, M, M}, hp->gamma, y_out,
+                                   dq_out, loss_row, loss_out, st);
   if (rc2 || !qa) return rc2;
   hipLaunchKernelGGL(k_redq_policy_seed, dim3(div_up(B, 256)), dim3(256), 0, st, qa, seed_out, minq_out, B, E);
   RLX_LAUNCH_CHECK();
@@ -340,7 +361,8 @@ int rlx_redq_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
                         uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_redq_hparams* hp,
                         float* metrics_out, int32_t* subsets_out, void* stream) {
   // one key per row: keys[2 + b] of B + 2 in a critic step, keys[1 + b] of B + 1 in the policy step; plain ReLU critics, no dropout
-  const RedqLoopSpec spec{"rlx_redq_update_f32", "redq", NORM_NONE, 0.f, 0.f, 1u, 1u, {2u, 1u}, {0u, 0u}, {0u, 0u}, {1u, 1u}, {0u, 0u}};
+  const RedqLoopSpec spec{"rlx_redq_update_f32", "redq", NORM_NONE, 0.f, 0.f, 1, "must be 1", 0, true, true, redq_check_hp_of, redq_critic_loss,
+                          1u, 1u, {2u, 1u}, {0u, 0u}, {0u, 0u}, {1u, 1u}, {0u, 0u}};
   return redq_loop(ctx, spec, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, states, next_states, actions,
                    rewards, terminations, B, key_io, scheme, q_opt_count_io, pi_opt_count_io, hp, metrics_out, subsets_out, stream);
 }

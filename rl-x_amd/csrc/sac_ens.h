@@ -2,7 +2,8 @@
 // ReLU critics (plain; droq.hip's with Dropout and LayerNorm in every hidden block) on net_pass.h.  The kernels and their launchers are in sac_ens.hip; here are their declarations, the device
 // helpers of the multi-output critics (value indexing, the wave-level bitonic sort) and the host helpers of an entry point: the
 // descriptor rules, the shapes of a call, host key splitting, and the policy pass that ends in a sample.  An algorithm's file keeps
-// its critic target and loss, its hyper-parameter check, its arena carve and its schedule.
+// its critic target and loss and its hyper-parameter check; the arena carve and the schedule are tqc.hip's own and, for the other three,
+// redq.hip's redq_loop (redq_loop.h).
 #pragma once
 #include "net_pass.h"
 #include "sac_sample.h"

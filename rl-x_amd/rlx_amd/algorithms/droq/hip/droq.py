@@ -32,26 +32,18 @@ def _with_layer_norm(flat, n_in, hidden, out_dim):
 
 class DroQ(REDQ):
     _NAME = "droq.hip"
+    _UPDATE = "droq_update"
 
-    def __init__(self, config, train_env, eval_env, run_path, writer):
-        alg = config.algorithm
-        self._refuse(alg)
+    def _read_ensemble(self, alg):
         self.dropout_rate = float(alg.dropout_rate)
         if not 0.0 <= self.dropout_rate < 1.0:
             raise ValueError("droq.hip: dropout_rate must be in [0, 1)")
         H = int(alg.nr_hidden_units)
         if H <= 0 or H % 64 != 0 or H > MAX_HIDDEN:
             raise ValueError(f"droq.hip: nr_hidden_units must be a multiple of 64, at most {MAX_HIDDEN} (the LayerNorm kernels' row width)")
-        for name, lo, hi in (("ensemble_size", 1, 16), ("q_update_steps", 1, 64)):
-            if not lo <= int(getattr(alg, name)) <= hi:
-                raise ValueError(f"droq.hip: {name} must be in {lo}..{hi}")
-        if not 1 <= int(alg.in_target_minimization_size) <= int(alg.ensemble_size):
-            raise ValueError("droq.hip: in_target_minimization_size must be in 1..ensemble_size")
+        super()._read_ensemble(alg)
         if 3 * int(alg.batch_size) + 2 > 2 ** 31 - 1:
             raise ValueError("droq.hip: batch_size too large for the 32-bit key count 3 * batch_size + 2")
-        super().__init__(config, train_env, eval_env, run_path, writer)
-        from rlx_amd.hip import DroqHparams
-        self.DroqHparams = DroqHparams
 
     def _init_critics(self, out_dim):
         """EnsembleSAC._init_critics (each net from its own split of critic_key, the target equal to the online critics, droq.py:64,
@@ -70,30 +62,18 @@ class DroQ(REDQ):
         self.qm, self.qv = torch.zeros_like(self.qparams), torch.zeros_like(self.qparams)
 
     def hparams(self):
+        from rlx_amd.hip import DroqHparams
         r = super().hparams()
-        hp = self.DroqHparams()
+        hp = DroqHparams()
         for name, _ in type(r)._fields_:
             setattr(hp, name, getattr(r, name))
         hp.dropout_rate = self.dropout_rate
         return hp
 
-    def update(self, batch):
-        """One `update` (droq.py:144-261) on batch = (states, next_states, actions, rewards, terminations) of q_update_steps *
-        batch_size rows, batch i in rows [i B, (i + 1) B), as redq.hip takes it."""
-        hp = self.hparams()
-        batch = self._select_columns(batch, hp)
-        self.key, self.nr_q_updates, self.nr_policy_updates = self.ctx.droq_update(
-            self.pdesc, self.pparams, self.pm, self.pv, self.qdesc, self.qparams, self.qm, self.qv, self.qtarget,
-            self.log_alpha, self.am, self.av, batch, self.key, self.nr_q_updates, self.nr_policy_updates, hp, self.metrics_dev, self.scheme)
-
     def critic_layout(self):
         layout = super().critic_layout()
         layout.update(layer_norm=True, dropout_rate=self.dropout_rate)
         return layout
-
-    def _check_layout(self, layout):
-        if layout != self.critic_layout():
-            raise ValueError(f"droq.hip: the checkpoint's critic layout {layout} does not fit this configuration {self.critic_layout()}")
 
     def general_properties():
         return GeneralProperties

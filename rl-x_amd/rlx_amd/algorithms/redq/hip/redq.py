@@ -32,26 +32,33 @@ def critic_lr_and_delta(count, *, anneal, learning_rate, nr_envs, learning_start
 
 
 class REDQ(EnsembleSAC):
+    """Also the base of aqe.hip and droq.hip, which share the high update-to-data loop: a subclass sets _NAME and _UPDATE (the
+    context's update call) and overrides _read_ensemble (its hyper-parameters and refusals; critic_out_dim), hparams and
+    critic_layout."""
     _NAME = "redq.hip"
     _COUNTERS = ("nr_q_updates", "nr_policy_updates")                  # BOTH optimizer step counts
+    _UPDATE = "redq_update"
 
     def __init__(self, config, train_env, eval_env, run_path, writer):
-        alg = config.algorithm
-        self._refuse(alg)
-        self.ensemble_size = int(alg.ensemble_size)
-        self.in_target_minimization_size = int(alg.in_target_minimization_size)
-        self.q_update_steps = int(alg.q_update_steps)
-        if not 1 <= self.ensemble_size <= 16:
-            raise ValueError("redq.hip: ensemble_size must be in 1..16")
-        if not 1 <= self.in_target_minimization_size <= self.ensemble_size:
-            raise ValueError("redq.hip: in_target_minimization_size must be in 1..ensemble_size")
-        if not 1 <= self.q_update_steps <= 64:
-            raise ValueError("redq.hip: q_update_steps must be in 1..64")
+        self._refuse(config.algorithm)
+        self._read_ensemble(config.algorithm)
         super().__init__(config, train_env, eval_env, run_path, writer)
-        from rlx_amd.hip import RedqHparams
-        self.RedqHparams = RedqHparams
         self.nr_q_updates = 0                                          # redq.py:280; nr_policy_updates (:279) is SAC's opt_count
-        self._init_critics(1)                                          # critic.py:17-53, redq.py:115-116
+        self._init_critics(self.critic_out_dim)                        # critic.py:17-53, redq.py:115-116
+
+    def _int_in(self, alg, name, lo, hi):
+        v = int(getattr(alg, name))
+        if not lo <= v <= hi:
+            raise ValueError(f"{self._NAME}: {name} must be in {lo}..{hi}")
+        return v
+
+    def _read_ensemble(self, alg):
+        self.ensemble_size = self._int_in(alg, "ensemble_size", 1, 16)
+        self.in_target_minimization_size = int(alg.in_target_minimization_size)
+        if not 1 <= self.in_target_minimization_size <= self.ensemble_size:
+            raise ValueError(f"{self._NAME}: in_target_minimization_size must be in 1..ensemble_size")
+        self.q_update_steps = self._int_in(alg, "q_update_steps", 1, 64)
+        self.critic_out_dim = 1
 
     # the policy's / alpha's optimizer counter under SAC's name: SAC's loop, log line and schedule read it
     @property
@@ -69,11 +76,16 @@ class REDQ(EnsembleSAC):
     def current_lr(self):
         return policy_lr(self.nr_policy_updates, **self._schedule_args())                                 # redq.py:88-92, :257
 
-    def hparams(self):
+    def _common_hparams(self):
+        """the fields the three hparams structs begin with: SAC's, the three learning rates (the critics' with its per-step delta,
+        redq.py:82-98), Adam's"""
         lr = self.current_lr()
         lr_q, delta = critic_lr_and_delta(self.nr_q_updates, **self._schedule_args())
-        return self.RedqHparams(self.gamma, self.tau, self.target_entropy, self.log_std_min, self.log_std_max, lr, lr_q, delta, lr, 0.9, 0.999,
-                                1e-8, self.ensemble_size, self.in_target_minimization_size, self.q_update_steps)
+        return (self.gamma, self.tau, self.target_entropy, self.log_std_min, self.log_std_max, lr, lr_q, delta, lr, 0.9, 0.999, 1e-8)
+
+    def hparams(self):
+        from rlx_amd.hip import RedqHparams
+        return RedqHparams(*self._common_hparams(), self.ensemble_size, self.in_target_minimization_size, self.q_update_steps)
 
     def _alloc(self):
         """SAC's buffers, with q_update_steps batches per update: [G * B, ...] = [G, B, ...] (replay_buffer.py:33-37)"""
@@ -92,7 +104,7 @@ class REDQ(EnsembleSAC):
         are selected here when the env defines them."""
         hp = self.hparams()
         batch = self._select_columns(batch, hp)
-        self.key, self.nr_q_updates, self.nr_policy_updates = self.ctx.redq_update(
+        self.key, self.nr_q_updates, self.nr_policy_updates = getattr(self.ctx, self._UPDATE)(
             self.pdesc, self.pparams, self.pm, self.pv, self.qdesc, self.qparams, self.qm, self.qv, self.qtarget,
             self.log_alpha, self.am, self.av, batch, self.key, self.nr_q_updates, self.nr_policy_updates, hp, self.metrics_dev, self.scheme)
 
@@ -108,7 +120,7 @@ class REDQ(EnsembleSAC):
 
     def _check_layout(self, layout):
         if layout != self.critic_layout():
-            raise ValueError(f"redq.hip: the checkpoint's critic layout {layout} does not fit this configuration {self.critic_layout()}")
+            raise ValueError(f"{self._NAME}: the checkpoint's critic layout {layout} does not fit this configuration {self.critic_layout()}")
 
     def general_properties():
         return GeneralProperties

@@ -1,4 +1,4 @@
-"""The pieces tqc.hip, redq.hip and aqe.hip share: all are sac.hip's host loop with an ensemble of independent ReLU critics, flat and back
+"""The pieces tqc.hip and redq.hip (with it aqe.hip and droq.hip, its subclasses) share: all are sac.hip's host loop with an ensemble of independent ReLU critics, flat and back
 to back, whose update takes gathered batches (csrc/sac_ens.h is the same layer on the library's side).
 
 A subclass is named as the reference's algorithm is and sets the class attributes _NAME (the plugin's name) and _COUNTERS (the

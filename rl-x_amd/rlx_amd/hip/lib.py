@@ -845,60 +845,63 @@ class Ctx:
             _ptr(metrics_out, f), _stream()), "rlx_tqc_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
 
-    # ---- REDQ
+    # ---- REDQ, AQE, DroQ: one `update` loop (csrc/redq_loop.h) behind three entry points
+    def _ens_losses(self, name, q, q_next, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out, loss_out, qa, seed_out, row_out):
+        f = self.torch.float32
+        _check(getattr(self.lib, name)(self.h, _ptr(q, f, True), _ptr(q_next, f, True), _ptr(rewards, f), _ptr(terminations, f),
+                                       _ptr(next_logp, f), _ptr(log_alpha, f), _ptr(qa, f, True), int(rewards.shape[0]),
+                                       ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True), _ptr(loss_out, f, True),
+                                       _ptr(seed_out, f, True), _ptr(row_out, f, True), _stream()), name)
+
+    def _utd_update(self, name, has_subsets, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count,
+                    pi_count, hp, metrics_out, scheme, subsets=False):
+        """the entry point `name`; has_subsets: it takes subsets_out (HOST [G, M], filled when `subsets` is true)"""
+        f = self.torch.float32
+        k = _key_arr(key)
+        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
+        G = max(int(hp.q_update_steps), 0)
+        M = max(int(hp.in_target_minimization_size), 0) if has_subsets else 0
+        sub = (c_int32 * max(G * M, 1))() if subsets else None
+        B = int(batch[3].numel()) // max(G, 1)
+        _check(getattr(self.lib, name)(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
+            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
+            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
+            _ptr(metrics_out, f), *([sub] if has_subsets else []), _stream()), name)
+        out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
+        return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
+
     def redq_losses(self, q, q_next_sel, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out=None, loss_out=None, qa=None,
                     seed_out=None, minq_out=None):
         """REDQ's two loss heads on given values (include/rlx_hip.h): q / dq_out / qa / seed_out [E, B], q_next_sel [M, B]."""
-        f = self.torch.float32
-        _check(self.lib.rlx_redq_losses_f32(self.h, _ptr(q, f, True), _ptr(q_next_sel, f, True), _ptr(rewards, f), _ptr(terminations, f),
-                                            _ptr(next_logp, f), _ptr(log_alpha, f), _ptr(qa, f, True), int(rewards.shape[0]),
-                                            ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True), _ptr(loss_out, f, True),
-                                            _ptr(seed_out, f, True), _ptr(minq_out, f, True), _stream()), "rlx_redq_losses_f32")
+        self._ens_losses("rlx_redq_losses_f32", q, q_next_sel, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out, loss_out, qa,
+                         seed_out, minq_out)
 
     def redq_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
                     metrics_out, scheme=THREEFRY_PARTITIONABLE, subsets=False):
         """batch = (states [G, B, O], next_states, actions [G, B, A], rewards [G, B], terminations), G = hp.q_update_steps.
         Returns (new_key, new_q_count, new_pi_count), and the [G, M] target subsets behind them when subsets is true."""
-        f = self.torch.float32
-        k = _key_arr(key)
-        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
-        G, M = max(int(hp.q_update_steps), 0), max(int(hp.in_target_minimization_size), 0)
-        sub = (c_int32 * max(G * M, 1))() if subsets else None
-        B = int(batch[3].numel()) // max(G, 1)
-        _check(self.lib.rlx_redq_update_f32(
-            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
-            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
-            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
-            _ptr(metrics_out, f), sub, _stream()), "rlx_redq_update_f32")
-        out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
-        return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
+        return self._utd_update("rlx_redq_update_f32", True, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch,
+                                key, q_count, pi_count, hp, metrics_out, scheme, subsets)
 
-    # ---- AQE
     def aqe_losses(self, q, q_next, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out=None, loss_out=None, qa=None,
                    seed_out=None, meanq_out=None):
         """AQE's two loss heads on given values (include/rlx_hip.h): q / q_next / dq_out / qa / seed_out [E, B, H]."""
-        f = self.torch.float32
-        _check(self.lib.rlx_aqe_losses_f32(self.h, _ptr(q, f, True), _ptr(q_next, f, True), _ptr(rewards, f), _ptr(terminations, f),
-                                           _ptr(next_logp, f), _ptr(log_alpha, f), _ptr(qa, f, True), int(rewards.shape[0]),
-                                           ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True), _ptr(loss_out, f, True),
-                                           _ptr(seed_out, f, True), _ptr(meanq_out, f, True), _stream()), "rlx_aqe_losses_f32")
+        self._ens_losses("rlx_aqe_losses_f32", q, q_next, rewards, terminations, next_logp, log_alpha, hp, dq_out, y_out, loss_out, qa,
+                         seed_out, meanq_out)
 
     def aqe_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
                    metrics_out, scheme=THREEFRY_PARTITIONABLE):
-        """batch = (states [G, B, O], next_states, actions [G, B, A], rewards [G, B], terminations), G = hp.q_update_steps.
-        Returns (new_key, new_q_count, new_pi_count)."""
-        f = self.torch.float32
-        k = _key_arr(key)
-        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
-        B = int(batch[3].numel()) // max(int(hp.q_update_steps), 1)
-        _check(self.lib.rlx_aqe_update_f32(
-            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
-            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
-            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
-            _ptr(metrics_out, f), _stream()), "rlx_aqe_update_f32")
-        return np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value
+        """redq_update's batch; returns (new_key, new_q_count, new_pi_count): AQE evaluates every target, there are no subsets."""
+        return self._utd_update("rlx_aqe_update_f32", False, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch,
+                                key, q_count, pi_count, hp, metrics_out, scheme)
 
-    # ---- DroQ
+    def droq_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
+                    metrics_out, scheme=THREEFRY_PARTITIONABLE, subsets=False):
+        """redq_update's arguments and results; the critics' flat layout has LayerNorm scale and bias in every hidden block."""
+        return self._utd_update("rlx_droq_update_f32", True, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch,
+                                key, q_count, pi_count, hp, metrics_out, scheme, subsets)
+
     def droq_mask(self, key, layout, j, E, l, L, B, D, rate, scheme=THREEFRY_PARTITIONABLE):
         """The dropout keep flags (include/rlx_hip.h: the mask stream) of B rows under layout = (base, stride, count) of the step key
         `key`, for the j-th of E networks and hidden layer l of L with D units -> torch.uint8 [B, D] on the device."""
@@ -917,23 +920,6 @@ class Ctx:
         _check(self.lib.rlx_droq_block_f32(self.h, _ptr(Z, f), _ptr(H_io, f), _ptr(scale_bias, f), _key_arr(key), scheme, base, stride, count,
                                            int(j), int(E), int(l), int(L), M, D, float(rate), 0 if dg_out is None else 1,
                                            _ptr(dg_out, f, True), _ptr(db_out, f, True), _stream()), "rlx_droq_block_f32")
-
-    def droq_update(self, pdesc, pparams, pm, pv, qdesc, qparams, qm, qv, qtarget, log_alpha, am, av, batch, key, q_count, pi_count, hp,
-                    metrics_out, scheme=THREEFRY_PARTITIONABLE, subsets=False):
-        """redq_update's arguments and results; the critics' flat layout has LayerNorm scale and bias in every hidden block."""
-        f = self.torch.float32
-        k = _key_arr(key)
-        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
-        G, M = max(int(hp.q_update_steps), 0), max(int(hp.in_target_minimization_size), 0)
-        sub = (c_int32 * max(G * M, 1))() if subsets else None
-        B = int(batch[3].numel()) // max(G, 1)
-        _check(self.lib.rlx_droq_update_f32(
-            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(qdesc),
-            _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f),
-            *[_ptr(x, f) for x in batch], B, k, scheme, ctypes.byref(qc), ctypes.byref(pc), ctypes.byref(hp),
-            _ptr(metrics_out, f), sub, _stream()), "rlx_droq_update_f32")
-        out = (np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value)
-        return out + (np.ctypeslib.as_array(sub)[:G * M].reshape(G, M).copy(),) if subsets else out
 
     # ---- PPO + LSTM
     def lstm_policy_param_count(self, desc):

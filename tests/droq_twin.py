@@ -18,7 +18,7 @@ back to back.  Q matrices here are [B, E]; the library's are [E, B].  The dtype 
 import numpy as np
 
 import redq_twin as rt
-from oracle import nets, ppo as oppo, prng, sac
+from oracle import nets, prng, sac
 
 METRICS = rt.METRICS
 STATE_KEYS = rt.STATE_KEYS
@@ -239,35 +239,13 @@ def policy_step(ps, qs, pp, qp, log_alpha, s, eps2, m_policy, h, cs=None):
     return metrics, gpolicy, dt.type(ga)
 
 
-def update(ps, qs, st, batch, eps1, eps2, subsets, masks, h, lr_policy, lr_critic, lr_critic_delta, lr_alpha, tau, critic_states=None,
-           critic_next_states=None):
-    """`update` (droq.py:144-261) from the state st: tests/redq_twin.py's update with the masks (update_masks' structure) as one
-    more input.  -> (new state, metrics, {"gq": [G] critic gradients, "gp", "ga"}, y [G, B])"""
-    dt = st["P"].dtype
-    c = lambda x: None if x is None else np.asarray(x, dt)
-    s, s2, a, r, term = (c(x) for x in batch)
-    cs, cs2 = c(critic_states), c(critic_next_states)
-    eps1, eps2 = c(eps1), c(eps2)
-    G = int(h["q_update_steps"])
-    Q, qm, qv, QT = st["Q"], st["qm"], st["qv"], st["QT"]
-    losses, norms, gqs, ys = [], [], [], []
-    for i in range(G):
-        loss, g, y = critic_step(ps, qs, st["P"], Q, QT, st["la"][0], (s[i], s2[i], a[i], r[i], term[i]), eps1[i], list(subsets[i]),
-                                 masks["online"][i], masks["target"][i], h, None if cs is None else cs[i], None if cs2 is None else cs2[i])
-        Q, qm, qv = oppo.adam_step(Q, g, qm, qv, st["q_count"] + i, dt.type(np.float32(lr_critic) + np.float32(i) * np.float32(lr_critic_delta)))
-        QT = sac.polyak(Q, QT, dt.type(tau))
-        losses.append(loss)
-        norms.append(np.linalg.norm(g))
-        gqs.append(g)
-        ys.append(y)
-    met, gp, ga = policy_step(ps, qs, st["P"], Q, st["la"][0], s[0], eps2, masks["policy"], h, None if cs is None else cs[0])
-    new = {"Q": Q, "qm": qm, "qv": qv, "QT": QT, "q_count": st["q_count"] + G, "pi_count": st["pi_count"] + 1}
-    new["P"], new["pm"], new["pv"] = oppo.adam_step(st["P"], gp, st["pm"], st["pv"], st["pi_count"], lr_policy)
-    new["la"], new["am"], new["av"] = oppo.adam_step(st["la"], np.array([ga], dt), st["am"], st["av"], st["pi_count"], lr_alpha)
-    met = dict(met)
-    met.update({"loss/q_loss": np.mean(losses), "gradients/policy_grad_norm": np.linalg.norm(gp),
-                "gradients/critic_grad_norm": np.mean(norms), "gradients/entropy_grad_norm": abs(float(ga))})
-    return new, met, {"gq": gqs, "gp": gp, "ga": ga}, np.stack(ys)
+def update(ps, qs, st, batch, eps1, eps2, subsets, masks, h, *rates_and_critic_states):
+    """`update` (droq.py:144-261): tests/redq_twin.py's run_update over this file's steps, with the target subsets [G, M] and the
+    masks (update_masks' structure) as two more inputs"""
+    return rt.run_update(lambda i, P, Q, QT, la, b, e1, cs, cs2: critic_step(ps, qs, P, Q, QT, la, b, e1, list(subsets[i]), masks["online"][i],
+                                                                             masks["target"][i], h, cs, cs2),
+                         lambda P, Q, la, s, e2, cs: policy_step(ps, qs, P, Q, la, s, e2, masks["policy"], h, cs),
+                         st, batch, eps1, eps2, h, *rates_and_critic_states)
 
 
 def losses_torch(ps, pp, qs, qp, qtp, log_alpha, batch, eps1, eps2, subset, m_online, m_target, m_policy, h, critic_states=None,
