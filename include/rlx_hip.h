@@ -198,6 +198,14 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   them and are staged behind the K loop, and no spilled register is reloaded at the tile top.  The same operand words into the
  *   same MFMAs in the same order, the same stores: bit-identical results (tests/test_gpu_l12_prefetch.py); 0, hidden[1] = 512,
  *   "ln_row_once" = 0 and every caller that does not take the k_l12fwd path run the earlier kernels unchanged.
+ * Round 12: "rollout_persistent" (1 default; 0 or 1, anything else is RLX_EINVAL): 1 lets rlx_ppo_rollout_f32 run the acting
+ *   steps as ceil(T / rollout_chunk_steps) launches of k_rollout_steps, each of which carries its 32-row tiles through several
+ *   steps (parameters, head weights, episode counters and the observation tile stay on chip between steps; the critic
+ *   workgroups rebuild their observations from the env's own functions, so no workgroup waits for another) -- where both nets
+ *   have hidden[0] = 512, two or three hidden layers and weight images from rlx_ppo_rollout_begin; everywhere else, with
+ *   "ro_exit" or stamps set, and with 0, the T launches of k_rollout_step run unchanged.  The same operations in the same order:
+ *   bit-identical results (tests/test_gpu_rollout_persistent.py).  "rollout_chunk_steps" (32 default; 1 .. 64, anything else
+ *   is RLX_EINVAL): acting steps per launch of k_rollout_steps; the results do not depend on it.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,
@@ -211,7 +219,9 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value);
  * the kernel under one row); "l12fwd_pf_launches" = launches of k_l12fwd_pf so far (option "l12_prefetch"; the profiler books both
  * forms of k_l12fwd under one row); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
  * the fp16 window of the split-operand engine -- and therefore ran their T steps on the exact-fp32 engine; "gemm_bx" = the
- * current value of that option                                                                                          */
+ * current value of that option; "ro_persistent_launches" / "ro_step_launches" = launches of k_rollout_steps / of
+ * k_rollout_step so far (option "rollout_persistent": which path a rollout took); "ro_critic_es_ptr" = device address of the
+ * int32 [N] episode-step counters the critic workgroups of the last persistent rollout kept (equal to ep_step after it)  */
 int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out);
 
 /* test hook: the next rlx_sac_update_f32 calls take their N(0,1) draws from eps_next / eps_cur (DEVICE [B, A] each: the
@@ -335,7 +345,8 @@ int rlx_ppo_rollout_step_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* p
  * and results as T calls of rlx_ppo_rollout_step_f32 with fuse_env = 1 and processed = NULL (bit-identical:
  * tests/test_gpu_rollout.py) -- what changes is the host: it leaves the loop after ~0.5 ms instead of ~3 ms of per-step binding
  * overhead, so whatever the caller queues next (rlx_ppo_prefetch_permutation, GAE, the update) reaches the GPU while it still
- * runs the rollout.                                                                                                          */
+ * runs the rollout.  With the option "rollout_persistent" (default) and a network inside k_rollout_steps' envelope the T steps
+ * run as ceil(T / rollout_chunk_steps) launches instead of T; keys, results and error returns are the same.                  */
 int rlx_ppo_rollout_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const rlx_mlp_desc* cdesc,
                         const float* cparams, float* states /*[T,N,O]*/, float* obs_last /*[N,O]*/, uint32_t key_io[2],
                         int scheme, float* actions /*[T,N,A]*/, float* values /*[T,N]*/, float* logps /*[T,N]*/, int T, int N,

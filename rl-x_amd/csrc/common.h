@@ -49,7 +49,7 @@ enum ScratchSlot {
   SL_MB_X, SL_MB_XC, SL_MB_AUX, SL_STATS,
   SL_ACT_P0, SL_ACT_P1, SL_ACT_P2, SL_ACT_C0, SL_ACT_C1, SL_ACT_C2,
   SL_DACT_0, SL_DACT_1, SL_LN_P, SL_LN_C,
-  SL_PARTIAL, SL_HEAD_PART, SL_NORM, SL_NORM2, SL_FWD_A, SL_FWD_B, SL_KEYS, SL_GRAD_P, SL_GRAD_C, SL_MEAN, SL_VALUE, SL_RO_NETS, SL_SAC, SL_LSTM, SL_LSTM_IDX, SL_STAGE, SL_OPT_A, SL_OPT_B, SL_STATS_ALL, SL_ZEROS, SL_STAT_PART, SL_LIDX, SL_COUNTS, SL_DIST_STATS, SL_OVERFLOW, SL_SCHED, SL_NV_ROWS, SL_WFRAG, SL_WFRAG_RO, SL_XMAX, SL_MB_GROUP_X, SL_MB_GROUP_AUX, SL_DZ0, SL_WFRAG_SAC, SL_ROW_REC,
+  SL_PARTIAL, SL_HEAD_PART, SL_NORM, SL_NORM2, SL_FWD_A, SL_FWD_B, SL_KEYS, SL_GRAD_P, SL_GRAD_C, SL_MEAN, SL_VALUE, SL_RO_NETS, SL_SAC, SL_LSTM, SL_LSTM_IDX, SL_STAGE, SL_OPT_A, SL_OPT_B, SL_STATS_ALL, SL_ZEROS, SL_STAT_PART, SL_LIDX, SL_COUNTS, SL_DIST_STATS, SL_OVERFLOW, SL_SCHED, SL_NV_ROWS, SL_WFRAG, SL_WFRAG_RO, SL_XMAX, SL_MB_GROUP_X, SL_MB_GROUP_AUX, SL_DZ0, SL_WFRAG_SAC, SL_ROW_REC, SL_RO_CRITIC_ES,
   SL_COUNT
 };
 
@@ -214,6 +214,12 @@ struct rlx_ctx {
   rlx_allreduce_fn ar_hook = nullptr;     // test hook standing in for the collectives (rlx_dbg_set_allreduce_hook)
   void* ar_hook_user = nullptr;
   int ro_exit = 0;                        // tuning aid: k_rollout_step returns after a phase (option "ro_exit")
+  int ro_persistent = 1;                  // rlx_ppo_rollout_f32: 1 k_rollout_steps -- ceil(T / ro_chunk_steps) launches of several acting steps each, where the
+                                          // shape is inside that kernel's envelope (rollout.hip); 0 the T launches of k_rollout_step.  Bit-identical results.
+  int ro_chunk_steps = 32;                // acting steps per launch of k_rollout_steps (option "rollout_chunk_steps", 1 .. 64)
+  int64_t ro_persistent_launches = 0;     // launches of k_rollout_steps / of k_rollout_step since the context was created
+  int64_t ro_step_launches = 0;
+  const void* ro_critic_es = nullptr;     // the critic workgroups' episode-step counters of the last persistent rollout (counter "ro_critic_es_ptr")
   int64_t bx_window_fallbacks = 0;        // rollouts whose acting nets had a weight outside the fp16 window and ran on the exact engine (rollout.hip)
   int64_t ar_calls = 0;                   // all-reduces issued through dist_allreduce (communicator or hook) since the context was created
   // ---- SAC update (sac.hip): critic-loss chain on the caller's stream, policy-loss chain on `side`

@@ -228,6 +228,16 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
   if (std::string(name) == "two_streams") { ctx->two_streams = value != 0; return RLX_OK; }
   if (std::string(name) == "ppo_twin") { ctx->ppo_twin = value; return RLX_OK; }
   if (std::string(name) == "ro_exit") { ctx->ro_exit = value; return RLX_OK; }
+  if (std::string(name) == "rollout_persistent") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: rollout_persistent is 0 or 1");
+    ctx->ro_persistent = value;
+    return RLX_OK;
+  }
+  if (std::string(name) == "rollout_chunk_steps") {
+    RLX_REQUIRE(value >= 1 && value <= 64, RLX_EINVAL, "rlx_dbg_set_option: rollout_chunk_steps is 1 .. 64");
+    ctx->ro_chunk_steps = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "lf_idle_cus") { ctx->lf_idle_cus = value < 0 ? 0 : value; return RLX_OK; }
   if (std::string(name) == "dw_recompute") { ctx->dw_recompute = value != 0; return RLX_OK; }
   if (std::string(name) == "dw_merge") { ctx->dw_merge = value != 0; return RLX_OK; }
@@ -286,6 +296,9 @@ int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out) {
   if (std::string(name) == "allreduce_calls") { *out = ctx->ar_calls; return RLX_OK; }
   if (std::string(name) == "dx_l1bwd_wrap_launches") { *out = ctx->dx_l1bwd_wrap_launches; return RLX_OK; }
   if (std::string(name) == "l12fwd_pf_launches") { *out = ctx->l12fwd_pf_launches; return RLX_OK; }
+  if (std::string(name) == "ro_persistent_launches") { *out = ctx->ro_persistent_launches; return RLX_OK; }
+  if (std::string(name) == "ro_step_launches") { *out = ctx->ro_step_launches; return RLX_OK; }
+  if (std::string(name) == "ro_critic_es_ptr") { *out = (int64_t)reinterpret_cast<uintptr_t>(ctx->ro_critic_es); return RLX_OK; }
   if (std::string(name) == "bx_window_fallbacks") { *out = ctx->bx_window_fallbacks; return RLX_OK; }
   if (std::string(name) == "gemm_bx") { *out = ctx->gemm_bx ? 1 : 0; return RLX_OK; }
   RLX_REQUIRE(false, RLX_EINVAL, "rlx_dbg_get_counter: unknown counter");

@@ -13,6 +13,12 @@
 // first layer and the tiny head on the VALU.  The policy workgroups finish with the sampling
 // epilogue and (optionally) the env transition of their 32 envs; observations are double
 // buffered by the caller (obs_in = Batch.states[t], obs_out = Batch.states[t+1]).
+//
+// Two entries: k_rollout_step, one acting step per launch (rlx_ppo_rollout_step_f32, the recurrent decoder, ESPO's acting call,
+// the phase stamps and "ro_exit"), and k_rollout_steps, up to RO_MAX_CHUNK steps per launch for the T steps of
+// rlx_ppo_rollout_f32 where the nets are inside its envelope (see the comment in front of it; option "rollout_persistent").
+// They share the hidden layers (fused_layer_bx); the persistent entry has its own copy of the first layer, head and epilogue,
+// because what it keeps across steps (registers, LDS regions sized by the host) differs -- k_rollout_step's code is untouched.
 #include "env_device.h"
 #include "gemm.h"
 #include "mlp.h"
@@ -725,6 +731,426 @@ __global__ __launch_bounds__(RO_THREADS, 1) void k_rollout_step(RolloutArgs a) {
 #undef RO_STAMP
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// k_rollout_steps: S consecutive acting steps in ONE launch (rlx_ppo_rollout_f32, option "rollout_persistent").  Same grid and
+// roles as k_rollout_step (workgroup = 32 rows x one network), same arithmetic in the same order -- what changes is what a
+// step no longer repeats:
+//   * first-layer bias, LayerNorm scale / bias: registers, loaded once per launch; logstd (and exp(logstd)), head bias, action
+//     bounds and the head weights: their own LDS regions, filled once per launch.  (W0's fragments are still requested every
+//     step -- 64 more live registers would cost the second wave slot -- but behind the head, for the coming step);
+//   * the observation tile of step s + 1 is written into LDS by the epilogue of step s (next to the obs_out store); only the
+//     launch's first step reads its tile from memory.  The action cost reads the same tile;
+//   * ep_step / ep_ret of the workgroup's rows live in registers (they are still stored every step, as before);
+//   * the draws of step s + 1 (sampling noise, pre-reset observation pairs: functions of (key, element) and (seed, env, clock)
+//     only) are made by waves 1-3 while wave 0 runs the per-row env phase of step s, and handed over through LDS.
+// No workgroup reads what another workgroup of the same launch writes: the env's observation stream does not depend on the
+// action (env_device.h), so the CRITIC workgroup rebuilds its rows' next observations itself -- obs_pair, the termination
+// draw and a private episode-step counter (args.critic_es: filled from ep_step before the first launch of a rollout, read at
+// the start of a launch and written back at its end by the critic workgroups only).  No flags, no spinning, no grid barrier.
+// Envelope: matrix-pipe first layer (hidden[0] = 512, obs <= 32), two or three hidden layers, all of them with weight images,
+// fused env.  Everything else takes the T launches of k_rollout_step.
+// LDS is sized by the host from the shape (ro_steps_layout): at 512-256-128, obs 17, 6 actions 116 KB of the CU's 160, which
+// leaves room for a workgroup of the permutation prefetch's k_rs_scatter (36 KB) next to a resident acting workgroup.
+constexpr int RO_MAX_CHUNK = 64;         // steps per launch: their noise subkeys travel in the kernel arguments (512 B)
+struct RolloutStepsLayout { int a1, wh, outs, lp, xs, eps, ox, red, done, keys, cst, total; };   // LDS offsets in floats
+struct RolloutStepsArgs {
+  RolloutArgs a;           // the launch's FIRST step as k_rollout_step takes it: obs_in = states[t0], action = actions[t0], ...,
+                           // env.t = the env clock of step t0; step s adds s rows of [N, .] to every per-step array
+  int S;                   // steps of this launch (<= RO_MAX_CHUNK)
+  int last_chunk;          // the launch's last step is the rollout's last: its next observation goes to obs_last
+  float* obs_last;         // [N,O]
+  int32_t* critic_es;      // [N] the critic workgroups' episode-step counters
+  RolloutStepsLayout L;
+  uint32_t keys[2 * RO_MAX_CHUNK];   // noise subkey of step s: keys[2 s], keys[2 s + 1]
+};
+
+__global__ __launch_bounds__(RO_THREADS, 2) void k_rollout_steps(RolloutStepsArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const RolloutArgs& a = g.a;
+  float* A0 = smem;
+  float* A1 = smem + g.L.a1;
+  float* Whs = smem + g.L.wh;               // head weights [hk][OD], resident for the launch
+  float* outs = smem + g.L.outs;            // [32][OD]
+  float* s_lp = smem + g.L.lp;              // [32][A] log-prob terms, then [32][A] action-cost terms
+  float* Xs0 = smem + g.L.xs;               // two [32][33] observation tiles: this step's and the next one's
+  float* eps_s = smem + g.L.eps;            // [32][A] sampling noise of the coming step
+  float* ox_s = smem + g.L.ox;              // [32][pairs] x 2 pre-reset observation pairs
+  float* red0 = smem + g.L.red;             // [2][4][32] LayerNorm partials + per-wave totals [4][64]
+  int* s_done = reinterpret_cast<int*>(smem + g.L.done);            // [32]
+  uint32_t* keys_s = reinterpret_cast<uint32_t*>(smem + g.L.keys);  // [2 S]
+  float* ls_s = smem + g.L.cst;             // per action dim: logstd, exp(logstd), lower bound, upper bound ([32] each); head bias [32]
+  float *sd_s = ls_s + 32, *lo_s = ls_s + 64, *hi_s = ls_s + 96, *hb_s = ls_s + 128;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int which = blockIdx.x & 1;
+  const int64_t r0 = (int64_t)(blockIdx.x >> 1) * RO_ROWS;
+  const RolloutNet* __restrict__ np = a.nets + which;
+  typedef const float __attribute__((address_space(1))) * gf32_t;
+  const float* P = np->params;
+  gf32_t Pg = (gf32_t)P;
+  const int n_hidden = np->n_hidden, act = np->act, ln_first = np->ln_first, OD = np->out_dim;
+  const int H1 = np->hidden[1], H2 = np->hidden[2];
+  const int64_t oW0 = np->W[0], ob0 = np->b[0], ob1 = np->b[1], ob2 = np->b[2];
+  const int64_t og0 = np->g0, obe0 = np->be0, oHW = np->headW, oHb = np->headb;
+  const int64_t oLS = a.nets[0].logstd;
+  const u32x4* img1 = reinterpret_cast<const u32x4*>(np->img[1]);
+  const u32x4* img2 = reinterpret_cast<const u32x4*>(np->img[2]);
+  const int imgnt1 = np->img_nt[1], imgnt2 = np->img_nt[2];
+  const int O = a.O, A = a.A, S = g.S;
+  const int pairs = (O + 1) / 2;
+  float* oy_s = ox_s + RO_ROWS * pairs;
+  float* s_cost = s_lp + RO_ROWS * A;
+  const int64_t NO = (int64_t)a.N * O, NA = (int64_t)a.N * A;
+  constexpr int H0 = 512, NT0 = 4, NW0 = RO_THREADS / 64, KS0 = 16, st = H0 + 1;
+  constexpr int EPI = (RO_ROWS * 32 + RO_THREADS - 1) / RO_THREADS;
+  constexpr int OPI = (RO_ROWS * 16 + RO_THREADS - 1) / RO_THREADS;
+  const int OP = (O + 1) & ~1;
+  const int li = lane & 31, lh = lane >> 5;
+  const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
+  const int colbase = w * 32 * NT0 + li;
+  const int hk = n_hidden > 2 ? H2 : H1;
+
+  // ---- once per launch
+  // (the subkeys are selected with compile-time indices: indexing the by-value kernel argument dynamically would copy it to scratch)
+  {
+    uint32_t kv = 0;
+#pragma unroll
+    for (int i = 0; i < 2 * RO_MAX_CHUNK; ++i) kv = (t == i) ? g.keys[i] : kv;
+    if (t < 2 * RO_MAX_CHUNK) keys_s[t] = kv;
+  }
+  // W0 fragments as in k_rollout_step.  They cannot stay in registers across the hidden layers (64 registers on top of the K
+  // loops' fragment ring would push the kernel past 256 and off the second wave slot, which the side stream's kernels need), so
+  // every step requests the coming step's copy behind its head, where the epilogue hides the round trip.
+  float w0r[KS0][NT0];
+  // (the branches around the loads are uniform -- whole MFMA steps past the observation width, and the one step of an odd
+  //  width whose second row does not exist, where every lane reads the first row and lanes 32-63 then take zero -- and the lane
+  //  offset is opaque at each site: with per-lane branches hipcc computed the 64 addresses once, in front of the step loop, and
+  //  kept them in scratch)
+#define RO_LOAD_W0                                                                                                  \
+  {                                                                                                                 \
+    int zw_;                                                                                                        \
+    asm volatile("s_mov_b32 %0, 0" : "=s"(zw_));                                                                    \
+    gf32_t w0a_ = Pg + oW0 + (int)(threadIdx.x >> 6) * 32 * NT0 + (int)(threadIdx.x & 31) + zw_;                    \
+    gf32_t w0b_ = w0a_ + (int)((threadIdx.x >> 5) & 1) * 512;                                                       \
+    const bool lo_half_ = ((threadIdx.x >> 5) & 1) == 0;                                                            \
+    _Pragma("unroll") for (int s_ = 0; s_ < KS0; ++s_) {                                                            \
+      if (2 * s_ + 1 < O) {                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < NT0; ++j) w0r[s_][j] = w0b_[(2 * s_) * 512 + 32 * j];                 \
+      } else if (2 * s_ < O) {                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NT0; ++j) {                                                           \
+          const float v_ = w0a_[(2 * s_) * 512 + 32 * j];                                                           \
+          w0r[s_][j] = lo_half_ ? v_ : 0.f;                                                                         \
+        }                                                                                                           \
+      } else {                                                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NT0; ++j) w0r[s_][j] = 0.f;                                           \
+      }                                                                                                             \
+    }                                                                                                               \
+  }
+  RO_LOAD_W0
+  float b0v[NT0], gam[NT0], bet[NT0];
+#pragma unroll
+  for (int j = 0; j < NT0; ++j) {
+    b0v[j] = Pg[ob0 + colbase + 32 * j];
+    gam[j] = ln_first ? Pg[og0 + colbase + 32 * j] : 1.f;
+    bet[j] = ln_first ? Pg[obe0 + colbase + 32 * j] : 0.f;
+  }
+  if (t < 32) {
+    hb_s[t] = t < OD ? Pg[oHb + t] : 0.f;
+    const bool in = which == 0 && t < A;
+    const float ls = in ? Pg[oLS + t] : 0.f;
+    ls_s[t] = ls;
+    sd_s[t] = expf(ls);
+    lo_s[t] = in && a.clip_and_rescale ? a.lo[t] : 0.f;
+    hi_s[t] = in && a.clip_and_rescale ? a.hi[t] : 0.f;
+  }
+  for (int i = t; i < hk * OD; i += RO_THREADS) Whs[i] = Pg[oHW + i];
+  // episode counters of this workgroup's rows (lanes 0-31 of wave 0): the env's own for the policy, the private copy for the critic
+  int es_r = 0;
+  float er_r = 0.f;
+  if (t < RO_ROWS && r0 + t < a.N) {
+    if (which == 0) { es_r = a.env.ep_step[r0 + t]; er_r = a.env.ep_ret[r0 + t]; }
+    else es_r = g.critic_es[r0 + t];
+  }
+  // the launch's first observation tile comes from memory; both tiles start as zeros (columns >= O and rows >= N stay zero)
+  for (int i = t; i < 2 * RO_ROWS * 33; i += RO_THREADS) Xs0[i] = 0.f;
+  __syncthreads();
+  {
+    constexpr int XPI = RO_ROWS * 32 / RO_THREADS;
+#pragma unroll
+    for (int c = 0; c < XPI; ++c) {
+      const int i = t + c * RO_THREADS, r = i >> 5, k = i & 31;
+      if (k < O && r0 + r < a.N) Xs0[r * 33 + k] = a.obs_in[(r0 + r) * O + k];
+    }
+  }
+  // the draws of one step, made by threads tid = 0 .. nthr - 1 and left in LDS: sampling noise under key (k0, k1) -- the policy
+  // only -- and the env's pre-reset next observation at clock tt.  Same functions and arguments as k_rollout_step: same bits.
+  auto draw_step = [&](int tid, int nthr, bool noise, uint32_t k0, uint32_t k1, uint32_t tt) {
+    if (noise) {
+      const uint64_t total = (uint64_t)a.N_global * A;
+      for (int it = tid; it < RO_ROWS * A; it += nthr) {
+        const int e = it / A, j = it - e * A;
+        const int64_t n = r0 + e;
+        float v = 0.f;
+        if (n < a.N) v = normal_from_bits(random_bits_at(k0, k1, (uint64_t)(n + a.noise_row_offset) * A + j, total, a.scheme));
+        eps_s[it] = v;
+      }
+    }
+    for (int it = tid; it < RO_ROWS * pairs; it += nthr) {
+      const int e = it / pairs, p = it - e * pairs;
+      const int64_t n = r0 + e;
+      float x = 0.f, y = 0.f;
+      if (n < a.N) obs_pair(a.env.seed, (uint32_t)(n + a.env.env_id_offset), tt, (uint32_t)p, x, y);
+      ox_s[it] = x;
+      oy_s[it] = y;
+    }
+  };
+  if (which == 0) draw_step(t, RO_THREADS, true, g.keys[0], g.keys[1], a.env.t);
+  __syncthreads();
+
+  int cur = 0;
+  const int t_launch = t;
+  for (int s = 0; s < S; ++s) {
+    // The thread index of the step body is made opaque to the optimizer once per step (a copy it cannot see through): otherwise
+    // every per-lane LDS / global address of the body is loop-invariant, gets hoisted in front of the step loop and stays live
+    // across it -- hundreds of registers, i.e. spills.  With it the body compiles like k_rollout_step's.
+    int tv;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(tv) : "v"(t_launch));
+    const int t = tv, lane = t & 63, w = t >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const bool lb0 = (lane & 1) != 0, lb1 = (lane & 2) != 0;
+    const int colbase = w * 32 * NT0 + li;
+    const float* Xc = Xs0 + cur * (RO_ROWS * 33);
+    float* Xn = Xs0 + (cur ^ 1) * (RO_ROWS * 33);
+    const uint32_t tt = a.env.t + (uint32_t)s;
+    // ---- layer 0 on the matrix pipe, LayerNorm row sums, element-wise pass: as in k_rollout_step
+    f32x16 z[NT0];
+#pragma unroll
+    for (int j = 0; j < NT0; ++j) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) z[j][r] = b0v[j];
+    }
+    {
+      const float* x0 = Xc + li * 33 + lh;
+#pragma unroll
+      for (int s_ = 0; s_ < KS0; ++s_) {
+        if (2 * s_ < OP) {                         // (uniform)
+          const float av = x0[2 * s_];
+#pragma unroll
+          for (int j = 0; j < NT0; ++j) z[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, w0r[s_][j], z[j], 0, 0, 0);
+        }
+      }
+    }
+    float* tot0 = red0 + 2 * NW0 * 32 + w * 64;
+    if (ln_first) {
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        float sv[4], ssv[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float s_ = 0.f, ss = 0.f;
+#pragma unroll
+          for (int j = 0; j < NT0; ++j) { s_ += z[j][4 * gq + e]; ss += z[j][4 * gq + e] * z[j][4 * gq + e]; }
+          sv[e] = s_;
+          ssv[e] = ss;
+        }
+        const float st_ = half_sum4(sv[0], sv[1], sv[2], sv[3], lb0, lb1);
+        const float sst = half_sum4(ssv[0], ssv[1], ssv[2], ssv[3], lb0, lb1);
+        if (li < 4) {
+          red0[(0 * NW0 + w) * 32 + 8 * gq + 4 * lh + li] = st_;
+          red0[(1 * NW0 + w) * 32 + 8 * gq + 4 * lh + li] = sst;
+        }
+      }
+      __syncthreads();
+      float v = 0.f;
+#pragma unroll
+      for (int q = 0; q < NW0; ++q) v += red0[((lane >> 5) * NW0 + q) * 32 + (lane & 31)];
+      tot0[lane] = v;
+    }
+    const float invH = 1.0f / (float)H0;
+    if (ln_first) {
+      RO_ACT_SWITCH(act,
+        _Pragma("unroll") for (int gq = 0; gq < 4; ++gq) {
+          _Pragma("unroll") for (int e = 0; e < 4; ++e) {
+            const int r = 4 * gq + e, row = 8 * gq + 4 * lh + e;
+            const float mean = tot0[row] * invH;
+            const float rs = rsqrtf(fmaxf(0.f, tot0[32 + row] * invH - mean * mean) + 1e-6f);
+            _Pragma("unroll") for (int j = 0; j < NT0; ++j)
+              A0[row * st + colbase + 32 * j] = actf((z[j][r] - mean) * rs * gam[j] + bet[j]);
+          }
+        })
+    } else {
+      RO_ACT_SWITCH(act,
+        _Pragma("unroll") for (int gq = 0; gq < 4; ++gq) {
+          _Pragma("unroll") for (int e = 0; e < 4; ++e) {
+            const int r = 4 * gq + e, row = 8 * gq + 4 * lh + e;
+            _Pragma("unroll") for (int j = 0; j < NT0; ++j) A0[row * st + colbase + 32 * j] = actf(z[j][r]);
+          }
+        })
+    }
+    // ---- hidden layers from their weight images (fused_layer_bx opens with a barrier, which publishes its input, and closes with one)
+    if (H1 == 256) fused_layer_bx<2>(A0, H0 + 1, H0, img1, imgnt1, P + ob1, A1, H1 + 1, act, t);
+    else fused_layer_bx<1>(A0, H0 + 1, H0, img1, imgnt1, P + ob1, A1, H1 + 1, act, t);
+    const float* hin = A1;
+    int hst = H1 + 1;
+    if (n_hidden > 2) {
+      if (H2 == 256) fused_layer_bx<2>(A1, H1 + 1, H1, img2, imgnt2, P + ob2, A0, H2 + 1, act, t);
+      else fused_layer_bx<1>(A1, H1 + 1, H1, img2, imgnt2, P + ob2, A0, H2 + 1, act, t);
+      hin = A0; hst = H2 + 1;
+    }
+    // ---- head on the VALU from the resident weights
+    {
+      const int r = t & 31;
+      const float* hr = hin + r * hst;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = (t >> 5) + 8 * i;
+        if (o < OD) {
+          float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll 4
+          for (int k = 0; k < hk; k += 2) {
+            acc0 = fmaf(hr[k], Whs[k * OD + o], acc0);
+            acc1 = fmaf(hr[k + 1], Whs[(k + 1) * OD + o], acc1);
+          }
+          outs[r * OD + o] = (acc0 + acc1) + hb_s[o];
+        }
+      }
+    }
+    __syncthreads();
+    RO_LOAD_W0                                     // the coming step's
+    int te;                                        // (the epilogue's addresses are not computed -- and kept -- in front of the layers either)
+    asm volatile("v_mov_b32 %0, %1" : "=v"(te) : "v"(t_launch));
+    {
+    const int t = te, w = t >> 6;
+    if (which == 1) {
+      // ---- critic: the value, then its rows' next observations rebuilt from the env's own functions
+      if (t < RO_ROWS && r0 + t < a.N) a.value[(int64_t)s * a.N + r0 + t] = outs[t];
+      if (w == 0) {
+        if (t < RO_ROWS) {
+          const int64_t n = r0 + t;
+          int done = 0;
+          if (n < a.N) {
+            uint32_t x0 = tt, x1 = ENV_STREAM_MISC;
+            threefry2x32(a.env.seed, (uint32_t)(n + a.env.env_id_offset), x0, x1);
+            const float ut = bits_to_unit(x1);
+            const int es = es_r + 1;
+            done = (ut < a.env.p_term || es >= a.env.horizon) ? 1 : 0;
+            es_r = done ? 0 : es;
+          }
+          s_done[t] = done;
+        }
+      } else if (s + 1 < S) draw_step(t - 64, RO_THREADS - 64, false, 0u, 0u, tt);
+      if (s + 1 == S) break;                       // (uniform: the next launch reads its first tile from states)
+      __syncthreads();
+      for (int it = t; it < RO_ROWS * pairs; it += RO_THREADS) {
+        const int e = it / pairs, p = it - e * pairs;
+        const int64_t n = r0 + e;
+        if (n >= a.N) continue;
+        float x = ox_s[it], y = oy_s[it];
+        if (s_done[e]) obs_pair(a.env.seed, (uint32_t)(n + a.env.env_id_offset), tt, ENV_STREAM_RESET + p, x, y);
+        Xn[e * 33 + 2 * p] = x;
+        if (2 * p + 1 < O) Xn[e * 33 + 2 * p + 1] = y;
+      }
+      cur ^= 1;
+      __syncthreads();
+      continue;
+    }
+    // ---- policy epilogue: sample, log-prob, env transition (k_rollout_step's, with the draws and the observations from LDS)
+    float* action_t = a.action + (int64_t)s * NA;
+    float* final_t = a.env.final_obs + (int64_t)s * NO;
+    float* obs_out = (g.last_chunk && s + 1 == S) ? g.obs_last : a.obs_out + (int64_t)s * NO;
+#pragma unroll
+    for (int q = 0; q < EPI; ++q) {
+      const int it = t + q * RO_THREADS;
+      if (it >= RO_ROWS * A) continue;
+      const int e = it / A, j = it - e * A;
+      const int64_t n = r0 + e;
+      if (n >= a.N) continue;
+      const float eps = eps_s[it];
+      const float ls = ls_s[j];
+      const float sd = sd_s[j];
+      const float mu = outs[it];
+      const float act = mu + sd * eps;
+      const float zs = (act - mu) / sd;
+      s_lp[it] = -0.5f * zs * zs - 0.5f * RO_LOG_2PI - ls;
+      action_t[n * A + j] = act;
+      float p = act;
+      if (a.clip_and_rescale) {
+        const float c = fminf(fmaxf(act, -1.f), 1.f);
+        p = lo_s[j] + 0.5f * (c + 1.0f) * (hi_s[j] - lo_s[j]);
+      }
+      const float d = env_cost_diff(p, Xc[e * 33 + j % O]);
+      s_cost[it] = d * d;
+    }
+    float ox[OPI], oy[OPI];                        // this step's pre-reset pairs: out of LDS before waves 1-3 overwrite them
+#pragma unroll
+    for (int q = 0; q < OPI; ++q) {
+      const int it = t + q * RO_THREADS;
+      ox[q] = oy[q] = 0.f;
+      if (it < RO_ROWS * pairs) {
+        const int e = it / pairs, p = it - e * pairs;
+        const int64_t n = r0 + e;
+        ox[q] = ox_s[it];
+        oy[q] = oy_s[it];
+        if (n < a.N) {
+          const int64_t o = n * O + 2 * p;
+          final_t[o] = ox[q];
+          if (2 * p + 1 < O) final_t[o + 1] = oy[q];
+        }
+      }
+    }
+    __syncthreads();
+    if (w == 0) {
+      if (t < RO_ROWS) {
+        const int64_t n = r0 + t;
+        int done = 0;
+        if (n < a.N) {
+          float lp = 0.f;
+          for (int j = 0; j < A; ++j) lp += s_lp[t * A + j];
+          a.logp[(int64_t)s * a.N + n] = lp;
+          float acc = 0.f;
+          for (int j = 0; j < A; ++j) acc += s_cost[t * A + j];
+          const EnvLaneOut e = env_lane_finish_v(a.env.seed, (uint32_t)(n + a.env.env_id_offset), tt, A, a.env.horizon, a.env.p_term,
+                                                 a.env.reward_noise, acc, es_r, er_r, a.env.ep_step, a.env.ep_ret, a.env.last_ret,
+                                                 a.env.last_len, (int)n);
+          done = e.done;
+          er_r = e.done ? 0.f : er_r + e.reward;
+          es_r = e.done ? 0 : es_r + 1;
+          a.env.reward[(int64_t)s * a.N + n] = e.reward;
+          a.env.terminated[(int64_t)s * a.N + n] = e.term ? 1.f : 0.f;
+          if (a.env.episode_stats && e.done) {
+            atomicAdd(&a.env.episode_stats[0], 1.f);
+            atomicAdd(&a.env.episode_stats[1], e.fin_ret);
+            atomicAdd(&a.env.episode_stats[2], e.fin_len);
+          }
+        }
+        s_done[t] = done;
+      }
+    } else if (s + 1 < S) {
+      // the coming step's draws, in the three waves that would otherwise wait for the per-row phase
+      draw_step(t - 64, RO_THREADS - 64, true, keys_s[2 * s + 2], keys_s[2 * s + 3], tt + 1u);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < OPI; ++q) {
+      const int it = t + q * RO_THREADS;
+      if (it >= RO_ROWS * pairs) continue;
+      const int e = it / pairs, p = it - e * pairs;
+      const int64_t n = r0 + e;
+      if (n >= a.N) continue;
+      float x = ox[q], y = oy[q];
+      if (s_done[e]) obs_pair(a.env.seed, (uint32_t)(n + a.env.env_id_offset), tt, ENV_STREAM_RESET + p, x, y);
+      const int64_t o = n * O + 2 * p;
+      obs_out[o] = x;
+      Xn[e * 33 + 2 * p] = x;
+      if (2 * p + 1 < O) { obs_out[o + 1] = y; Xn[e * 33 + 2 * p + 1] = y; }
+    }
+    cur ^= 1;
+    __syncthreads();
+    }
+  }
+  if (which == 1 && t < RO_ROWS && r0 + t < a.N) g.critic_es[r0 + t] = es_r;
+#undef RO_LOAD_W0
+}
+
 static bool fill_net(const rlx_mlp_desc& d, const float* params, RolloutNet* n) {
   const MlpLayout L = make_layout(d);
   n->params = params;
@@ -749,7 +1175,38 @@ static bool fill_net(const rlx_mlp_desc& d, const float* params, RolloutNet* n) 
   return d.out_dim * RO_ROWS <= 1024;
 }
 
-static int upload_nets_and_launch(rlx_ctx* ctx, const RolloutNet (&hn)[2], RolloutArgs& a, hipStream_t st) {
+// LDS layout of k_rollout_steps for the two nets of a launch; false: outside its envelope (or its LDS does not fit)
+constexpr int RO_STEPS_MAX_LDS = 160 * 1024;
+static bool ro_steps_layout(const RolloutNet (&hn)[2], int O, int A, RolloutStepsLayout* L) {
+  int h1 = 0, wh = 0, od = 0;
+  for (int n = 0; n < 2; ++n) {
+    const RolloutNet& q = hn[n];
+    if (q.wide_in != 0 || q.hidden[0] != 512 || O > 32 || q.n_hidden < 2 || q.n_hidden > 3) return false;
+    for (int l = 1; l < q.n_hidden; ++l)
+      if (!q.img[l]) return false;
+    const int hk = q.hidden[q.n_hidden - 1];
+    h1 = q.hidden[1] > h1 ? q.hidden[1] : h1;
+    wh = hk * q.out_dim > wh ? hk * q.out_dim : wh;
+    od = q.out_dim > od ? q.out_dim : od;
+  }
+  auto up4 = [](int x) { return (x + 3) & ~3; };
+  const int pairs = (O + 1) / 2;
+  L->a1 = RO_ROWS * (512 + 1);                      // A0: layer 0's output, and the third hidden layer's
+  L->wh = L->a1 + up4(RO_ROWS * (h1 + 1));
+  L->outs = L->wh + up4(wh);
+  L->lp = L->outs + up4(RO_ROWS * od);
+  L->xs = L->lp + up4(2 * RO_ROWS * A);
+  L->eps = L->xs + up4(2 * RO_ROWS * 33);
+  L->ox = L->eps + up4(RO_ROWS * A);
+  L->red = L->ox + up4(2 * RO_ROWS * pairs);
+  L->done = L->red + 2 * 4 * 32 + 4 * 64;
+  L->keys = L->done + RO_ROWS;
+  L->cst = L->keys + 2 * RO_MAX_CHUNK;
+  L->total = L->cst + 5 * 32;
+  return (size_t)L->total * sizeof(float) <= (size_t)RO_STEPS_MAX_LDS;
+}
+
+static int upload_nets(rlx_ctx* ctx, const RolloutNet (&hn)[2], RolloutArgs& a, hipStream_t st) {
   // descriptor table lives in device memory; re-uploaded only when it changes
   RolloutNet* dn = (RolloutNet*)scratch(ctx, SL_RO_NETS, sizeof(hn));
   if (!dn) return RLX_ENOMEM;
@@ -759,7 +1216,13 @@ static int upload_nets_and_launch(rlx_ctx* ctx, const RolloutNet (&hn)[2], Rollo
     ctx->ro_nets_shadow.assign(reinterpret_cast<const char*>(hn), reinterpret_cast<const char*>(hn) + sizeof(hn));
   }
   a.nets = dn;
-  static AttrOnce attr_set;      
+  return RLX_OK;
+}
+
+static int upload_nets_and_launch(rlx_ctx* ctx, const RolloutNet (&hn)[2], RolloutArgs& a, hipStream_t st) {
+  const int rc = upload_nets(ctx, hn, a, st);
+  if (rc) return rc;
+  static AttrOnce attr_set;
   const size_t lds = (size_t)RO_LDS_FLOATS * sizeof(float);
   if (!attr_set.done()) {
     RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_step),
@@ -769,6 +1232,7 @@ static int upload_nets_and_launch(rlx_ctx* ctx, const RolloutNet (&hn)[2], Rollo
   const int grid = div_up(a.N, RO_ROWS) * 2;
   hipLaunchKernelGGL(k_rollout_step, dim3(grid), dim3(RO_THREADS), lds, st, a);
   RLX_LAUNCH_CHECK();
+  ++ctx->ro_step_launches;
   return RLX_OK;
 }
 
@@ -951,6 +1415,74 @@ int rlx_ppo_rollout_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pp
               "rlx_ppo_rollout_f32: NULL pointer");
   RLX_REQUIRE(T > 0 && N > 0, RLX_EINVAL, "rlx_ppo_rollout_f32: bad sizes");
   const int64_t O = pdesc->in_dim, A = pdesc->out_dim;
+  // Persistent form (k_rollout_steps): ceil(T / S) launches of S steps each.  Taken only where every check of the step entry
+  // would pass and the shape is inside the persistent kernel's envelope; everything else -- and every error -- goes through the
+  // T step calls below, unchanged.
+  if (ctx->ro_persistent && ctx->ro_exit == 0 && !ctx->dbg_stamps && pparams && cdesc && cparams && key_io && N_global >= N &&
+      rlx_ppo_rollout_step_supported(pdesc, cdesc) && (!clip_and_rescale || (act_low && act_high)) && ep_step && ep_ret &&
+      last_ret && last_len && horizon > 0 && ctx->ro_img.valid && ctx->gemm_bx && ctx->ro_img.params[0] == pparams &&
+      ctx->ro_img.params[1] == cparams) {
+    RolloutNet hn[2];
+    memset(hn, 0, sizeof(hn));
+    fill_net(*pdesc, pparams, &hn[0]);
+    fill_net(*cdesc, cparams, &hn[1]);
+    for (int n = 0; n < 2; ++n)
+      for (int l = 1; l < 3; ++l) { hn[n].img[l] = ctx->ro_img.img[n][l]; hn[n].img_nt[l] = ctx->ro_img.nt[n][l]; }
+    RolloutStepsLayout L;
+    if (ro_steps_layout(hn, (int)O, (int)A, &L)) {
+      RolloutStepsArgs g{};
+      RolloutArgs& a = g.a;
+      a.N = N; a.O = (int)O; a.A = (int)A; a.scheme = scheme;
+      a.clip_and_rescale = clip_and_rescale; a.lo = act_low; a.hi = act_high;
+      a.noise_row_offset = noise_row_offset; a.N_global = N_global;
+      a.env.enabled = 1;
+      a.env.seed = env_seed; a.env.env_id_offset = env_id_offset; a.env.horizon = horizon;
+      a.env.p_term = p_term; a.env.reward_noise = reward_noise; a.env.ep_step = ep_step; a.env.ep_ret = ep_ret;
+      a.env.last_ret = last_ret; a.env.last_len = last_len; a.env.episode_stats = episode_stats;
+      g.obs_last = obs_last;
+      g.L = L;
+      g.critic_es = (int32_t*)scratch(ctx, SL_RO_CRITIC_ES, (size_t)N * sizeof(int32_t));
+      if (!g.critic_es) return RLX_ENOMEM;
+      ctx->ro_critic_es = g.critic_es;
+      hipStream_t st = (hipStream_t)stream;
+      const int rc = upload_nets(ctx, hn, a, st);
+      if (rc) return rc;
+      // the critic workgroups' episode-step counters start as the env's (stream-ordered: behind whatever wrote ep_step)
+      RLX_HIP_TRY(hipMemcpyAsync(g.critic_es, ep_step, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+      static AttrOnce attr_set;
+      if (!attr_set.done()) {
+        RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rollout_steps), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        RO_STEPS_MAX_LDS));
+        attr_set.mark();
+      }
+      const int chunk = ctx->ro_chunk_steps < 1 ? 1 : (ctx->ro_chunk_steps > RO_MAX_CHUNK ? RO_MAX_CHUNK : ctx->ro_chunk_steps);
+      const int grid = div_up(N, RO_ROWS) * 2;
+      for (int t0 = 0; t0 < T; t0 += chunk) {
+        const int S = T - t0 < chunk ? T - t0 : chunk;
+        for (int s = 0; s < S; ++s) {      // the key chain of the T step calls: key, subkey = split(key)
+          uint32_t ks[4];
+          split_host(key_io, ks, 2, scheme);
+          key_io[0] = ks[0]; key_io[1] = ks[1];
+          g.keys[2 * s] = ks[2]; g.keys[2 * s + 1] = ks[3];
+        }
+        g.S = S;
+        g.last_chunk = t0 + S == T ? 1 : 0;
+        a.obs_in = states + (int64_t)t0 * N * O;
+        a.obs_out = states + (int64_t)(t0 + 1) * N * O;     // (the rollout's last step writes obs_last instead)
+        a.action = actions + (int64_t)t0 * N * A;
+        a.value = values + (int64_t)t0 * N;
+        a.logp = logps + (int64_t)t0 * N;
+        a.env.t = env_t0 + (uint32_t)t0;
+        a.env.final_obs = final_obs + (int64_t)t0 * N * O;
+        a.env.reward = rewards + (int64_t)t0 * N;
+        a.env.terminated = terminated + (int64_t)t0 * N;
+        hipLaunchKernelGGL(k_rollout_steps, dim3(grid), dim3(RO_THREADS), (size_t)L.total * sizeof(float), st, g);
+        RLX_LAUNCH_CHECK();
+        ++ctx->ro_persistent_launches;
+      }
+      return RLX_OK;
+    }
+  }
   for (int t = 0; t < T; ++t) {
     const int rc = rlx_ppo_rollout_step_f32(
         ctx, pdesc, pparams, cdesc, cparams, states + (int64_t)t * N * O, t + 1 < T ? states + (int64_t)(t + 1) * N * O : obs_last,

@@ -528,6 +528,9 @@ class Ctx:
         return out.value
 
     def set_option(self, name, value):
+        """rlx_dbg_set_option (include/rlx_hip.h lists the options).  The acting loop's: "rollout_persistent" (1: rollout() runs
+        ceil(T / rollout_chunk_steps) launches of several steps each where the nets allow it; 0: T launches) and
+        "rollout_chunk_steps" (1 .. 64, default 32); get_counter("ro_persistent_launches") / ("ro_step_launches") tell which ran."""
         _check(self.lib.rlx_dbg_set_option(self.h, name.encode(), int(value)), "rlx_dbg_set_option")
 
     def get_counter(self, name):
