@@ -940,6 +940,100 @@ int rlx_droq_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, flo
                         const rlx_droq_hparams* hp, float* metrics_out /*DEVICE [10]*/, int32_t* subsets_out /*HOST [G,M] or NULL*/,
                         void* stream);
 
+/* ---- batch renormalisation (rl_x/algorithms/crossq/flax/batch_renorm.py:77-130) ---------------------------------------------------
+ * The library's column-statistics layer: it normalises x [M, D] over its M ROWS, per column, with scale g, bias b and running
+ * statistics ra_mean (initially 0) / ra_var (initially 1).
+ *   eval (:87-93)    y = (x - ra_mean) rsqrt(ra_var + eps) g + b; no state changes.
+ *   train (:95-128)  mu = mean_i x, v = max(0, mean_i x^2 - mu^2);  r = clip(sqrt(v + eps) / sqrt(ra_var + eps), 1 / r_max, r_max),
+ *                    d = clip((mu - ra_mean) / sqrt(ra_var + eps), -d_max, d_max), both constants of the backward (stop_gradient);
+ *                    w = warmed;  cm = mu - w d sqrt(v) / r;  rho = rsqrt(v (w / r^2 + 1 - w) + eps);  y = (x - cm) rho g + b;
+ *                    then ra_mean <- momentum ra_mean + (1 - momentum) mu, ra_var likewise with v, in place.
+ * warmed is the CALLER's statement that the layer's count of earlier training passes has reached warm_up_steps (:104); the library
+ * keeps no step counter.  Column sums run in double and in a fixed order: identical calls give identical bits.
+ * DEVIATION, zero batch variance: where v == 0 the reference's sqrt(v) has an infinite derivative (its autodiff gives NaN there);
+ * the library takes that term's gradient as 0 where w = 0 or v = 0, and every result stays finite. */
+typedef struct rlx_brn_config {
+  float momentum;                              /* batch_renorm_momentum (crossq default_config.py: 0.99); in [0, 1) */
+  float eps, r_max, d_max;                     /* batch_renorm.py:80-83: 1e-3, 3, 5 */
+  int32_t warmed;                              /* w above: 0 plain batch norm with eps, non-zero the clipped r / d correction */
+} rlx_brn_config;
+enum { RLX_BRN_EVAL_FWD = 0, RLX_BRN_TRAIN_FWD = 1, RLX_BRN_EVAL_BWD = 2, RLX_BRN_TRAIN_BWD = 3 };
+
+/* test entry point: one batch-renormalisation layer alone, over E independent networks in one call (all DEVICE, float32):
+ * x [E, M, ld] (never written), ld a multiple of 4 and >= D, 16-byte aligned; scale_bias [E, 2 D]: g then b; stats [E, 2 D]: ra_mean
+ * then ra_var; save [E, 7 ((D + 3) & ~3)]: written by RLX_BRN_TRAIN_FWD, read by RLX_BRN_TRAIN_BWD (NULL in the eval modes).
+ *   RLX_BRN_EVAL_FWD / _TRAIN_FWD  y_io [E, M, ld] receives y; the training pass advances stats in place.
+ *   RLX_BRN_EVAL_BWD / _TRAIN_BWD  y_io holds d L / d y and receives d L / d x, times 1[x > 0] when relu_mask != 0 (x is a ReLU's
+ *                                  output: the ReLU's derivative fused); dgb_out [E, 2 D] (or NULL) receives d g then d b.
+ *                                  _TRAIN_BWD answers the _TRAIN_FWD that wrote save, on the same x; stats is not read.
+ * The columns D .. ld - 1 of what y_io receives are 0.  M >= 2 (one row has no variance), D >= 1, 1 <= E <= 16 (RLX_EUNSUP above);
+ * every other bad argument is RLX_EINVAL; nothing is written when a check fails. */
+int rlx_brn_f32(rlx_ctx*, const float* x, int ld, int64_t M, int D, int E, const float* scale_bias, float* stats,
+                const rlx_brn_config* cfg, int mode, float* y_io, float* save, int relu_mask, float* dgb_out, void* stream);
+
+/* ---- CrossQ: batch-renormalised critics, no target networks (rl_x/algorithms/crossq/flax) ----------------------------------------
+ * SAC's tanh-Gaussian policy and entropy coefficient over ensemble_size critics, every Dense of every network preceded by a batch
+ * renormalisation (above): x -> BRN -> Dense -> ReLU -> BRN -> ... -> BRN -> Dense head (critic.py:25-60, policy.py:34-72).  There are
+ * no target networks and no Polyak step.  Networks: rlx_mlp_desc with act = RLX_ACT_RELU, ln_first = 0, has_logstd = 0; policy
+ * out_dim = 2 A (columns [0, A) the mean, [A, 2 A) the log-std, clipped to [log_std_min, log_std_max]); critics in_dim = Oc + A,
+ * out_dim = 1.  FLAT LAYOUT of one network: bn0.scale[in], bn0.bias[in], W1[in, H1], b1[H1], bn1.scale[H1], bn1.bias[H1], W2, b2, ...,
+ * bnL.scale[HL], bnL.bias[HL], W_head[HL, out], b_head[out] (rlx_crossq_param_count); the E critics BACK TO BACK.  RUNNING STATISTICS
+ * are a vector of their own per network: bn0.mean[in], bn0.var[in], bn1.mean[H1], bn1.var[H1], ... (rlx_crossq_stats_count; initially
+ * mean 0, var 1); qstats holds the E critics' back to back.
+ * WARM-UP: a network's layers use the clipped r / d correction once its count of earlier training passes has reached
+ * brn_warmup_steps.  A network makes one training pass per update, so the library decides from the optimiser counts it is handed:
+ * critics q_opt_count >= brn_warmup_steps, policy pi_opt_count >= brn_warmup_steps (in the reference a net's `steps` equals its
+ * number of updates).
+ * Envelope: hidden widths multiples of 64 up to 2048, 1..3 hidden layers, A <= 64, B >= 2 (one row has zero batch variance),
+ * 1 <= ensemble_size <= 16; outside it RLX_EUNSUP (widths, E > 16) or RLX_EINVAL, rlx_last_error() names the argument, and nothing is
+ * written.  Passes of 4096 rows and more run their hidden-layer GEMMs on the split-operand engine, as REDQ's.
+ * rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) block draws of the two updates ([B, A] each: eps_next the critic
+ * update's, eps_cur the policy update's); acting ignores it. */
+typedef struct rlx_crossq_hparams {              /* crossq/flax/default_config.py */
+  float gamma, target_entropy, log_std_min, log_std_max;
+  float lr_policy, lr_critic, lr_alpha;          /* learning_rate (1e-3) for all three in the reference */
+  float policy_adam_b1, critic_adam_b1;          /* 0.5, 0.5 */
+  float alpha_adam_b1;                           /* optax's default 0.9 (crossq.py: the entropy coefficient's plain optax.adam) */
+  float adam_b2, adam_eps;                       /* 0.999, 1e-8 */
+  float brn_momentum, brn_eps, brn_r_max, brn_d_max;   /* 0.99; batch_renorm.py:80-83: 1e-3, 3, 5 */
+  int32_t brn_warmup_steps;                      /* batch_renorm_warmup_steps (100000) */
+  int32_t ensemble_size;                         /* 2 */
+  const float *critic_states, *critic_next_states;   /* [B, Oc] the critics' own observation columns, or NULL both */
+} rlx_crossq_hparams;
+
+int64_t rlx_crossq_param_count(const rlx_mlp_desc* desc);   /* floats of one network's flat parameter vector */
+int64_t rlx_crossq_stats_count(const rlx_mlp_desc* desc);   /* floats of one network's running statistics */
+
+/* acting (crossq.py:135-143): the policy in EVAL mode on obs [N, pdesc->in_dim]; key, subkey = split(key_io) (HOST, advanced);
+ * action [N, A] = tanh(mean + std normal(subkey, (N, A))), or tanh(mean) when deterministic != 0 (the key advances either way). */
+int rlx_crossq_act_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const float* pstats, const float* obs, int64_t N,
+                       uint32_t key_io[2], int scheme, float* action, int deterministic, const rlx_crossq_hparams* hp, void* stream);
+
+/* the critic update (crossq.py:147-206) in one call on one stream, no host synchronisation: key, subkey = split(key); the policy in
+ * EVAL mode on s'; a' = tanh(.) from ONE block draw normal(subkey, (B, A)), logp' with the 1e-6 term; every critic in TRAIN mode on
+ * the 2 B rows [(s, a); (s', a')] in one joint pass; q = the first B outputs, next_q the last B; y = r + gamma (1 - term) (min_e next_q
+ * - alpha logp') under stop_gradient; q_loss = mean over E and B of (q - y)^2; plain Adam with critic_adam_b1 at step q_opt_count + 1
+ * over all E critics, no clipping; qstats advance.  q_opt_count_io (HOST) += 1.  metrics_out DEVICE float[10] in
+ * rlx_sac_update_f32's order: this call writes [0] q_loss and [7] critic_grad_norm and leaves the other slots alone.  pparams,
+ * pstats and log_alpha are only read. */
+int rlx_crossq_critic_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const float* pstats,
+                                 const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qstats /*[E*ns]*/,
+                                 const float* log_alpha, const float* states /*[B,O]*/, const float* next_states,
+                                 const float* actions, const float* rewards /*[B]*/, const float* terminations, int64_t B,
+                                 uint32_t key_io[2], int scheme, int64_t* q_opt_count_io /* += 1 */, const rlx_crossq_hparams* hp,
+                                 float* metrics_out /*DEVICE [10]*/, void* stream);
+
+/* the policy and entropy update (crossq.py:210-274) on the same batch: key, subkey = split(key); the policy in TRAIN mode on s; a
+ * block draw (B, A); the critics in EVAL mode with the statistics as the critic update left them; policy_loss = mean(alpha logp -
+ * min_e q), the gradient to the minimising critic (split evenly among exact ties, as jnp.min's); entropy_loss = mean(exp(log_alpha)
+ * (-logp - target_entropy)); Adam on the policy with policy_adam_b1 and on log_alpha with alpha_adam_b1, both at step pi_opt_count +
+ * 1; pstats advance.  pi_opt_count_io (HOST) += 1.  metrics_out: this call writes [1..6], [8] and [9] (= 0) and leaves [0] and [7]
+ * alone.  qparams and qstats are only read.  hp->critic_states (with critic_next_states non-NULL too) gives the critics' columns. */
+int rlx_crossq_policy_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, float* pstats,
+                                 const rlx_mlp_desc* qdesc, const float* qparams, const float* qstats, float* log_alpha, float* am,
+                                 float* av, const float* states /*[B,O]*/, int64_t B, uint32_t key_io[2], int scheme,
+                                 int64_t* pi_opt_count_io /* += 1 */, const rlx_crossq_hparams* hp, float* metrics_out, void* stream);
+
 /* =================================== REPPO ===============================================
  * Relative Entropy Pathwise Policy Optimization (rl_x/algorithms/reppo/pytorch): on-policy rollouts, soft TD-lambda targets,
  * per minibatch a distributional critic step and a pathwise policy step through the updated critic with a sampled KL trust

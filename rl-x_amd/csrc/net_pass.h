@@ -1,5 +1,6 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip and droq.hip (the
-// last four through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip, droq.hip and
+// crossq.hip (the last five through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of brn.hip (batch
+// renormalisation, the column-statistics layer), the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> [Dropout ->] {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
 // of blocks, the streams, and what differs in the graph (REPPO's critic).
@@ -76,6 +77,32 @@ static inline int bwd_rows_grid(const rlx_ctx* ctx, int64_t M) {
 static inline size_t head_stage_floats(int K, int N, int64_t M) {
   return a64((size_t)div_up(M, 32) * ((((size_t)K * N + 3) & ~size_t(3)) + (((size_t)N + 3) & ~size_t(3))));
 }
+
+// ---- brn.hip: batch renormalisation over the ROWS of x [M, D] (row stride ld, a multiple of four, 16-byte aligned; M >= 2), the
+// column-statistics layer (crossq/flax/batch_renorm.py:77-130; brn.hip's header has the arithmetic).  One launch serves E networks
+// whose buffers lie a fixed distance apart: x by e_x floats (0: one input shared by all), y / dY / dX by e_y, g / b / dg / db by e_p,
+// the running statistics by e_s.
+struct BrnCfg { float momentum, eps, r_max, d_max; };
+struct BrnEns { int E; int64_t e_x, e_y, e_p, e_s; };
+static inline int brn_dp(int D) { return (D + 3) & ~3; }
+constexpr int BRN_SAVE_ROWS = 7;
+// floats per network a training pass leaves for its backward (save: E of them back to back)
+static inline size_t brn_save_floats(int D) { return (size_t)BRN_SAVE_ROWS * brn_dp(D); }
+int brn_slabs(const rlx_ctx* ctx, int64_t M);                             // row slabs of the column sums: a function of M and num_cus only
+size_t brn_work_floats(const rlx_ctx* ctx, int64_t M, int D, int E);      // `work` of a training pass or a backward (reusable once issued)
+// y = (x - ra_mean) rsqrt(ra_var + eps) g + b: one launch, no state changes
+int brn_fwd_eval(const float* x, int ld, int64_t M, int D, const float* g, const float* b, const float* ra_mean, const float* ra_var,
+                 float eps, float* y, const BrnEns& n, hipStream_t st);
+// the training pass: y from the batch statistics under the clipped r / d correction (warmed) or plain batch norm (not warmed);
+// ra_mean / ra_var advance in place; save receives what brn_bwd needs
+int brn_fwd_train(const rlx_ctx* ctx, const float* x, int ld, int64_t M, int D, const float* g, const float* b, float* ra_mean, float* ra_var,
+                  const BrnCfg& cfg, bool warmed, float* y, float* save, float* work, const BrnEns& n, hipStream_t st);
+// dY (in dY_dX) -> dX, in place; save != NULL: the backward of the training pass that wrote it, else of an eval pass (from ra_mean,
+// ra_var and eps).  relu_mask: x is a ReLU's output and dX is multiplied by 1[x > 0].  dg / db (NULL: not wanted): the scale / bias
+// gradients.  Padding columns of dX are 0.
+int brn_bwd(const rlx_ctx* ctx, const float* x, int ld, int64_t M, int D, const float* g, const float* save, const float* ra_mean,
+            const float* ra_var, float eps, float* dY_dX, bool relu_mask, float* dg, float* db, float* work, const BrnEns& n,
+            hipStream_t st);
 
 // ---- scratch arena: a bump allocator over one scratch slot.  An entry point writes its carve ONCE, as a callable over an Arena&;
 // arena_carve runs it over a null base to measure, sizes the slot with that, and runs it again over the slot -- the total cannot

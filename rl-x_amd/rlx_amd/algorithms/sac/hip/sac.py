@@ -60,12 +60,12 @@ class SAC:
         self.buffer_size = int(config.algorithm.buffer_size)
         self.learning_starts = config.algorithm.learning_starts
         self.batch_size = int(config.algorithm.batch_size)
-        self.tau = config.algorithm.tau
+        self.tau = config.algorithm.get("tau", 0.0)                   # (crossq.hip, a subclass, has no target networks and no tau)
         self.gamma = config.algorithm.gamma
         self.target_entropy = config.algorithm.target_entropy
         self.log_std_min = float(config.algorithm.log_std_min)
         self.log_std_max = float(config.algorithm.log_std_max)
-        self.nr_hidden_units = int(config.algorithm.nr_hidden_units)
+        self.nr_hidden_units = int(config.algorithm.get("nr_hidden_units", None) or config.algorithm.policy_nr_hidden_units)   # (crossq.hip: two widths)
         self.logging_frequency = config.algorithm.logging_frequency
         self.evaluation_frequency = config.algorithm.evaluation_frequency
         self.evaluation_episodes = int(config.algorithm.evaluation_episodes)

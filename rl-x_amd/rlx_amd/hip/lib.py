@@ -98,6 +98,28 @@ class DroqHparams(Structure):
     _fields_ = RedqHparams._fields_ + [("dropout_rate", c_float)]
 
 
+class BrnConfig(Structure):
+    """rlx_brn_config: one batch-renormalisation layer's constants (crossq/flax/batch_renorm.py:80-83) and `warmed`"""
+    _fields_ = [("momentum", c_float), ("eps", c_float), ("r_max", c_float), ("d_max", c_float), ("warmed", c_int32)]
+
+
+def brn_config(momentum=0.99, eps=1e-3, r_max=3.0, d_max=5.0, warmed=False):
+    return BrnConfig(float(momentum), float(eps), float(r_max), float(d_max), int(bool(warmed)))
+
+
+BRN_EVAL_FWD, BRN_TRAIN_FWD, BRN_EVAL_BWD, BRN_TRAIN_BWD = 0, 1, 2, 3
+BRN_SAVE_ROWS = 7       # a training pass leaves BRN_SAVE_ROWS * ((D + 3) & ~3) floats per network for its backward
+BRN_SLAB_ROWS = 64      # rows per slab of the column sums (until M exceeds 4 * CUs slabs)
+
+
+class CrossqHparams(Structure):
+    """rlx_crossq_hparams (crossq/flax/default_config.py)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "target_entropy", "log_std_min", "log_std_max", "lr_policy", "lr_critic", "lr_alpha",
+                                       "policy_adam_b1", "critic_adam_b1", "alpha_adam_b1", "adam_b2", "adam_eps", "brn_momentum",
+                                       "brn_eps", "brn_r_max", "brn_d_max")] + [
+        ("brn_warmup_steps", c_int32), ("ensemble_size", c_int32), ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
+
+
 class ReppoDesc(Structure):
     """rlx_reppo_desc: REPPO's RMSNorm policy and branching critic (include/rlx_hip.h: flat layouts)."""
     _fields_ = [("policy_obs_dim", c_int32), ("critic_obs_dim", c_int32), ("act_dim", c_int32), ("policy_hidden", c_int32),
@@ -280,6 +302,16 @@ _SIGNATURES = {
                                    c_int, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "rlx_droq_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                             + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(DroqHparams), c_void_p, POINTER(c_int32), c_void_p]),
+    "rlx_brn_f32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, POINTER(BrnConfig), c_int, c_void_p, c_void_p,
+                            c_int, c_void_p, c_void_p]),
+    "rlx_crossq_param_count": (c_int64, [_DESCP]),
+    "rlx_crossq_stats_count": (c_int64, [_DESCP]),
+    "rlx_crossq_act_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_int64, _U32P, c_int, c_void_p, c_int,
+                                   POINTER(CrossqHparams), c_void_p]),
+    "rlx_crossq_critic_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, _DESCP] + [c_void_p] * 10
+                                     + [c_int64, _U32P, c_int, _I64P, POINTER(CrossqHparams), c_void_p, c_void_p]),
+    "rlx_crossq_policy_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 6
+                                     + [c_int64, _U32P, c_int, _I64P, POINTER(CrossqHparams), c_void_p, c_void_p]),
     "rlx_lstm_policy_param_count": (c_int64, [_LDESCP]),
     "rlx_ppo_lstm_rollout_begin": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p]),
     "rlx_ppo_lstm_act_f32": (c_int, [c_void_p, _LDESCP, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _U32P, c_int,
@@ -923,6 +955,53 @@ class Ctx:
         _check(self.lib.rlx_droq_block_f32(self.h, _ptr(Z, f), _ptr(H_io, f), _ptr(scale_bias, f), _key_arr(key), scheme, base, stride, count,
                                            int(j), int(E), int(l), int(L), M, D, float(rate), 0 if dg_out is None else 1,
                                            _ptr(dg_out, f, True), _ptr(db_out, f, True), _stream()), "rlx_droq_block_f32")
+
+    def brn(self, x, D, scale_bias, stats, cfg, mode, y_io, save=None, relu_mask=False, dgb_out=None):
+        """One batch-renormalisation layer (include/rlx_hip.h: rlx_brn_f32) over x [E, M, ld] or [M, ld] (never written), D <= ld
+        columns of which are data.  scale_bias / stats [E, 2 D].  mode BRN_EVAL_FWD / BRN_TRAIN_FWD: y_io receives y (the training
+        pass advances stats and fills save [E, BRN_SAVE_ROWS * ((D + 3) & ~3)]); BRN_EVAL_BWD / BRN_TRAIN_BWD: y_io holds dY and
+        receives dX (times 1[x > 0] under relu_mask), dgb_out [E, 2 D] the scale then bias gradients."""
+        f = self.torch.float32
+        E = int(x.shape[0]) if x.dim() == 3 else 1
+        M, ld = (int(v) for v in x.shape[-2:])
+        _check(self.lib.rlx_brn_f32(self.h, _ptr(x, f), ld, M, int(D), E, _ptr(scale_bias, f), _ptr(stats, f), ctypes.byref(cfg), int(mode),
+                                    _ptr(y_io, f), _ptr(save, f, True), int(bool(relu_mask)), _ptr(dgb_out, f, True), _stream()),
+               "rlx_brn_f32")
+
+    # ---- CrossQ
+    def crossq_counts(self, desc):
+        """(floats of one network's flat parameter vector, floats of its running statistics) under CrossQ's layout"""
+        return int(self.lib.rlx_crossq_param_count(ctypes.byref(desc))), int(self.lib.rlx_crossq_stats_count(ctypes.byref(desc)))
+
+    def crossq_act(self, pdesc, pparams, pstats, obs, key, action, hp, deterministic=False, scheme=THREEFRY_PARTITIONABLE):
+        """the policy in eval mode on obs [N, O] -> action [N, A]; returns the new key"""
+        f = self.torch.float32
+        k = _key_arr(key)
+        _check(self.lib.rlx_crossq_act_f32(self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pstats, f), _ptr(obs, f), int(obs.shape[0]), k,
+                                           scheme, _ptr(action, f), int(bool(deterministic)), ctypes.byref(hp), _stream()), "rlx_crossq_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def crossq_critic_update(self, pdesc, pparams, pstats, qdesc, qparams, qm, qv, qstats, log_alpha, batch, key, q_count, hp, metrics_out,
+                             scheme=THREEFRY_PARTITIONABLE):
+        """batch = (states [B, O], next_states, actions [B, A], rewards [B], terminations); returns (new_key, new_q_count)"""
+        f = self.torch.float32
+        k, qc = _key_arr(key), c_int64(int(q_count))
+        _check(self.lib.rlx_crossq_critic_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pstats, f), ctypes.byref(qdesc), _ptr(qparams, f), _ptr(qm, f), _ptr(qv, f),
+            _ptr(qstats, f), _ptr(log_alpha, f), *[_ptr(x, f) for x in batch], int(batch[3].numel()), k, scheme, ctypes.byref(qc),
+            ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_crossq_critic_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), qc.value
+
+    def crossq_policy_update(self, pdesc, pparams, pm, pv, pstats, qdesc, qparams, qstats, log_alpha, am, av, states, key, pi_count, hp,
+                             metrics_out, scheme=THREEFRY_PARTITIONABLE):
+        """the policy and entropy update on states [B, O]; returns (new_key, new_pi_count)"""
+        f = self.torch.float32
+        k, pc = _key_arr(key), c_int64(int(pi_count))
+        _check(self.lib.rlx_crossq_policy_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), _ptr(pstats, f), ctypes.byref(qdesc), _ptr(qparams, f),
+            _ptr(qstats, f), _ptr(log_alpha, f), _ptr(am, f), _ptr(av, f), _ptr(states, f), int(states.shape[0]), k, scheme, ctypes.byref(pc),
+            ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_crossq_policy_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), pc.value
 
     # ---- PPO + LSTM
     def lstm_policy_param_count(self, desc):

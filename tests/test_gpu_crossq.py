@@ -1,0 +1,338 @@
+"""GPU: rlx_crossq_critic_update_f32, rlx_crossq_policy_update_f32 and rlx_crossq_act_f32 against the twin (tests/crossq_twin.py) in
+float64 on the same float32 inputs: tests/test_gpu_droq.py's recipe.  A case is a critic update followed by a policy update on the
+same batch, with the N(0, 1) block draws injected through rlx_dbg_set_sac_noise; the keyed draws are checked on their own.
+
+Figures and bars are tests/test_gpu_redq.py's (BARS, and figures() restated without its Polyak figure QT: there are no target
+networks), with Pmax / Qmax by its rule 2 lr + 1e-6 at this file's learning rate, plus `ps` and `qs`, the two running-statistics
+vectors, at 1e-5 relative L2.  Multi-call and 4096-row cases take max(bar, 2 F32_GAP), F32_GAP being the twin in numpy float32
+against the twin in float64, measured once on a CPU (this file run as a script) and recorded below.  The TQC ReLU-kink rule is not
+used.
+
+Every case's builder asserts on the CPU, in every layer of every training pass, a batch variance of at least 1e-6 and -- where the
+pass is warmed, so that the clips matter -- a relative distance of at least 1e-3 of every unclipped r and d from its edges.  Two
+cases have so few rows that a ReLU unit would be dead in all of them (b2: 2 rows; wide: 16 rows of 2048 units), and the warmed
+cases (warm, e3, one_layer) move their layers through the r / d correction: their hidden Dense biases are raised by 0.5 / 1
+(dense_bias) so that every unit keeps a variance.  A unit that is then active in EVERY row makes its Dense bias a pure shift of
+the BRN that follows: its gradient is exactly 0, float32 leaves rounding noise of ~1e-9 there, and Adam with eps 1e-8 turns that
+noise into steps of up to a learning rate (measured: Qmax 4.6e-4 and a q_value off by 4e-5 with every moment within 3e-7).  Those
+cases therefore run Adam with eps 1e-5, under which such a step is ~1e-7; the other cases keep the reference's 1e-8."""
+import numpy as np
+import pytest
+import torch
+
+import crossq_twin as tw
+from oracle import nets, prng
+from rlx_amd.hip import RlxError, lib as L
+from test_gpu_redq import BARS as REDQ_BARS, _rel, _t
+
+pytestmark = pytest.mark.gpu
+
+KEY = prng.prng_key(11)
+LR = 1e-3
+BARS = {k: v for k, v in REDQ_BARS.items() if k != "QT"}
+BARS.update(Pmax=2 * LR + 1e-6, Qmax=2 * LR + 1e-6, ps=1e-5, qs=1e-5)
+VAR_FLOOR, MARGIN = 1e-6, 1e-3
+
+#        O  A   B   policy hidden  critic hidden     E  Oc    warmup  stats_away dense_bias
+CASES = {
+    "base": (5, 2, 67, [64, 64], [64, 64], 2, None, 100000, False, 0.0),
+    "warm": (5, 2, 67, [64, 64], [64, 64], 2, None, 0, True, 1.0),
+    "e1": (5, 2, 67, [64, 64], [64, 64], 1, None, 100000, False, 0.0),
+    "e3": (5, 2, 67, [64, 64], [64, 64], 3, None, 0, True, 1.0),
+    "critic_states": (12, 3, 70, [64, 64], [64, 64], 2, 9, 100000, False, 0.0),
+    "one_layer": (5, 2, 67, [128], [128], 2, None, 0, True, 1.0),
+    "three_layers": (5, 2, 67, [64, 192, 128], [64, 192, 128], 2, None, 100000, False, 0.0),
+    "b2": (5, 2, 2, [64, 64], [64, 64], 2, None, 100000, False, 0.5),
+    "wide": (5, 2, 8, [64, 64], [2048, 2048], 1, None, 100000, False, 0.5),
+    "rows4096": (5, 2, 4096, [64, 64], [64, 64], 2, None, 100000, False, 0.0),
+}
+SEEDS = {"e3": 1, "b2": 1}                                                                    # case -> seed (0 where not listed): python tests/test_gpu_crossq.py
+# the twin in float32 against the twin in float64, for the cases the rule above covers: python tests/test_gpu_crossq.py
+F32_GAP = {
+    "second": {"metrics": 4.36e-07, "norms": 2.12e-07, "pm": 9.86e-07, "qm": 6.33e-07, "pv": 9.62e-07, "qv": 1.99e-07, "ps": 2.77e-08, "qs": 2.43e-08, "la": 1.74e-08, "P99": 3.76e-08, "Pmax": 3.58e-07, "Q99": 4.64e-08, "Qmax": 1.82e-05},
+    "rows4096": {"metrics": 1.61e-07, "norms": 5.21e-06, "pm": 1.76e-06, "qm": 2.07e-04, "pv": 1.97e-06, "qv": 3.15e-05, "ps": 1.88e-08, "qs": 2.05e-08, "la": 1.29e-08, "P99": 4.05e-08, "Pmax": 2.10e-06, "Q99": 4.71e-08, "Qmax": 2.16e-07},
+}
+METRIC_SLOTS = {"critic": (0, 7), "policy": (1, 2, 3, 4, 5, 6, 8, 9)}
+
+
+class Case:
+    def __init__(self, name, seed=None):
+        O, A, B, ph, qh, E, Oc, warmup, away, bias = CASES[name]
+        self.name, self.O, self.A, self.B, self.E, self.Oc = name, O, A, B, E, O if Oc is None else Oc
+        p = tw.problem(100 * (SEEDS.get(name, 0) if seed is None else seed) + O + B + E, O, A, B, ph, qh, E, Oc, warmup, away, bias)
+        self.ps, self.qs, self.state, self.batch, self.cbatch, self.eps, self.h = (p[k] for k in ("ps", "qs", "state", "batch", "cbatch", "eps", "h"))
+        if bias:
+            self.h["adam_eps"] = 1e-5
+        self.pd = L.mlp_desc(O, ph, 2 * A, nets.ACT_RELU, False, False)
+        self.qd = L.mlp_desc(self.Oc + A, qh, 1, nets.ACT_RELU, False, False)
+
+    def hp(self, **kw):
+        h = dict(self.h, **kw)
+        return L.CrossqHparams(*[h[n] for n, _ in L.CrossqHparams._fields_[:16]], int(h["brn_warmup_steps"]), int(h["ensemble_size"]))
+
+    def twin(self, st, dtype=np.float64, variant=None, h=None):
+        """-> (state after the critic update, state after both, metrics of both, infos)"""
+        st = {k: (np.asarray(v, np.float32).astype(dtype) if k in tw.STATE_KEYS else v) for k, v in st.items()}
+        h = h or self.h
+        mid, m1, i1 = tw.critic_update(self.ps, self.qs, st, self.batch, self.cbatch, self.eps[0], h, variant)
+        new, m2, i2 = tw.policy_update(self.ps, self.qs, mid, self.batch, self.cbatch, self.eps[1], h)
+        return mid, new, dict(m1, **m2), (i1, i2)
+
+    def usable(self, st=None, h=None):
+        """the module docstring's conditions for the pair of calls from `st`"""
+        _, _, _, infos = self.twin(st or self.state, h=h)
+        return all(i["vmin"] >= VAR_FLOOR and (not i["warmed"] or i["margin"] >= MARGIN) for i in infos)
+
+
+class Run:
+    """a critic update, then (unless critic_only) a policy update, on device copies of a twin state"""
+
+    def __init__(self, ctx, dev, c, st, key=KEY, scheme=1, inject=True, critic_only=False, hp=None, prof=False):
+        self.t = t = {k: _t(st[k], dev) for k in tw.STATE_KEYS}
+        self.met = met = torch.full((10,), 7.0, device=dev)
+        hp = hp or c.hp()
+        keep = [_t(x, dev) for x in c.cbatch] if c.cbatch else []
+        if keep:
+            hp.critic_states, hp.critic_next_states = keep[0].data_ptr(), keep[1].data_ptr()
+        eps = (_t(c.eps[0], dev), _t(c.eps[1], dev)) if inject else (None, None)      # kept alive: the library holds the pointers
+        ctx.dbg_set_sac_noise(*eps)
+        batch = tuple(_t(x, dev) for x in c.batch)
+        if prof:
+            ctx.prof_begin()
+        try:
+            self.key1, self.q_count = ctx.crossq_critic_update(c.pd, t["pp"], t["ps"], c.qd, t["qp"], t["qm"], t["qv"], t["qs"], t["la"], batch,
+                                                               np.asarray(key, np.uint32), st["q_count"], hp, met, scheme)
+            self.key, self.pi_count = self.key1, st["pi_count"]
+            if not critic_only:
+                self.key, self.pi_count = ctx.crossq_policy_update(c.pd, t["pp"], t["pm"], t["pv"], t["ps"], c.qd, t["qp"], t["qs"], t["la"],
+                                                                   t["am"], t["av"], batch[0], self.key1, st["pi_count"], hp, met, scheme)
+        finally:
+            ctx.dbg_set_sac_noise(None, None)
+            if prof:
+                ctx.prof_end()
+        torch.cuda.synchronize()
+        self.out = {k: v.cpu().numpy() for k, v in t.items()}
+        self.metrics = met.cpu().numpy()
+
+    def same_bits(self, other):
+        return all(np.array_equal(self.out[k], other.out[k]) for k in tw.STATE_KEYS) and np.array_equal(self.metrics, other.metrics) \
+            and np.array_equal(self.key, other.key)
+
+
+def metrics_vector(met):
+    return [float(met[n]) for n in tw.METRICS] + [0.0]
+
+
+def figures(out, metrics, new, met):
+    """tests/test_gpu_redq.py's figures() without QT, under this twin's state keys, plus the statistics vectors"""
+    exp, m = metrics_vector(met), np.asarray(metrics, np.float64)
+    f = {"metrics": max(abs(m[i] - exp[i]) / max(abs(exp[i]), 1.0) for i in (0, 1, 2, 3, 4, 5, 8)),
+         "norms": max(abs(m[i] - exp[i]) / abs(exp[i]) for i in (6, 7))}
+    for k in ("pm", "qm", "pv", "qv", "ps", "qs"):
+        f[k] = _rel(out[k], new[k])
+    f["la"] = abs(float(out["la"][0]) - float(new["la"][0]))
+    for k, s in (("P", "pp"), ("Q", "qp")):
+        d = np.abs(np.asarray(out[s], np.float64) - new[s])
+        f[k + "99"], f[k + "max"] = float(np.quantile(d, 0.99)), float(d.max())
+    return f
+
+
+def f32_gap(c, st=None):
+    _, new, met, _ = c.twin(st or c.state)
+    _, new32, met32, _ = c.twin(st or c.state, np.float32)
+    return figures(new32, metrics_vector(met32), new, met)
+
+
+def check(c, r, new, met, label, gap_key=None):
+    f = figures(r.out, r.metrics, new, met)
+    gap = F32_GAP.get(gap_key, {})
+    bars = {k: max(b, 2 * gap.get(k, 0.0)) for k, b in BARS.items()}
+    print(f"crossq {label}: " + " ".join(f"{k} {v:.2e}/{bars[k]:.1e}" for k, v in f.items()))
+    assert r.metrics[9] == 0.0
+    print("    metrics got/exp: " + " ".join(f"{g:.7g}/{e:.7g}" for g, e in zip(r.metrics, metrics_vector(met))))
+    bad = {k: (v, bars[k]) for k, v in f.items() if not v <= bars[k]}
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_pair_of_updates_matches_the_twin(ctx, dev, name):
+    c = Case(name)
+    assert c.usable(), name
+    _, new, met, _ = c.twin(c.state)
+    r = Run(ctx, dev, c, c.state, scheme=1 if name != "e1" else 0)
+    assert (r.q_count, r.pi_count) == (1, 1)
+    check(c, r, new, met, name, name if name == "rows4096" else None)
+    if name in ("base", "warm", "wide"):                                       # identical bits of two identical calls
+        assert r.same_bits(Run(ctx, dev, c, c.state, scheme=1))
+
+
+def test_rows_4096_take_the_split_operand_engine(ctx, dev):
+    """4096 rows: the hidden-layer GEMMs run on the split-operand images (engine 1), tests/test_gpu_droq.py's profiler-row check.
+    Forward launches of 64 x 64: the critic update's joint pass over 8192 rows, E; over 4096 rows the policy on s' (1), the policy on
+    s (1) and the E critics of the policy update.  The ragged first layers (K 5 and 7) stay on the exact engine (engine 0)."""
+    c = Case("rows4096")
+    _, new, met, _ = c.twin(c.state)
+    r = Run(ctx, dev, c, c.state, prof=True)
+    check(c, r, new, met, "rows4096 profiled", "rows4096")
+    rows = [q for q in ctx.prof_rows() if q["kernel"] in ("k_gemm_fwd", "k_gemm_dx", "k_gemm_dw")]
+    print("crossq 4096 gemm rows:", [(q["kernel"], q["engine"], q["M"], q["N"], q["K"], q["launches"]) for q in rows])
+    if ctx.get_counter("gemm_bx") != 1:
+        assert all(q["engine"] == 0 for q in rows), rows
+        return
+    for M, n in ((8192, c.E), (4096, 2 + c.E)):
+        hidden = [q for q in rows if q["kernel"] == "k_gemm_fwd" and (q["M"], q["N"], q["K"]) == (M, 64, 64)]
+        assert hidden and {q["engine"] for q in hidden} == {1} and sum(q["launches"] for q in hidden) == n, (M, hidden)
+    first = [q for q in rows if q["kernel"] == "k_gemm_fwd" and q["K"] in (5, 7)]
+    assert first and {q["engine"] for q in first} == {0}, first
+    dx = [q for q in rows if q["kernel"] == "k_gemm_dx" and (q["N"], q["K"]) == (64, 64)]
+    assert dx and {q["engine"] for q in dx} == {1}, dx
+    assert r.same_bits(Run(ctx, dev, c, c.state))
+
+
+def test_second_pair_from_the_first_pairs_state(ctx, dev):
+    """non-zero moments and statistics, counts 1 -> 2"""
+    c = Case("warm")
+    _, st1, _, _ = c.twin(c.state)
+    st1 = {k: (np.asarray(v, np.float32).astype(np.float64) if k in tw.STATE_KEYS else v) for k, v in st1.items()}
+    assert c.usable(st1)
+    _, new, met, _ = c.twin(st1)
+    r = Run(ctx, dev, c, st1)
+    assert (r.q_count, r.pi_count) == (2, 2)
+    check(c, r, new, met, "second pair", "second")
+
+
+def test_pairs_across_the_warm_up_boundary(ctx, dev):
+    """counts warmup - 1 (not warmed), then warmup (warmed): the switch follows the two optimiser counts"""
+    c = Case("warm")
+    h = dict(c.h, brn_warmup_steps=3)
+    for count, warmed in ((2, False), (3, True)):
+        st = dict(c.state, q_count=count, pi_count=count)
+        assert c.usable(st, h)
+        _, new, met, infos = c.twin(st, h=h)
+        assert all(i["warmed"] == warmed for i in infos)
+        r = Run(ctx, dev, c, st, hp=c.hp(brn_warmup_steps=3))
+        assert (r.q_count, r.pi_count) == (count + 1, count + 1)
+        check(c, r, new, met, f"count {count}")
+    # and the two differ: the warmed pass is not the plain batch norm
+    cold = c.twin(dict(c.state, q_count=2, pi_count=2), h=h)[1]
+    hot = c.twin(dict(c.state, q_count=3, pi_count=3), h=h)[1]
+    assert _rel(cold["qm"], hot["qm"]) > 1e-3
+
+
+def test_critic_call_leaves_the_policy_side_alone(ctx, dev):
+    c = Case("base")
+    mid, _, met, _ = c.twin(c.state)
+    r = Run(ctx, dev, c, c.state, critic_only=True)
+    for k in ("pp", "pm", "pv", "ps", "la", "am", "av"):
+        assert np.array_equal(r.out[k], np.asarray(c.state[k], np.float32)), k
+    assert all(r.metrics[i] == 7.0 for i in METRIC_SLOTS["policy"]) and all(r.metrics[i] != 7.0 for i in METRIC_SLOTS["critic"])
+    assert _rel(r.out["qs"], mid["qs"]) <= BARS["qs"] and _rel(r.out["qm"], mid["qm"]) <= BARS["qm"]
+    # the policy call leaves the critic slots alone
+    full = Run(ctx, dev, c, c.state)
+    assert full.metrics[0] == r.metrics[0] and full.metrics[7] == r.metrics[7]
+
+
+@pytest.mark.parametrize("variant", ["zero_next_rows", "separate_halves"])
+def test_device_is_far_from_the_wrong_twins(ctx, dev, variant):
+    """a backward over the first B rows alone, and a pass that normalises the two halves separately, are both > 100 bars away"""
+    c = Case("base")
+    r = Run(ctx, dev, c, c.state, critic_only=True)
+    right = c.twin(c.state)[0]
+    wrong = c.twin(c.state, variant=variant)[0]
+    assert _rel(r.out["qm"], right["qm"]) <= BARS["qm"]
+    assert _rel(r.out["qm"], wrong["qm"]) > 100 * BARS["qm"], _rel(r.out["qm"], wrong["qm"])
+
+
+@pytest.mark.parametrize("scheme", [1, 0])
+def test_keyed_draws_and_key_chain(ctx, dev, scheme):
+    """without injection the block draws are prng.normal(subkey, (B, A)) of the oracle's chain, and the returned key is its key"""
+    c = Case("base")
+    k1, e1 = tw.key_chain(KEY, (c.B, c.A), bool(scheme))
+    k2, e2 = tw.key_chain(k1, (c.B, c.A), bool(scheme))
+    r = Run(ctx, dev, c, c.state, scheme=scheme, inject=False)
+    assert np.array_equal(r.key1, k1) and np.array_equal(r.key, k2)
+    c.eps = (e1.astype(np.float32), e2.astype(np.float32))
+    assert c.usable()
+    _, new, met, _ = c.twin(c.state)
+    check(c, r, new, met, f"keyed scheme {scheme}")                            # (the oracle's erfinv and the device's agree to an ulp, not bit for bit)
+    other = Run(ctx, dev, c, c.state, scheme=1 - scheme, inject=False)         # and the other scheme draws another block
+    assert not np.array_equal(other.key, r.key) and not np.array_equal(other.out["qm"], r.out["qm"])
+
+
+@pytest.mark.parametrize("N,A", [(1, 2), (67, 1), (67, 64), (4096 * 256 + 1, 1)])
+def test_acting(ctx, dev, N, A):
+    """deterministic and sampled; N 1, 67 and one past elem_grid's cap (the noise kernel's 4096 x 256 elements); A 1 and 64"""
+    O, ph = 3, [64]
+    rng = np.random.default_rng([N, A])
+    ps = tw.NetSpec(O, ph, 2 * A)
+    pp = (ps.init(rng) + 0.02 * rng.standard_normal(ps.n_params)).astype(np.float32)
+    pp[ps.W[ps.L]:] *= 0.3
+    pst = ps.fresh_stats()
+    pst[:O], pst[O:2 * O] = rng.uniform(-0.5, 0.5, O), rng.uniform(0.5, 2.0, O)
+    pst = pst.astype(np.float32)
+    obs = rng.standard_normal((N, O)).astype(np.float32)
+    h = tw.hparams(A)
+    pd = L.mlp_desc(O, ph, 2 * A, nets.ACT_RELU, False, False)
+    hp = L.CrossqHparams(*[h[n] for n, _ in L.CrossqHparams._fields_[:16]], int(h["brn_warmup_steps"]), int(h["ensemble_size"]))
+    k1, eps = tw.key_chain(KEY, (N, A))
+    tp, ts, to = _t(pp, dev), _t(pst, dev), _t(obs, dev)
+    for det in (True, False):
+        out = torch.full((N, A), 7.0, device=dev)
+        key = ctx.crossq_act(pd, tp, ts, to, KEY, out, hp, deterministic=det)
+        assert np.array_equal(key, k1)
+        got = out.cpu().numpy()
+        exp = np.concatenate([tw.act(ps, pp.astype(np.float64), pst.astype(np.float64), obs[i:i + 65536].astype(np.float64), eps[i:i + 65536], h, det)
+                              for i in range(0, N, 65536)])
+        assert np.abs(got - exp).max() <= 2e-6, (N, A, det, np.abs(got - exp).max())
+    assert np.array_equal(ts.cpu().numpy(), pst)                               # eval mode: no state changes
+
+
+REFUSALS = [("width_96", -4, "multiples of 64"), ("width_2112", -4, "at most 2048"), ("b_1", -1, "B must be at least 2"),
+            ("e_17", -4, "ensemble_size at most 16"), ("tanh", -1, "RLX_ACT_RELU"), ("one_critic_pointer", -1, "critic_states"),
+            ("momentum_1", -1, "brn_momentum"), ("momentum_neg", -1, "brn_momentum")]
+
+
+@pytest.mark.parametrize("what,code,word", REFUSALS)
+def test_refusals_write_nothing(ctx, dev, what, code, word):
+    c = Case("base")
+    hp, st = c.hp(), c.state
+    if what in ("width_96", "width_2112"):
+        c.qd = L.mlp_desc(c.Oc + c.A, [64, 96 if what == "width_96" else 2112], 1, nets.ACT_RELU, False, False)
+    elif what == "b_1":
+        c.batch = tuple(x[:1] for x in c.batch)
+        c.eps = tuple(x[:1] for x in c.eps)
+    elif what == "e_17":
+        hp = c.hp(ensemble_size=17)
+    elif what == "tanh":
+        c.pd = L.mlp_desc(c.O, [64, 64], 2 * c.A, nets.ACT_TANH, False, False)
+    elif what == "one_critic_pointer":
+        keep = _t(c.batch[0], dev)
+        hp.critic_states = keep.data_ptr()
+    elif what == "momentum_1":
+        hp = c.hp(brn_momentum=1.0)
+    elif what == "momentum_neg":
+        hp = c.hp(brn_momentum=-0.01)
+    t = {k: _t(st[k], dev) for k in tw.STATE_KEYS}
+    before = {k: v.clone() for k, v in t.items()}
+    met = torch.full((10,), 7.0, device=dev)
+    batch = tuple(_t(x, dev) for x in c.batch)
+    calls = (lambda: ctx.crossq_critic_update(c.pd, t["pp"], t["ps"], c.qd, t["qp"], t["qm"], t["qv"], t["qs"], t["la"], batch, KEY, 0, hp, met),
+             lambda: ctx.crossq_policy_update(c.pd, t["pp"], t["pm"], t["pv"], t["ps"], c.qd, t["qp"], t["qs"], t["la"], t["am"], t["av"],
+                                              batch[0], KEY, 0, hp, met))
+    for call in calls:
+        with pytest.raises(RlxError) as err:
+            call()
+        assert f"rc={code}" in str(err.value) and word in str(err.value), str(err.value)
+    torch.cuda.synchronize()
+    assert all(torch.equal(t[k], before[k]) for k in t) and bool((met == 7.0).all())
+
+
+if __name__ == "__main__":      # SEEDS and F32_GAP (CPU only)
+    seeds = {n: next(s for s in range(50) if Case(n, s).usable()) for n in CASES}
+    print("SEEDS =", {n: s for n, s in seeds.items() if s})
+    c = Case("warm", seeds["warm"])
+    st1 = c.twin(c.state)[1]
+    st1 = {k: (np.asarray(v, np.float32).astype(np.float64) if k in tw.STATE_KEYS else v) for k, v in st1.items()}
+    print("usable second:", c.usable(st1), "boundary:", [c.usable(dict(c.state, q_count=n, pi_count=n), dict(c.h, brn_warmup_steps=3)) for n in (2, 3)])
+    fmt = lambda g: "{" + ", ".join(f'"{k}": {v:.2e}' for k, v in g.items()) + "}"
+    print('F32_GAP = {\n    "second": ' + fmt(f32_gap(c, st1)) + ',\n    "rows4096": ' + fmt(f32_gap(Case("rows4096", seeds["rows4096"]))) + ",\n}")
