@@ -1,6 +1,7 @@
 """Python mirror of the host selection arithmetic the FastSAC / FastTD3 passes go through (rl-x_amd/csrc: net_pass.h, dense_head.hip,
-mlp.hip, gemm_bx.h / gemm_bx.hip, fastsac.hip): which kernel, which grid and which GEMM engine a shape gets.  The shape tests
-recompute each case's claims from these, and build the engine each profiled GEMM row has to show."""
+mlp.hip, gemm_bx.h / gemm_bx.hip, fastsac.hip) and the ensemble-SAC family's (sac_ens.h, redq.hip's redq_loop, tqc.hip): which kernel,
+which grid and which GEMM engine a shape gets.  The shape tests recompute each case's claims from these, and build the engine --
+for the ensemble family the launches per engine -- each profiled GEMM row has to show."""
 
 BX_MAX_JOBS = 32          # gemm_bx.h
 SPLIT_ROWS = 4096         # net_images / bx_dw_usable: rows from which the split-operand engine serves a pass
@@ -125,6 +126,97 @@ def expected_engines(update, bx, B, p_in, p_hidden, c_in, c_hidden, A):
                 put(("k_gemm_dw", d, w, B), 1 if bx_dw_usable(on, B, d, pad4(d), w) else 0)
             d = w
     return out
+
+
+# ------------------------------------------------------------------------ the ensemble-SAC family (sac_ens.h, redq.hip, tqc.hip)
+def ens_lanes_per_row(A):
+    """sac_ens.h ens_lanes_per_row: threads that share a row in k_ens_sample / k_ens_policy_grad -- the power of two at or above A,
+    at most 64"""
+    ap = 1
+    while ap < A and ap < 64:
+        ap <<= 1
+    return ap
+
+
+def ens_sample_rows_per_block(A):
+    """k_ens_sample / k_ens_policy_grad: (rows per 256-thread block, idle lanes per row)"""
+    ap = ens_lanes_per_row(A)
+    return 256 // ap, ap - A
+
+
+def drop_ln_relu_form(D):
+    """dense_head.hip launch_drop_ln_relu: NJMAX of the k_drop_ln_relu instance a block of D units gets (4: the lean form, D <= 256;
+    12: the wide one, D <= 768)"""
+    assert D % 64 == 0 and 0 < D <= 768
+    return 4 if D <= 256 else 12
+
+
+def ens_nets(algo, step, p_in, p_hidden, c_in, c_hidden, E, M=None):
+    """The list redq_loop (REDQ and DroQ: M selected targets; AQE: M = E) hands to trunk_images in front of a critic step ("critic")
+    and of the policy step ("policy"), and rlx_tqc_update_f32's one list ("update"), in their order.  A net is
+    (in_dim, hidden, bwd, fwd, grads, dxa): trunk_images' (in_dim, hidden, bwd) and the passes that use the images -- forward
+    passes, backward passes with weight gradients, backward passes for the input gradient on the action columns alone."""
+    pol, cri = (p_in, tuple(p_hidden)), (c_in, tuple(c_hidden))
+    if algo == "tqc":               # policy on s' and on s, one backward; online critics on (s, a) with gradients and on (s, a~) for dQ/da
+        assert step == "update"
+        return [pol + (True, 2, 1, 0)] + [cri + (True, 2, 1, 1)] * E + [cri + (False, 1, 0, 0)] * E
+    M = E if algo == "aqe" else M
+    if step == "critic":
+        return [pol + (False, 1, 0, 0)] + [cri + (False, 1, 0, 0)] * M + [cri + (True, 1, 1, 0)] * E
+    assert step == "policy"
+    return [pol + (True, 1, 1, 0)] + [cri + (True, 1, 0, 1)] * E
+
+
+def image_cut(nets):
+    """where trunk_images' list ends: (net index, layer) of the first matrix without an image although its input width is aligned,
+    None when every aligned matrix got one"""
+    have = trunk_images([n[:3] for n in nets])[2]
+    for i, (in_dim, hidden, *_) in enumerate(nets):
+        d = in_dim
+        for l, w in enumerate(hidden):
+            if d % 4 == 0 and (i, l) not in have:
+                return i, l
+            d = w
+    return None
+
+
+def expected_engine_counts(steps, bx, B, A):
+    """{(kernel, M, N, K): {engine: launches}} of every trunk GEMM the profiler sees over `steps`: one ens_nets list per trunk_images
+    call, each with the passes that follow it (expected_engines' rules and prof-row shapes).  Where a list ends inside a network,
+    or between two networks of one shape, that shape shows on both engines."""
+    on = bool(bx) and B >= SPLIT_ROWS
+    out = {}
+
+    def put(key, eng, n):
+        if n:
+            e = out.setdefault(key, {})
+            e[eng] = e.get(eng, 0) + n
+    for nets in steps:
+        have = trunk_images([n[:3] for n in nets])[2] if on else set()
+        for i, (in_dim, hidden, bwd, fwd, grads, dxa) in enumerate(nets):
+            assert bwd or not (grads or dxa)
+            d = in_dim
+            for l, w in enumerate(hidden):
+                eng = 1 if (i, l) in have else 0
+                put(("k_gemm_fwd", B, w, d), eng, fwd)
+                if l > 0:
+                    put(("k_gemm_dx", B, d, w), eng, grads + dxa)
+                elif not dx_cols_ok(w, A):
+                    put(("k_gemm_dx", B, d, w), 0, dxa)             # first_layer_dx's whole-GEMM fallback: no transposed image
+                put(("k_gemm_dw", d, w, B), 1 if bx_dw_usable(on, B, d, pad4(d), w) else 0, grads)
+                d = w
+    return out
+
+
+def check_engine_counts(rows, expected):
+    """every profiled trunk GEMM row against expected_engine_counts: the same shapes, and per shape the same launches per engine"""
+    seen = {}
+    for q in rows:
+        if q["kernel"] in ("k_gemm_fwd", "k_gemm_dx", "k_gemm_dw"):
+            e = seen.setdefault((q["kernel"], q["M"], q["N"], q["K"]), {})
+            e[q["engine"]] = e.get(q["engine"], 0) + q["launches"]
+    bad = {k: (seen.get(k), expected.get(k)) for k in set(seen) | set(expected) if seen.get(k) != expected.get(k)}
+    assert not bad, bad
 
 
 def check_engines(rows, expected):

@@ -67,13 +67,18 @@ def _hp(E, H, dropped, G, target_entropy=-1.0, delta=0.0):
 
 
 class Case:
-    def __init__(self, name):
-        O, A, B, ph, qh, E, H, dropped, G, Oc, delta = CASES[name]
+    """name: a key of CASES -- or a row in CASES' form for a case of another table (tests/ens_cases.py), then called `label`, drawn from
+    `seed` (the inputs) and seed + 1 (the noise), with no float32 gap until that table sets one (self.gap)"""
+
+    def __init__(self, name, label=None, seed=None):
+        O, A, B, ph, qh, E, H, dropped, G, Oc, delta = CASES[name] if isinstance(name, str) else name
+        name = name if isinstance(name, str) else label
         self.name, self.O, self.A, self.B, self.E, self.H, self.dropped, self.G, self.delta = name, O, A, B, E, H, dropped, G, delta
         self.Oc = O if Oc is None else Oc
-        p = tw.problem(O + B + G, O, A, B, ph, qh, E, H, dropped, G, Oc)
+        self.gap = F32_GAP.get(name, {})
+        p = tw.problem(O + B + G if seed is None else seed, O, A, B, ph, qh, E, H, dropped, G, Oc)
         self.ps, self.qs, self.state, self.batch, self.cbatch, self.h = p["ps"], p["qs"], p["state"], p["batch"], p["cbatch"], p["h"]
-        rng = np.random.default_rng(7 + B)
+        rng = np.random.default_rng(7 + B if seed is None else seed + 1)
         self.eps = (rng.standard_normal((G, B, A)).astype(np.float32), rng.standard_normal((B, A)).astype(np.float32))
         self.pd = mlp_desc(O, ph, 2 * A, nets.ACT_RELU, False, False)
         self.qd = mlp_desc(self.Oc + A, qh, H, nets.ACT_RELU, False, False)
@@ -160,8 +165,7 @@ def f32_gap(c):
 
 def check(c, r, new, met, label):
     f = figures(r.out, r.metrics, new, met)
-    gap = F32_GAP.get(c.name, {})
-    bars = {k: max(b, 2 * gap.get(k, 0.0)) for k, b in BARS.items()}
+    bars = {k: max(b, 2 * c.gap.get(k, 0.0)) for k, b in BARS.items()}
     print(f"aqe update {label}: " + " ".join(f"{k} {v:.2e}/{bars[k]:.1e}" for k, v in f.items()))
     assert r.metrics[9] == 0.0
     bad = {k: (v, bars[k]) for k, v in f.items() if not v <= bars[k]}
@@ -169,7 +173,8 @@ def check(c, r, new, met, label):
 
 
 def _run_and_check(ctx, dev, name, scheme=1, prof=False):
-    c = Case(name)
+    c = name if isinstance(name, Case) else Case(name)                             # (a Case of another table: tests/ens_cases.py)
+    name = c.name
     r = Run(ctx, dev, c, c.state, KEY, scheme, inject=c.eps, prof=prof)
     key_e, _ = c.chain(KEY, scheme)
     assert np.array_equal(r.key, key_e)                                            # the oracle's chain: G + 1 splits of B + 1

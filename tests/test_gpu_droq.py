@@ -51,13 +51,18 @@ F32_GAP = {
 
 
 class Case:
-    def __init__(self, name):
-        O, A, B, ph, qh, E, M, G, Oc, delta, rate = CASES[name]
+    """name: a key of CASES -- or a row in CASES' form for a case of another table (tests/ens_cases.py), then called `label`, drawn from
+    `seed` (the inputs) and seed + 1 (the noise), with no float32 gap until that table sets one (self.gap)"""
+
+    def __init__(self, name, label=None, seed=None):
+        O, A, B, ph, qh, E, M, G, Oc, delta, rate = CASES[name] if isinstance(name, str) else name
+        name = name if isinstance(name, str) else label
         self.name, self.O, self.A, self.B, self.E, self.M, self.G, self.Oc, self.delta = name, O, A, B, E, M, G, O if Oc is None else Oc, delta
         self.rate, self.qh = rate, qh
-        p = tw.problem(O + B + G, O, A, B, ph, qh, E, M, G, Oc, rate=rate)
+        self.gap = F32_GAP.get(name, {})
+        p = tw.problem(O + B + G if seed is None else seed, O, A, B, ph, qh, E, M, G, Oc, rate=rate)
         self.ps, self.qs, self.state, self.batch, self.cbatch, self.h = p["ps"], p["qs"], p["state"], p["batch"], p["cbatch"], p["h"]
-        rng = np.random.default_rng(7 + B)
+        rng = np.random.default_rng(7 + B if seed is None else seed + 1)
         self.eps = (rng.standard_normal((G, B, A)).astype(np.float32), rng.standard_normal((B, A)).astype(np.float32))
         self.pd = mlp_desc(O, ph, 2 * A, nets.ACT_RELU, False, False)
         self.qd = mlp_desc(self.Oc + A, qh, 1, nets.ACT_RELU, False, False)
@@ -134,8 +139,7 @@ def f32_gap(c):
 
 
 def bars_of(c):
-    gap = F32_GAP.get(c.name, {})
-    return {k: max(b, 2 * gap.get(k, 0.0)) for k, b in BARS.items()}
+    return {k: max(b, 2 * c.gap.get(k, 0.0)) for k, b in BARS.items()}
 
 
 def check(c, r, new, met, label):
@@ -147,7 +151,8 @@ def check(c, r, new, met, label):
 
 
 def _run_and_check(ctx, dev, name, scheme=1, prof=False):
-    c = Case(name)
+    c = name if isinstance(name, Case) else Case(name)                             # (a Case of another table: tests/ens_cases.py)
+    name = c.name
     r = Run(ctx, dev, c, c.state, KEY, scheme, inject=c.eps, prof=prof)
     key_e, sks, _ = c.chain(KEY, scheme)
     assert np.array_equal(r.key, key_e)                                            # the oracle's chain: G splits of 3 B + 2, one of 2 B + 1

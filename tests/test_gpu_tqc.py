@@ -29,10 +29,10 @@ def _rel(got, exp):
 class Case:
     """test_sac_update_matches_oracle's inputs (head_scale 0.1) for E critics of N atoms; Oc: the critics' own observation width"""
 
-    def __init__(self, O, A, B, ph, qh, E, N, dropped, Oc=None, kappa=1.0):
+    def __init__(self, O, A, B, ph, qh, E, N, dropped, Oc=None, kappa=1.0, seed=None):
         self.O, self.A, self.B, self.E, self.N, self.dropped, self.ph, self.qh = O, A, B, E, N, dropped, list(ph), list(qh)
         self.Oc = O if Oc is None else Oc
-        rng = np.random.default_rng(O + B)
+        rng = np.random.default_rng(O + B if seed is None else seed)
         self.ps, self.qs = ps, qs = tw.make_specs(O, self.Oc, A, self.ph, self.qh, N)
         pp = (sac.lecun_normal_init(ps, rng) + 0.02 * rng.standard_normal(ps.n_params)).astype(np.float32)
         pp[ps.head["W"]:ps.head["W"] + ps.head["in"] * ps.head["out"]] *= 0.1
@@ -52,10 +52,13 @@ class Case:
         h = self.h
         return TqcHparams(GAMMA, TAU, h["target_entropy"], -20.0, 2.0, LR, LR, LR, 0.9, 0.999, 1e-8, h["huber_kappa"], self.E, self.N, self.dropped)
 
-    def twin(self, st, eps):
-        """-> tw.update's (new state, metrics, gradients, aux)"""
+    def twin(self, st, eps, dtype=np.float64):
+        """-> tw.update's (new state, metrics, gradients, aux); dtype: the arithmetic of the whole evaluation (the state's float32
+        values in it)"""
         cb = self.cbatch or (None, None)
-        f = lambda x: None if x is None else x.astype(np.float64)
+        f = lambda x: None if x is None else x.astype(dtype)
+        if dtype != np.float64:
+            st = {k: (np.asarray(v, np.float32).astype(dtype) if k in tw.STATE_KEYS else v) for k, v in st.items()}
         return tw.update(self.ps, self.qs, st, tuple(f(x) for x in self.batch), f(eps[0]), f(eps[1]), self.h, LR, TAU, f(cb[0]), f(cb[1]))
 
 

@@ -44,10 +44,18 @@ def truncated_target(next_atoms, rewards, terminations, alpha, next_logp, gamma,
     return rewards[:, None] + gamma * (1 - terminations)[:, None] * (z - alpha * next_logp[:, None])
 
 
-def pair_loss(q_atoms, y, kappa):
-    """tqc.py:161-170 for a batch: q_atoms [B, T], y [B, K] -> (per-sample loss [B], d mean_b(loss) / d q_atoms [B, T])"""
+PAIR_ROWS = 4096
+
+
+def pair_loss(q_atoms, y, kappa, batch=None):
+    """tqc.py:161-170 for a batch: q_atoms [B, T], y [B, K] -> (per-sample loss [B], d mean_b(loss) / d q_atoms [B, T]); batch: the
+    size of the batch the mean is taken over when the rows are a part of it"""
     B, T = q_atoms.shape
     K = y.shape[1]
+    if B > PAIR_ROWS:                 # rows are independent: the same arithmetic per row, PAIR_ROWS of them at a time ([B, T, K] temporaries)
+        parts = [pair_loss(q_atoms[i:i + PAIR_ROWS], y[i:i + PAIR_ROWS], kappa, batch=batch or B) for i in range(0, B, PAIR_ROWS)]
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    B = batch or B
     tau = ((np.arange(T, dtype=q_atoms.dtype) + 0.5) / T)[None, :, None]
     delta = y[:, None, :] - q_atoms[:, :, None]                       # [B, T, K]
     ad = np.abs(delta)
