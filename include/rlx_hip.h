@@ -985,8 +985,8 @@ int rlx_brn_f32(rlx_ctx*, const float* x, int ld, int64_t M, int D, int E, const
  * critics q_opt_count >= brn_warmup_steps, policy pi_opt_count >= brn_warmup_steps (in the reference a net's `steps` equals its
  * number of updates).
  * Envelope: hidden widths multiples of 64 up to 2048, 1..3 hidden layers, A <= 64, B >= 2 (one row has zero batch variance),
- * 1 <= ensemble_size <= 16; outside it RLX_EUNSUP (widths, E > 16) or RLX_EINVAL, rlx_last_error() names the argument, and nothing is
- * written.  Passes of 4096 rows and more run their hidden-layer GEMMs on the split-operand engine, as REDQ's.
+ * 1 <= ensemble_size <= 16; outside it RLX_EUNSUP (widths, E > 16, and A > 64 in the two updates) or RLX_EINVAL, rlx_last_error() names
+ * the argument, and nothing is written.  Passes of 4096 rows and more run their hidden-layer GEMMs on the split-operand engine, as REDQ's.
  * rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the N(0, 1) block draws of the two updates ([B, A] each: eps_next the critic
  * update's, eps_cur the policy update's); acting ignores it. */
 typedef struct rlx_crossq_hparams {              /* crossq/flax/default_config.py */

@@ -17,7 +17,15 @@ ZERO BATCH VARIANCE: the reference's sqrt(v) has an infinite derivative at v = 0
 and this twin take that term's gradient as 0 where w = 0 or v = 0.
 
 The reference's CrossQ exists in JAX only and JAX is not installed: PARITY UNPINNED by the reference.  The dtype of x is the dtype of
-the whole evaluation; the constants are taken through float32, as the library receives them."""
+the whole evaluation; the constants are taken through float32, as the library receives them.
+
+FLOAT32 MODES.  A float32 evaluation is what separates float32 rounding from a wrong kernel (tests/test_gpu_crossq.py F32_GAP).  Plain
+float32 (dsum=False) takes the column sums and the one-pass variance in float32 too, which brn.hip does not: k_brn_colsum and
+k_brn_finish_* accumulate and do the per-column arithmetic in double because float loses it (at 4096 rows the plain mode is 2e-4 off
+in the critics' first moments).  dsum=True is float32 AS THE KERNELS ACCUMULATE: mu, v, the clips, cm, s, rho, t, sdy, sdyx, dg, db
+and the statistics update in float64, cast to float32 where the kernels store float32 (rho, s, t, the coefficients of the element-wise
+passes, dg, db, the statistics; mu and cm stay float pairs, i.e. double); the element-wise passes and the GEMMs in float32.  On float64
+inputs dsum changes nothing that is computed."""
 import numpy as np
 
 EPS, R_MAX, D_MAX, MOMENTUM = 1e-3, 3.0, 5.0, 0.99
@@ -28,12 +36,13 @@ class BrnCfg:
         self.momentum, self.eps, self.r_max, self.d_max = (float(np.float32(v)) for v in (momentum, eps, r_max, d_max))
 
 
-def brn_eval(x, g, b, ra_mean, ra_var, cfg):
-    """-> (y, cache): the running statistics as they are; nothing advances"""
+def brn_eval(x, g, b, ra_mean, ra_var, cfg, dsum=False):
+    """-> (y, cache): the running statistics as they are; nothing advances.  (dsum: an eval pass has no column sums; the flag only
+    reaches the backward's dg and db)"""
     dt = x.dtype
     rho = (1.0 / np.sqrt(ra_var + dt.type(cfg.eps))).astype(dt)
     y = ((x - ra_mean) * rho * g + b).astype(dt)
-    return y, {"train": False, "x": x, "g": g, "cm": ra_mean.astype(dt), "rho": rho}
+    return y, {"train": False, "dsum": dsum, "x": x, "g": g, "cm": ra_mean.astype(dt), "rho": rho}
 
 
 def brn_batch_stats(x):
@@ -51,9 +60,60 @@ def brn_clips(mu, v, ra_mean, ra_var, cfg):
     return r_raw, d_raw, np.clip(r_raw, dt.type(1.0 / cfg.r_max), dt.type(cfg.r_max)), np.clip(d_raw, dt.type(-cfg.d_max), dt.type(cfg.d_max))
 
 
-def brn_train(x, g, b, ra_mean, ra_var, cfg, warmed):
-    """-> (y, cache, new_ra_mean, new_ra_var)"""
+def _pair(v, dt):
+    """a float64 vector as brn.hip's float pair -> (hi, lo) in dt"""
+    hi = v.astype(dt)
+    return hi, (v - hi.astype(np.float64)).astype(dt)
+
+
+def brn_train_dsum(x, g, b, ra_mean, ra_var, cfg, warmed):
+    """brn_train as k_brn_colsum / k_brn_finish_fwd / k_brn_apply_fwd compute it on x of a narrower type: the column sums and the
+    per-column arithmetic in float64, the element-wise pass in x's type"""
+    dt, f8 = x.dtype, np.float64
+    x8 = x.astype(f8)
+    mu, v = brn_batch_stats(x8)
+    ram, rav = ra_mean.astype(f8), ra_var.astype(f8)
+    r_raw, d_raw, r, d = brn_clips(mu, v, ram, rav, cfg)
+    w = 1.0 if warmed else 0.0
+    sq = np.sqrt(v)
+    cm = mu - w * d * sq / r
+    s = w / (r * r) + (1 - w)
+    rho = 1.0 / np.sqrt(v * s + cfg.eps)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where((w > 0) & (v > 0), (d / r) / (2 * sq), 0)
+    cm_hi, cm_lo = _pair(cm, dt)
+    y = (((x - cm_hi) - cm_lo) * (rho * g.astype(f8)).astype(dt) + b).astype(dt)
+    m = cfg.momentum
+    cache = {"train": True, "dsum": True, "x": x, "g": g, "mu": mu, "v": v, "r": r, "d": d, "cm": cm_hi.astype(f8) + cm_lo.astype(f8),
+             "s": s.astype(dt), "rho": rho.astype(dt), "t": t.astype(dt), "r_raw": r_raw, "d_raw": d_raw}
+    return y, cache, (m * ram + (1 - m) * mu).astype(dt), (m * rav + (1 - m) * v).astype(dt)
+
+
+def brn_backward_dsum(dY, cache, relu_mask=False):
+    """brn_backward as k_brn_colsum<BWD> / k_brn_finish_bwd / k_brn_apply_bwd compute it"""
+    x, g = cache["x"], cache["g"]
+    dt, f8 = x.dtype, np.float64
+    M = x.shape[0]
+    x8, dY8, g8 = x.astype(f8), dY.astype(f8), g.astype(f8)
+    sdy, sdyx = dY8.sum(axis=0), (dY8 * x8).sum(axis=0)
+    cm, rho = cache["cm"].astype(f8), cache["rho"].astype(f8)
+    dX = dY * (g8 * rho).astype(dt)
+    if cache["train"]:
+        S1, S2 = g8 * sdy, g8 * (sdyx - cm * sdy)
+        dcm, dcv = -rho * S1, -0.5 * rho ** 3 * S2
+        dv = dcv * cache["s"].astype(f8) - dcm * cache["t"].astype(f8)
+        mu_hi, mu_lo = _pair(cache["mu"], dt)
+        dX = dX + ((2 * dv / M).astype(dt) * ((x - mu_hi) - mu_lo) + (dcm / M).astype(dt))
+    if relu_mask:
+        dX = dX * (x > 0)
+    return dX.astype(dt), (rho * (sdyx - cm * sdy)).astype(dt), sdy.astype(dt)
+
+
+def brn_train(x, g, b, ra_mean, ra_var, cfg, warmed, dsum=False):
+    """-> (y, cache, new_ra_mean, new_ra_var).  dsum: see FLOAT32 MODES"""
     dt = x.dtype
+    if dsum and dt != np.float64:
+        return brn_train_dsum(x, g, b, ra_mean, ra_var, cfg, warmed)
     mu, v = brn_batch_stats(x)
     r_raw, d_raw, r, d = brn_clips(mu, v, ra_mean, ra_var, cfg)
     w = dt.type(1.0 if warmed else 0.0)
@@ -75,6 +135,9 @@ def brn_backward(dY, cache, relu_mask=False, keep_sqrt_term=True):
     gradient of cm's sqrt(v) term everywhere (what the zero-variance rule does on a constant column)."""
     x, g, cm, rho = cache["x"], cache["g"], cache["cm"], cache["rho"]
     dt = x.dtype
+    if cache.get("dsum") and dt != np.float64:
+        assert keep_sqrt_term
+        return brn_backward_dsum(dY, cache, relu_mask)
     M = x.shape[0]
     xc = x - cm
     db = dY.sum(axis=0)
@@ -133,7 +196,7 @@ class NetSpec:
         return s
 
 
-def net_forward(spec, p, stats, x, train, warmed, cfg, groups=None):
+def net_forward(spec, p, stats, x, train, warmed, cfg, groups=None, dsum=False):
     """-> (head output [M, out], caches, new statistics).  groups: row slices normalised SEPARATELY in a training pass (None: the
     whole batch together, as the reference does; the statistics then advance from the first group)"""
     dt = x.dtype
@@ -143,12 +206,12 @@ def net_forward(spec, p, stats, x, train, warmed, cfg, groups=None):
         g, b = p[spec.bn[l]:spec.bn[l] + D], p[spec.bn[l] + D:spec.bn[l] + 2 * D]
         m0, v0 = stats[spec.st[l]:spec.st[l] + D], stats[spec.st[l] + D:spec.st[l] + 2 * D]
         if not train:
-            y, bc = brn_eval(h, g, b, m0, v0, cfg)
+            y, bc = brn_eval(h, g, b, m0, v0, cfg, dsum)
             bcs = [(slice(None), bc)]
         else:
             y, bcs = np.empty_like(h), []
             for i, rows in enumerate(groups or [slice(None)]):
-                y[rows], bc, m1, v1 = brn_train(h[rows], g, b, m0, v0, cfg, warmed)
+                y[rows], bc, m1, v1 = brn_train(h[rows], g, b, m0, v0, cfg, warmed, dsum)
                 bcs.append((rows, bc))
                 if i == 0:
                     new_stats[spec.st[l]:spec.st[l] + D], new_stats[spec.st[l] + D:spec.st[l] + 2 * D] = m1, v1
@@ -228,7 +291,7 @@ def cfg_of(h):
     return BrnCfg(h["brn_momentum"], h["brn_eps"], h["brn_r_max"], h["brn_d_max"])
 
 
-def critic_update(ps, qs, st, batch, cbatch, eps, h, variant=None):
+def critic_update(ps, qs, st, batch, cbatch, eps, h, variant=None, dsum=False):
     """crossq.py:147-206 -> (new state, metrics, info).  batch = (s, s', a, r, term); cbatch = (cs, cs') or None; eps [B, A].
     variant: None, "zero_next_rows" (the next-state rows' gradients zeroed below the last BRN) or "separate_halves" (the two halves
     normalised separately): two wrong implementations a device result must be far from"""
@@ -237,7 +300,7 @@ def critic_update(ps, qs, st, batch, cbatch, eps, h, variant=None):
     cs, cs2 = (s, s2) if cbatch is None else (np.asarray(x).astype(dt) for x in cbatch)
     B, E, cfg = s.shape[0], h["ensemble_size"], cfg_of(h)
     alpha = np.exp(st["la"][0])
-    head, _, _ = net_forward(ps, st["pp"], st["ps"], s2, False, False, cfg)
+    head, _, _ = net_forward(ps, st["pp"], st["ps"], s2, False, False, cfg, dsum=dsum)
     a2, logp2, _, _ = sample(head, eps.astype(dt), h["log_std_min"], h["log_std_max"])
     x = np.concatenate([np.concatenate([cs, a], axis=1), np.concatenate([cs2, a2], axis=1)], axis=0)
     warmed = st["q_count"] >= h["brn_warmup_steps"]
@@ -245,7 +308,7 @@ def critic_update(ps, qs, st, batch, cbatch, eps, h, variant=None):
     outs, caches, new_qs = [], [], []
     for e in range(E):
         o, c, ns = net_forward(qs, st["qp"][e * qs.n_params:(e + 1) * qs.n_params], st["qs"][e * qs.n_stats:(e + 1) * qs.n_stats], x, True, warmed,
-                               cfg, groups)
+                               cfg, groups, dsum)
         outs.append(o[:, 0]); caches.append(c); new_qs.append(ns)
     q = np.stack(outs, axis=1)                                                     # [2 B, E]
     y = r + dt.type(np.float32(h["gamma"])) * (1 - term) * (q[B:].min(axis=1) - alpha * logp2)
@@ -268,7 +331,7 @@ def critic_update(ps, qs, st, batch, cbatch, eps, h, variant=None):
     return new, {"loss/q_loss": float(q_loss), "gradients/critic_grad_norm": float(np.sqrt((g * g).sum()))}, info
 
 
-def policy_update(ps, qs, st, batch, cbatch, eps, h):
+def policy_update(ps, qs, st, batch, cbatch, eps, h, dsum=False):
     """crossq.py:210-274 -> (new state, metrics, info)"""
     dt = st["pp"].dtype
     s = np.asarray(batch[0]).astype(dt)
@@ -279,12 +342,13 @@ def policy_update(ps, qs, st, batch, cbatch, eps, h):
     la = st["la"][0]
     alpha = np.exp(la)
     warmed = st["pi_count"] >= h["brn_warmup_steps"]
-    head, pc, new_ps = net_forward(ps, st["pp"], st["ps"], s, True, warmed, cfg)
+    head, pc, new_ps = net_forward(ps, st["pp"], st["ps"], s, True, warmed, cfg, dsum=dsum)
     a, logp, std, inside = sample(head, eps, h["log_std_min"], h["log_std_max"])
     x = np.concatenate([cs, a], axis=1)
     qa, qc = [], []
     for e in range(E):
-        o, c, _ = net_forward(qs, st["qp"][e * qs.n_params:(e + 1) * qs.n_params], st["qs"][e * qs.n_stats:(e + 1) * qs.n_stats], x, False, False, cfg)
+        o, c, _ = net_forward(qs, st["qp"][e * qs.n_params:(e + 1) * qs.n_params], st["qs"][e * qs.n_stats:(e + 1) * qs.n_stats], x, False, False, cfg,
+                              dsum=dsum)
         qa.append(o[:, 0]); qc.append(c)
     qa = np.stack(qa, axis=1)
     mn = qa.min(axis=1)

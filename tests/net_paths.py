@@ -1,6 +1,7 @@
 """Python mirror of the host selection arithmetic the FastSAC / FastTD3 passes go through (rl-x_amd/csrc: net_pass.h, dense_head.hip,
 mlp.hip, gemm_bx.h / gemm_bx.hip, fastsac.hip) and the ensemble-SAC family's (sac_ens.h, redq.hip's redq_loop, tqc.hip): which kernel,
-which grid and which GEMM engine a shape gets.  The shape tests recompute each case's claims from these, and build the engine --
+which grid and which GEMM engine a shape gets; and of what crossq.hip and brn.hip decide on the host (cq_images' lists, cq_dw's bands,
+the column sums' slabs, the element-wise walk).  The shape tests recompute each case's claims from these, and build the engine --
 for the ensemble family the launches per engine -- each profiled GEMM row has to show."""
 
 BX_MAX_JOBS = 32          # gemm_bx.h
@@ -217,6 +218,100 @@ def check_engine_counts(rows, expected):
             e[q["engine"]] = e.get(q["engine"], 0) + q["launches"]
     bad = {k: (seen.get(k), expected.get(k)) for k in set(seen) | set(expected) if seen.get(k) != expected.get(k)}
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------- CrossQ (crossq.hip, brn.hip)
+G_BM, G_BN, G_BK = 128, 128, 32     # gemm.h
+REDUCE_MAX_BLOCKS = 4096            # mlp.h
+BRN_SLAB_ROWS = 64                  # brn.hip
+
+
+def choose_mc(M, tiles, num_cus):
+    """mlp.hip choose_mc: the M-split of a weight-gradient GEMM -> (slab rows, slabs)"""
+    S = max(div_up(num_cus, tiles), 1)
+    Mc = max(div_up(div_up(M, S), G_BK) * G_BK, G_BK)
+    return Mc, max(div_up(M, Mc), 1)
+
+
+def cq_dw_blocks(num_cus, M, k, N):
+    """crossq.hip cq_dw: the workgroups the slab reduction of a band of k rows of W [., N], and of the bias, is counted at"""
+    S = choose_mc(M, div_up(k, G_BM) * div_up(N, G_BN), num_cus)[1]
+    return div_up(k * N, 64 if S >= 128 else 256) + div_up(N, 16)
+
+
+def cq_dw_bands(num_cus, M, Kd, N):
+    """crossq.hip cq_dw: the row bands of W [Kd, N] in which a Dense's weight gradient over M rows is taken -- the band is halved (to a
+    multiple of 64) until cq_dw_blocks fits REDUCE_MAX_BLOCKS -> the band sizes, in order"""
+    kb = Kd
+    while kb > 64 and cq_dw_blocks(num_cus, M, kb, N) > REDUCE_MAX_BLOCKS:
+        kb = div_up(kb // 2, 64) * 64
+    return [min(kb, Kd - k0) for k0 in range(0, Kd, kb)]
+
+
+def brn_rows_per_slab(num_cus, M):
+    """brn.hip brn_rows_per_slab: the rows one workgroup of k_brn_colsum sums -- BRN_SLAB_ROWS until M passes what 4 num_cus slabs hold"""
+    cap = 4 * max(num_cus, 1)
+    return div_up(M, cap) if div_up(M, BRN_SLAB_ROWS) > cap else BRN_SLAB_ROWS
+
+
+def brn_walk(M, ld):
+    """the grid-stride walk of k_brn_apply_* over the float4 groups of [M, ld] (BrnWalk) -> (groups, most steps a thread takes,
+    step_cg, whether a step can carry into the next row: the `cg >= ld4` branch)"""
+    ld4, groups = ld // 4, M * (ld // 4)
+    stride = elem_grid(groups)[0] * 256
+    step_cg = stride % ld4
+    return groups, div_up(groups, stride), step_cg, groups > stride and step_cg > 0
+
+
+def cq_nets(update, p_in, p_hidden, c_in, c_hidden, E, B):
+    """The networks of rlx_crossq_critic_update_f32 ("critic": the policy in eval mode on s', B rows; the E critics' joint training pass
+    of 2 B rows, backward with weight gradients) and of rlx_crossq_policy_update_f32 ("policy": the policy's training pass and the E
+    critics in eval mode for dQ/da, all of B rows), in cq_images' order -> [(rows of the network's pass, net in ens_nets' form)]"""
+    pol, cri = (p_in, tuple(p_hidden)), (c_in, tuple(c_hidden))
+    if update == "critic":
+        return [(B, pol + (False, 1, 0, 0))] + [(2 * B, cri + (True, 1, 1, 0))] * E
+    assert update == "policy"
+    return [(B, pol + (True, 1, 1, 0))] + [(B, cri + (True, 1, 0, 1))] * E
+
+
+def cq_image_list(update, p_in, p_hidden, c_in, c_hidden, E, B):
+    """the list cq_images hands to the image builder, in the form ens_nets returns (image_cut and trunk_images take it): a network is
+    listed only when ITS pass has SPLIT_ROWS rows or more"""
+    return [n for rows, n in cq_nets(update, p_in, p_hidden, c_in, c_hidden, E, B) if rows >= SPLIT_ROWS]
+
+
+def cq_engine_counts(updates, bx, num_cus, p_in, p_hidden, c_in, c_hidden, E, B):
+    """{(kernel, M, N, K): {engine: launches}} of every trunk GEMM of the given updates, from expected_engine_counts per row count of
+    a call's passes -- the image list is one per call, a listed network's launches are counted at its own rows -- with what CrossQ does
+    differently from the ensemble family: the first Dense's input gradient is always the whole GEMM on the exact engine (cq_bwd: BRN 0
+    needs all of it), and a weight gradient is one launch per band of cq_dw_bands, every band on its Dense's engine"""
+    out = {}
+
+    def add(key, eng, n):
+        if n:
+            out.setdefault(key, {})
+            out[key][eng] = out[key].get(eng, 0) + n
+    for update in updates:
+        nets = cq_nets(update, p_in, p_hidden, c_in, c_hidden, E, B)
+        listed = [(rows, n) for rows, n in nets if rows >= SPLIT_ROWS]
+        # per row count the whole image list, the launches of the networks at other row counts struck out; an unlisted network alone
+        groups = [(r, [n if rows == r else n[:3] + (0, 0, 0) for rows, n in listed]) for r in sorted({rows for rows, _ in listed})]
+        groups += [(rows, [n]) for rows, n in nets if rows < SPLIT_ROWS]
+        for rows, g in groups:
+            first = {("k_gemm_dx", rows, n[0], n[1][0]) for n in g}
+            assert not first & {("k_gemm_dx", rows, d, w) for n in g for d, w in zip(n[1], n[1][1:])}, "a hidden Dense of a first one's shape"
+            for (kernel, M, N, K), engines in expected_engine_counts([g], bx, rows, 0).items():       # (A 0: no dx_cols kernel here)
+                if (kernel, M, N, K) in first:
+                    continue                                                                          # counted below
+                for eng, launches in engines.items():
+                    if kernel == "k_gemm_dw":
+                        for k in cq_dw_bands(num_cus, rows, M, N):
+                            add((kernel, k, N, K), eng, launches)
+                    else:
+                        add((kernel, M, N, K), eng, launches)
+            for in_dim, hidden, _, _, grads, dxa in g:
+                add(("k_gemm_dx", rows, in_dim, hidden[0]), 0, grads + dxa)
+    return out
 
 
 def check_engines(rows, expected):

@@ -196,6 +196,64 @@ def test_whole_updates_match_autograd(warmup):
     assert (new["q_count"], new["pi_count"]) == (1, 1) and np.array_equal(new["qs"], mid["qs"]) and not np.array_equal(new["ps"], mid["ps"])
 
 
+# ------------------------------------------------------------------- float32 with the column sums in double (FLOAT32 MODES, dsum)
+def _gap_case(name):
+    """(case, its float64 twin's (new, met)) of tests/test_gpu_crossq.py, whose figures and bars these tests use"""
+    import test_gpu_crossq as m
+    c = m.Case(name)
+    return m, c, c.twin(c.state)[1:3]
+
+
+def test_double_sums_leave_the_float64_twin_bit_identical():
+    m, c, (new, met) = _gap_case("warm")
+    _, new_d, met_d, _ = c.twin(c.state, dsum=True)
+    assert all(np.array_equal(new[k], new_d[k]) for k in tw.STATE_KEYS) and met == met_d
+
+
+def test_double_sum_layer_keeps_a_far_off_column():
+    """a column of mean 50 and deviation 0.5 over 4096 rows: float32 sums lose its variance, double sums under float32 element-wise
+    passes hold y, dX, dg, db to 1e-5 and the advanced statistics to 1e-6 -- the bars brn.hip is held to (tests/test_gpu_brn.py)"""
+    rng = np.random.default_rng(7)
+    M, D, cfg = 4096, 6, tw.BrnCfg()
+    x = (50.0 + 0.5 * rng.standard_normal((M, D))).astype(np.float32)
+    g, b, dY = (1 + 0.2 * rng.standard_normal(D)).astype(np.float32), (0.3 * rng.standard_normal(D)).astype(np.float32), \
+        rng.standard_normal((M, D)).astype(np.float32)
+    m0, v0 = np.full(D, 49.5, np.float32), np.full(D, 0.3, np.float32)
+    f8 = lambda *a: [v.astype(np.float64) for v in a]
+    y, cache, m1, v1 = tw.brn_train(*f8(x, g, b, m0, v0), cfg, True)
+    exp = (y,) + tw.brn_backward(dY.astype(np.float64), cache) + (m1, v1)
+    worst = {}
+    for dsum in (False, True):
+        y, cache, m1, v1 = tw.brn_train(x, g, b, m0, v0, cfg, True, dsum)
+        got = (y,) + tw.brn_backward(dY, cache) + (m1, v1)
+        assert all(a.dtype == np.float32 for a in got)
+        worst[dsum] = [_rel(a, e) for a, e in zip(got, exp)]
+    assert max(worst[True][:4]) <= 1e-5 and max(worst[True][4:]) <= 1e-6, worst[True]
+    assert worst[False][0] > 1e-5 and worst[False][5] > 1e-5, worst[False]       # float sums miss both bars (y, the advanced variance)
+
+
+@pytest.mark.parametrize("name", ["base", "warm"])
+def test_double_sum_float32_is_within_half_of_every_bar(name):
+    m, c, ref = _gap_case(name)
+    gap = m.f32_gap(c, ref=ref)
+    print(f"{name}: double-sum float32 twin against the float64 twin: " + " ".join(f"{k} {v:.1e}" for k, v in gap.items()))
+    bad = {k: (v, m.BARS[k]) for k, v in gap.items() if not v <= 0.5 * m.BARS[k]}
+    assert not bad, bad
+
+
+def test_double_sums_are_what_4096_rows_need():
+    """why the mode exists: at 4096 rows the float32 twin's distance in the critics' first moments is the float column sums', which
+    brn.hip does not take -- with them in double it is at least ten times closer, within half of every one-step bar, and the recorded
+    F32_GAP leaves every bar of rows4096 at its one-step value"""
+    m, c, ref = _gap_case("rows4096")
+    naive, gap = m.f32_gap(c, dsum=False, ref=ref), m.f32_gap(c, ref=ref)
+    print(f"rows4096 qm: float sums {naive['qm']:.2e}, double sums {gap['qm']:.2e}")
+    assert naive["qm"] >= 10 * gap["qm"] and naive["qm"] > m.BARS["qm"]
+    assert all(v <= 0.5 * m.BARS[k] for k, v in gap.items()), gap
+    assert all(abs(v - m.F32_GAP["rows4096"][k]) <= 0.05 * m.BARS[k] for k, v in gap.items()), gap       # what is recorded is what this measures
+    assert all(max(b, 2 * m.F32_GAP[n].get(k, 0.0)) == b for n in m.F32_GAP for k, b in m.BARS.items())
+
+
 def test_key_chain_is_the_oracles():
     from oracle import prng
     key = prng.prng_key(5)

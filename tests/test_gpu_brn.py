@@ -12,12 +12,25 @@ lower / upper edge -- by choosing the running statistics from the batch's (cross
 asserts on the CPU that every unclipped factor is at least 1e-3 relative away from its edge and every batch variance at least 1e-6.
 Column min(3, D - 1) has mean 50 and std 0.5: its variance is lost in float sums, the double accumulators must hold the bar there.
 
+LARGE holds the shapes that reach the two branches no smaller shape does (nc = num_cus of the device, taken at run time; reaches()
+restates the two conditions and test_crossq_cases.py asserts them at nc 256):
+  (256 nc + 65, 7, 8, 1)      more rows than 4 nc slabs of 64 hold: brn_rows_per_slab's second branch (65 rows a slab), the last slab
+                              short, ragged width
+  (256 nc + 65, 64, 64, 2)    the same over two networks; at nc 256 also 1 049 616 float4 groups, just past elem_grid's cap of
+                              4096 x 256 threads: some threads take a second step of BrnWalk::next, with step_cg 0
+  (45000, 190, 192, 1)        2.16 M groups, two to three steps a thread, ld4 48 so that a step carries into the next row (the
+                              `cg >= ld4` branch); the ragged last group has D 190 in ld 192
+  (2100, 2047, 2048, 1)       the widest layer, ragged, past the cap
+
 Bars: y, dX, dg, db 1e-5 relative L2 per array; the advanced statistics 1e-6 relative L2."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import crossq_twin as tw
+import net_paths as npth
 from rlx_amd.hip import lib as L
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +39,8 @@ BAR, STAT_BAR = 1e-5, 1e-6
 MARGIN, VAR_FLOOR = 1e-3, 1e-6
 SHAPES = [(2, 1, 4, 1), (2, 64, 64, 1), (3, 7, 8, 1), (134, 7, 8, 1), (134, 64, 64, 1), (134, 192, 192, 1), (16, 2048, 2048, 1),
           (L.BRN_SLAB_ROWS + 1, 64, 64, 1), (8192, 64, 64, 1), (134, 64, 64, 3)]
+# appended to SHAPES (kind indices len(SHAPES) + position); "256nc+65" rows are resolved on the device: rows_of()
+LARGE = [("256nc+65", 7, 8, 1), ("256nc+65", 64, 64, 2), (45000, 190, 192, 1), (2100, 2047, 2048, 1)]
 KINDS = [(1.3, 0.7), (0.2, 0.5), (4.0, -0.5), (1.2, -7.0), (0.8, 6.5)]        # (r, d) wanted: inside, r low / high, d low / high
 MODES = ("eval", "cold", "warm")
 # (M, D, ld, E) -> the first seed under which the builder's conditions hold (0 where not listed): python tests/test_gpu_brn.py
@@ -40,10 +55,28 @@ def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
 
 
-def make_case(M, D, ld, E, constant_column=None, seed=None):
+def rows_of(M, num_cus):
+    """a shape's row count: itself, or LARGE's "256nc+65" """
+    return 256 * num_cus + 65 if M == "256nc+65" else M
+
+
+def reaches(M, ld, num_cus):
+    """what a LARGE shape is there for -> (BrnWalk::next runs: more float4 groups than elem_grid's 4096 x 256 threads; slabs of more
+    than BRN_SLAB_ROWS rows: brn_rows_per_slab's second branch)"""
+    return M * ld // 4 > 4096 * 256, npth.brn_rows_per_slab(num_cus, M) != L.BRN_SLAB_ROWS
+
+
+@functools.lru_cache(maxsize=2)
+def large_case(M, D, ld, E, si):
+    """make_case of a LARGE shape, built once for the tests that read it (none writes it)"""
+    return make_case(M, D, ld, E, si=si)
+
+
+def make_case(M, D, ld, E, constant_column=None, seed=None, si=None):
     """-> dict of float32 arrays: x, dY [E, M, ld] (padding 0), gb, stats [E, 2 D]"""
     seed = SEEDS.get((M, D, ld, E), 0) if seed is None else seed
-    si = [s[:3] for s in SHAPES].index((M, D, ld)) if (M, D, ld) in [s[:3] for s in SHAPES] else 0
+    if si is None:
+        si = [s[:3] for s in SHAPES].index((M, D, ld)) if (M, D, ld) in [s[:3] for s in SHAPES] else 0
     rng = np.random.default_rng([seed, M, D, ld, E])
     cfg = tw.BrnCfg()
     x = rng.standard_normal((E, M, D)) * rng.uniform(0.5, 2.0, (E, 1, D)) + rng.uniform(-2, 2, (E, 1, D))
@@ -120,9 +153,16 @@ def device(ctx, dev, c, mode, relu, fill=7.0):
 
 @pytest.mark.parametrize("relu", [False, True])
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("M,D,ld,E", SHAPES)
+@pytest.mark.parametrize("M,D,ld,E", SHAPES + LARGE)
 def test_layer_matches_the_twin(ctx, dev, M, D, ld, E, mode, relu):
-    c = make_case(M, D, ld, E)
+    if (M, D, ld, E) in LARGE:
+        si, nc = len(SHAPES) + LARGE.index((M, D, ld, E)), torch.cuda.get_device_properties(0).multi_processor_count
+        M = rows_of(M, nc)
+        walk, slab = reaches(M, ld, nc)
+        assert walk if si >= len(SHAPES) + 2 else slab, (M, ld, nc)            # (the second shape walks too at nc 256: 256 nc + 65 > 65536)
+        c = large_case(M, D, ld, E, si)
+    else:
+        c = make_case(M, D, ld, E)
     check_margins(c)
     exp = twin(c, mode, relu)
     got = device(ctx, dev, c, mode, relu)
@@ -186,6 +226,24 @@ def test_eval_backward_without_parameter_gradients(ctx, dev, relu):
     assert max(_rel(got[e, :, :7], exp["dX"][e]) for e in range(3)) <= BAR
 
 
+@pytest.mark.parametrize("relu", [False, True])
+def test_eval_backward_without_parameter_gradients_past_the_grid_cap(ctx, dev, relu):
+    """k_brn_apply_bwd_eval has a walk of its own: (45000, 190, 192), two to three steps a thread, steps that carry into the next row"""
+    M, D, ld, E = LARGE[2]
+    groups, steps, step_cg, carries = npth.brn_walk(M, ld)
+    assert reaches(M, ld, 256)[0] and steps >= 2 and carries
+    c = large_case(M, D, ld, E, len(SHAPES) + 2)
+    exp = twin(c, "eval", relu)
+    x, gb, stats, d = _t(c["x"], dev), _t(c["gb"], dev), _t(c["stats"], dev), _t(c["dY"], dev)
+    ctx.brn(x, D, gb, stats, L.brn_config(), L.BRN_EVAL_BWD, d, relu_mask=relu)
+    got = d.cpu().numpy()
+    assert not got[:, :, D:].any()
+    assert _rel(got[0, :, :D], exp["dX"][0]) <= BAR
+    d2 = _t(c["dY"], dev)
+    ctx.brn(x, D, gb, stats, L.brn_config(), L.BRN_EVAL_BWD, d2, relu_mask=relu)
+    assert torch.equal(d, d2)
+
+
 REFUSALS = [("m_1", -1, "M must be at least 2"), ("d_0", -1, "D must be positive"), ("ld_below_d", -1, "ld must be"),
             ("ld_odd", -1, "ld must be"), ("e_0", -1, "E must be at least 1"), ("e_17", -4, "E at most 16"),
             ("momentum_1", -1, "momentum"), ("momentum_neg", -1, "momentum"), ("eps_0", -1, "eps"), ("r_max_low", -1, "r_max"),
@@ -246,4 +304,5 @@ def _usable(*a, **k):
 
 if __name__ == "__main__":      # SEEDS: the builder's conditions for every case, on a CPU
     cases = [(s, {}) for s in SHAPES] + [((67, 7, 8, 1), {"constant_column": 5})]
+    cases += [((rows_of(s[0], 256),) + s[1:], {"si": len(SHAPES) + i}) for i, s in enumerate(LARGE)]        # (at num_cus 256)
     print("SEEDS =", {s: seed for s, seed in ((s, next(i for i in range(1000) if _usable(*s, seed=i, **k))) for s, k in cases) if seed})
