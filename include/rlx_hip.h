@@ -206,6 +206,13 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   "ro_exit" or stamps set, and with 0, the T launches of k_rollout_step run unchanged.  The same operations in the same order:
  *   bit-identical results (tests/test_gpu_rollout_persistent.py).  "rollout_chunk_steps" (32 default; 1 .. 64, anything else
  *   is RLX_EINVAL): acting steps per launch of k_rollout_steps; the results do not depend on it.
+ * Round 13: "tail32_lean" (1 default; 0 or 1, anything else is RLX_EINVAL): with "tail32_waves" = 8, 1 runs k_tail32_bx_lean in
+ *   every launch of the 32-row tail (single, twin, valid-rows): the head weights sit in LDS with 16 bytes of padding per eight
+ *   rows (the head's reads are conflict-free instead of 8-way), the metric fold and the bias / logstd column sums run on waves
+ *   4 and 5 beside the head's weight-gradient partials (the metric sums have LDS slots of their own: one barrier fewer), and those
+ *   partials cross row groups as 16-byte LDS stores and loads; 65920 instead of 65600 bytes of LDS.  Every sum keeps its operands
+ *   and their order: bit-identical results (tests/test_gpu_tail32_lean.py); 0, and "tail32_waves" = 4, run the earlier kernels
+ *   unchanged.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,

@@ -168,6 +168,12 @@ struct rlx_ctx {
   int tail32_waves = 8;                   // k_tail32_bx: waves per 32-row tile, 4 or 8 (same LDS: two or four waves per SIMD; bit-identical results).
                                           // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 67.14 vs 68.34 ms per iteration at 32768-row
                                           // minibatches (block-to-block sd 0.19 / 0.24), 112.41 vs 115.96 at 4096 rows
+  int tail32_lean = 1;                    // k_tail32_bx on eight waves: 1 runs k_tail32_bx_lean (head weights in LDS with 16 bytes of padding per eight
+                                          // rows: conflict-free head reads; the serial sections on waves 4 / 5; 16-byte head-gradient partials); 0 the
+                                          // earlier kernel.  No effect with tail32_waves = 4.  Every sum keeps its operands and order: bit-identical.
+                                          // MEASURED (in-process A/B, 8 blocks of 5 iterations each): 60.51 vs 61.34 ms per iteration at 32768-row
+                                          // minibatches (block-to-block sd 0.07 / 0.07); 102.80 vs 105.05 at 4096 rows in a drifting process (sd 0.80 /
+                                          // 0.71: bar not cleared, no gain claimed there)
   int ln_row_once = 1;                    // k_dx_l1bwd<BX> / k_l12fwd: 1 every wave computes a row's LayerNorm mean and 1 / std ONCE (lanes 0-31, one row
                                           // each: ln_row_stats in l1fused.hip) and the per-row loops load them; 0 the earlier form, every lane
                                           // recomputes both for each of its 16 rows at every use.  Same operations in the same order: bit-identical.

@@ -251,6 +251,11 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
     ctx->tail32_waves = value;
     return RLX_OK;
   }
+  if (std::string(name) == "tail32_lean") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: tail32_lean is 0 or 1");
+    ctx->tail32_lean = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "ln_row_once") {
     RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: ln_row_once is 0 or 1");
     ctx->ln_row_once = value;

@@ -1024,13 +1024,15 @@ __global__ __launch_bounds__(256, 2) void k_tail_bx(TailNet p, TailNet c, const 
 #define RLX_T32_STAMPS 0
 #endif
 constexpr int T32_ROWS = 32;
-template <bool POLICY, int ACT, int N2, int NWV>
+constexpr int T32_LEAN_LDS = (TL_K3 / 8) * 16 + 64;        // LEAN: the head weights' padding, the metric sums' own slots
+template <bool POLICY, int ACT, int N2, int NWV, int LEAN = 0>
 __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__ smem, const float* __restrict__ mb_a,
                                             const float* __restrict__ aux, const double* __restrict__ stats,
                                             float* __restrict__ metrics, int64_t M, float inv_mb, float clip, float ent_coef,
                                             float critic_coef, const int32_t* __restrict__ valid_rows, float gs,
                                             unsigned long long* __restrict__ stamps) {
   static_assert(NWV == 4 || NWV == 8, "tail32: four or eight waves per tile");
+  static_assert(!LEAN || NWV == 8, "tail32: the lean form is an eight-wave form");
   constexpr int K = TL_K3, AP = 8, NP = 2, RP = T32_ROWS / NP, KQ = K / 8;     // head: 8 threads per row, 16 columns each
   constexpr int NT = 64 * NWV, TPR = NT / T32_ROWS;                            // threads; threads per row of the plane split and of dZ3
   constexpr int HROW = 2 * N2 + 16, HPL = T32_ROWS * HROW;                     // H2 planes: padded rows
@@ -1039,11 +1041,16 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
   char* H2P = smem;
   float* T = reinterpret_cast<float*>(smem + 2 * HPL);
   char* D3P = smem + 2 * HPL;
-  float* Ws = reinterpret_cast<float*>(smem + 2 * HPL + TREG);    // [K][8]
-  float* Ds = Ws + K * AP;                                        // [32][8]
+  // LEAN: the head weights with 16 bytes of padding per eight rows.  The eight threads of a row read rows KQ = 16 apart: 512 bytes,
+  // the same four banks in every 16-lane group of a ds_read_b128 (8-way); 512 + 32 bytes apart they fall on eight different 16-byte
+  // slots of the 256-byte bank row.  dZ3's half-wave broadcasts stay broadcasts.
+  auto wso = [](int k) { return k * AP + (LEAN ? (k >> 3) * 4 : 0); };
+  float* Ws = reinterpret_cast<float*>(smem + 2 * HPL + TREG);    // [K][8] (+ 4 floats per 8 rows: wso)
+  float* Ds = Ws + K * AP + (LEAN ? (K / 8) * 4 : 0);             // [32][8]
   float* DLs = Ds + T32_ROWS * AP;                                // [32][8]
   float* red = DLs + T32_ROWS * AP;                               // [16] metric sums, then [NP][K][8]
   float* BL = red + NP * K * AP;                                  // [2][8] head bias, logstd (NWV == 8): the 16 floats behind the partial sums
+  float* MS = LEAN ? BL + 2 * AP : red;                       // [4][4] metric sums of the head waves: slots of their own, or the front of red
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31, lh = lane >> 5;
   const int64_t m0 = (int64_t)blockIdx.x * T32_ROWS;
   const int A = n.A, PS = n.PS;
@@ -1132,8 +1139,9 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
       for (int u = 0; u < K * AP / 256; ++u) wv[u] = n.Wh[((i0 >> 3) + 32 * u) * A + ac];
       if (i0 < AP) bl = n.bh[ac];
       else if (POLICY && i0 < 2 * AP) bl = n.logstd[ac];
+      // (the earlier form's index stands verbatim: through wso() hipcc's code for the existing entry changed)
 #pragma unroll
-      for (int u = 0; u < K * AP / 256; ++u) Ws[i0 + 256 * u] = a < A ? wv[u] : 0.f;
+      for (int u = 0; u < K * AP / 256; ++u) Ws[LEAN ? wso((i0 >> 3) + 32 * u) + a : i0 + 256 * u] = a < A ? wv[u] : 0.f;
       if (i0 < 2 * AP) BL[i0] = a < A ? bl : 0.f;
     }
   }
@@ -1206,7 +1214,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
   for (int j = 0; j < KQ / 4; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float* wr = Ws + (q8 * KQ + 4 * j + e) * AP;
+      const float* wr = Ws + wso(q8 * KQ + 4 * j + e);
       const hl_f4 w0 = *reinterpret_cast<const hl_f4*>(wr), w1 = *reinterpret_cast<const hl_f4*>(wr + 4);
       const float hv = h[j][e];
 #pragma unroll
@@ -1271,11 +1279,34 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
   m0s = wave_sum(m0s);
   m1s = wave_sum(m1s);
   m2s = wave_sum(m2s);
-  if ((t & 63) == 0) { red[(t >> 6) * 4 + 0] = m0s; red[(t >> 6) * 4 + 1] = m1s; red[(t >> 6) * 4 + 2] = m2s; }
+  if ((t & 63) == 0) { MS[(t >> 6) * 4 + 0] = m0s; MS[(t >> 6) * 4 + 1] = m1s; MS[(t >> 6) * 4 + 2] = m2s; }
   }   // hw
   T32_STAMP(6)
   __syncthreads();
   float* pw = n.partials + (int64_t)blockIdx.x * PS;
+  if (LEAN) {
+    // the serial sections on waves 4 and 5, beside the head waves' weight-gradient partials: the metric sums have slots of their own,
+    // so no second barrier has to keep the partials out of them
+    if (t == 320) {
+      float* pm = pw + K * A + 2 * A;
+      pm[0] = (MS[0] + MS[4]) + (MS[8] + MS[12]);
+      pm[1] = (MS[1] + MS[5]) + (MS[9] + MS[13]);
+      pm[2] = (MS[2] + MS[6]) + (MS[10] + MS[14]);
+    }
+    // (wave 4, lanes 0-7: a bias column each; lanes 8-15: a logstd column each -- every sum its 32 rows in order, as below, but the
+    //  two sums of a column side by side: the whole section is one dependent chain of 32 additions, and it has to end before the
+    //  head waves' partials do)
+    if (t >= 256 && t < 256 + 2 * AP && (t & 7) < A) {
+      const int a = t & 7;
+      const bool lsd = (t & 8) != 0;
+      const float* src = lsd ? DLs : Ds;
+      float sm = 0.f;
+      if (POLICY || !lsd) {
+        for (int rr = 0; rr < T32_ROWS; ++rr) sm += src[rr * AP + a];
+      }
+      pw[K * A + (lsd ? A : 0) + a] = sm;
+    }
+  } else {
   if (t == 0) {
     float* pm = pw + K * A + 2 * A;
     pm[0] = (red[0] + red[4]) + (red[8] + red[12]);
@@ -1283,6 +1314,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
     pm[2] = (red[2] + red[6]) + (red[10] + red[14]);
   }
   __syncthreads();
+  }
   T32_STAMP(7)
   {  // head weight gradient: thread (k, row group): RP rows in order, then the NP groups in order
     const int k = t % K, part = t / K;
@@ -1296,17 +1328,32 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
 #pragma unroll
       for (int a = 0; a < 4; ++a) { dw[a] = fmaf(hv, d0[a], dw[a]); dw[4 + a] = fmaf(hv, d1[a], dw[4 + a]); }
     }
+    if (LEAN) {
+      // only the second row group's sums cross: as two 16-byte stores into two [K][4] halves (lanes 16 bytes apart: conflict-free
+      // as stores and as the ds_read_b128 below), not eight 4-byte ones at a 32-byte lane stride (8-way)
+      if (part == 1) {
+        *reinterpret_cast<hl_f4*>(red + k * 4) = hl_f4{dw[0], dw[1], dw[2], dw[3]};
+        *reinterpret_cast<hl_f4*>(red + (K + k) * 4) = hl_f4{dw[4], dw[5], dw[6], dw[7]};
+      }
+    } else {
 #pragma unroll
     for (int a = 0; a < AP; ++a) red[(part * K + k) * AP + a] = dw[a];
+    }
     }   // hw
     __syncthreads();
     if (part == 0) {
+      if (LEAN) {
+        const hl_f4 r0 = *reinterpret_cast<const hl_f4*>(red + k * 4), r1 = *reinterpret_cast<const hl_f4*>(red + (K + k) * 4);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) { dw[a] += r0[a]; dw[4 + a] += r1[a]; }
+      } else {
 #pragma unroll
       for (int a = 0; a < AP; ++a) dw[a] += red[(K + k) * AP + a];
+      }
       for (int a = 0; a < A; ++a) pw[k * A + a] = dw[a];
     }
   }
-  if (t < A) {
+  if (!LEAN && t < A) {
     float sb = 0.f, sl = 0.f;
     for (int rr = 0; rr < T32_ROWS; ++rr) {
       sb += Ds[rr * AP + t];
@@ -1344,7 +1391,7 @@ __device__ __forceinline__ void tail32_body(const TailNet& n, char* __restrict__
       hl_f4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float* wr = Ws + (zc + 4 * j + e) * AP;
+        const float* wr = Ws + wso(zc + 4 * j + e);
         const hl_f4 w0 = *reinterpret_cast<const hl_f4*>(wr), w1 = *reinterpret_cast<const hl_f4*>(wr + 4);
         float sacc = 0.f;
 #pragma unroll
@@ -1436,6 +1483,29 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void k_tail32_bx(TailNet p, Tail
     tail32_body<false, ACT, N2, NWV>(c, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs, stamps);
 }
 
+// The eight-wave tail, lean form (option tail32_lean = 1, the default).  The same tile, the same sums with the same operands in the
+// same order -- bit-identical results -- with what the result does not need taken off the head waves' path:
+//   - the head weights sit in LDS with 16 bytes of padding per eight rows, so the head's reads (eight threads of a row, rows 16
+//     apart) are conflict-free instead of 8-way;
+//   - waves 4 and 5, idle from their staging to dZ3, run the serial sections (metric fold, bias / logstd column sums) beside the
+//     head's weight-gradient partials, and the metric sums have LDS slots of their own: one barrier fewer;
+//   - the head's weight-gradient partials cross row groups as 16-byte LDS stores and loads.
+// Phase stamps: profiles/r13_tail32_phases.txt (which also has the part tried and dropped: act'(H2) built once by waves 4-7 as an
+// fp32 image in the planes' place -- the dZ2 epilogue got shorter by what the head, beside the image's stores, got longer).
+template <int ACT, int N2>
+__global__ __launch_bounds__(512, 4) void k_tail32_bx_lean(TailNet p, TailNet c, const float* __restrict__ mb_a,
+                                                           const float* __restrict__ aux, const double* __restrict__ stats,
+                                                           float* __restrict__ metrics, int64_t M, float inv_mb, float clip,
+                                                           float ent_coef, float critic_coef, const int32_t* __restrict__ valid_rows,
+                                                           float gs, int both, int which, unsigned long long* __restrict__ stamps) {
+  extern __shared__ __attribute__((aligned(16))) char tl32_smem[];
+  const bool critic = both ? blockIdx.y != 0 : which != 0;
+  if (!critic)
+    tail32_body<true, ACT, N2, 8, 1>(p, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs, stamps);
+  else
+    tail32_body<false, ACT, N2, 8, 1>(c, tl32_smem, mb_a, aux, stats, metrics, M, inv_mb, clip, ent_coef, critic_coef, valid_rows, gs, stamps);
+}
+
 // rows per workgroup (= per block of head partials) of the tail form in use
 // Which tail form a minibatch of mb rows takes.  ppo_tail = -1 (default): the 32-row form up to 8192 rows (4096 rows: 99.5 vs 107.0 us
 // per update -- twice the workgroups when there are fewer 64-row tiles than CUs) and above 16384 rows, i.e. in the two-chain
@@ -1472,20 +1542,23 @@ static int launch_tail(rlx_ctx* ctx, const TailNet* p, const TailNet* c, const M
     constexpr int TREG = (T32_ROWS * TL_TS * 4 > 2 * DPL) ? T32_ROWS * TL_TS * 4 : 2 * DPL;
     const size_t lds32 = 2 * HPL + TREG + ((size_t)TL_K3 * 8 + 2 * T32_ROWS * 8 + 16 + 2 * TL_K3 * 8) * sizeof(float);
     unsigned long long* stamps = RLX_T32_STAMPS ? (unsigned long long*)ctx->dbg_stamps : nullptr;
-#define RLX_TAIL32_LAUNCH(NWV)                                                                                       \
+#define RLX_TAIL32_LAUNCH(KERNEL, NWV, LDS)                                                                          \
   {                                                                                                                  \
     static AttrOnce attr32;                                                                                          \
     if (!attr32.done()) {                                                                                            \
-      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tail32_bx<RLX_ACT_ELU, 256, NWV>),             \
+      RLX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),                                         \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                      \
       attr32.mark();                                                                                                 \
     }                                                                                                                \
-    RLX_PLAUNCH((k_tail32_bx<RLX_ACT_ELU, 256, NWV>), dim3((unsigned)(mb / T32_ROWS), both ? 2 : 1), dim3(64 * NWV), lds32, st, tp, \
+    RLX_PLAUNCH((KERNEL), dim3((unsigned)(mb / T32_ROWS), both ? 2 : 1), dim3(64 * NWV), LDS, st, tp,                \
                 tc, s.mb_a, s.aux, s.stats, metrics, mb, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, s.valid_rows, gs,   \
                 both, which, stamps);                                                                                \
   }
-    if (ctx->tail32_waves == 8) RLX_TAIL32_LAUNCH(8)     // (default) eight waves per 32-row tile: same LDS, four waves per SIMD, bit-identical results
-    else RLX_TAIL32_LAUNCH(4)
+    // (default) eight waves per 32-row tile: same LDS, four waves per SIMD, bit-identical results; its lean form (default) with the
+    // head weights padded and the metric sums in slots of their own: 65920 bytes, still two workgroups per CU
+    if (ctx->tail32_waves == 8 && ctx->tail32_lean) RLX_TAIL32_LAUNCH((k_tail32_bx_lean<RLX_ACT_ELU, 256>), 8, lds32 + T32_LEAN_LDS)
+    else if (ctx->tail32_waves == 8) RLX_TAIL32_LAUNCH((k_tail32_bx<RLX_ACT_ELU, 256, 8>), 8, lds32)
+    else RLX_TAIL32_LAUNCH((k_tail32_bx<RLX_ACT_ELU, 256, 4>), 4, lds32)
 #undef RLX_TAIL32_LAUNCH
     RLX_LAUNCH_CHECK();
     return RLX_OK;

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Tuning aid: phase stamps (clock64 of thread 0, workgroup 0) of k_tail32_bx at the bench minibatch, for four and eight waves
-per tile (option tail32_waves).  Needs a library built with the stamps compiled in:
+per tile (option tail32_waves) and, on eight waves, the earlier and the lean form (option tail32_lean = 0 / 1) alternated twice in
+one process -- the stamps sit at the same source positions in both ("metric sums" is one barrier in the lean form; its serial
+sections and its act'(H2) image run on waves 4-7, which thread 0 does not stamp: read the whole tile).
+Needs a library built with the stamps compiled in:
     RLX_BUILD_TAG=t32s RLX_EXTRA_DEFINES=-DRLX_T32_STAMPS=1 python rl-x_amd/build.py
     RLX_HIP_LIBRARY=rl-x_amd/lib/librlxhip_t32s.so python tools/tail32_phases.py [minibatch rows]
 The per-phase entry runs the two networks' chains on two streams, as the update does; the stamps are those of the launch that
@@ -27,8 +30,9 @@ ctx.set_option("ppo_tail", 2)
 names = ["H2 request + split + plane stores", "barrier", "phase A K loop", "act + H3 tile stores", "barrier",
          "head + loss + seeds", "metric sums (two barriers)", "head dW partials + barrier + sums", "barrier", "dZ3",
          "barrier", "phase C K loop", "dZ2 epilogue"]
-for waves in (4, 8):
+for waves, lean in ((4, 0), (8, 0), (8, 1), (8, 0), (8, 1)):
     ctx.set_option("tail32_waves", waves)
+    ctx.set_option("tail32_lean", lean)
     for _ in range(3):
         ctx.ppo_minibatch_fwd_bwd(pd, P, pg, cd, C, cg, met, states, actions, logp, ret, adv, idx, hp)
     runs = []
@@ -44,7 +48,7 @@ for waves in (4, 8):
         raise SystemExit("no stamps: build with -DRLX_T32_STAMPS=1 and select the library with RLX_HIP_LIBRARY")
     d = [int(s[i + 1] - s[i]) for i in range(13)]
     ticks, wall_us = int(s[13] - s[0]), (int(s[15]) - int(s[14])) / 100.0
-    print(f"k_tail32_bx, {waves} waves per tile, mb {mb}: workgroup 0's tile = {ticks} clock64 ticks in {wall_us:.2f} us of wall_clock64"
+    print(f"k_tail32_bx, {waves} waves per tile, tail32_lean = {lean}, mb {mb}: workgroup 0's tile = {ticks} clock64 ticks in {wall_us:.2f} us of wall_clock64"
           f" -> {ticks / max(wall_us, 1e-9) / 1e3:.2f} GHz   (totals of 5 runs: {' '.join(str(int(r[13] - r[0])) for r in runs)})")
     for n, v in zip(names, d):
         print(f"    {n:40s} {v:7d}  {100.0 * v / ticks:5.1f} %")
