@@ -1213,6 +1213,81 @@ int rlx_espo_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, flo
                         const float* advantages, int64_t B, const int32_t* idx, int mb, int max_epochs, int64_t* opt_count_io, float lr,
                         const rlx_espo_hparams* hp, float* metrics_out, int32_t* epochs_run_out, void* stream);
 
+/* =================================== FastMPO =============================================
+ * Massively parallel MPO (rl_x/algorithms/fastmpo/flax_full_jit): one or two categorical critics whose target is the floor/ceil
+ * projection (FastSAC's, c51_body.h) of the MEAN over K target-policy samples of the target critics' pmfs, MPO's E-step over the
+ * min or mean of the critics and its M-step and dual step (mpo.hip's kernels), optax's clip_by_global_norm + adamw for policy,
+ * critic and duals, Polyak targets for policy and critic.
+ * Networks (policy.py:42-124, critic.py:25-89), kind 0 "fastsac": Dense -> LayerNorm(1e-6) -> SiLU x3; 1 "fasttd3": Dense -> ReLU
+ * x3; 2 "mpo": Dense -> LayerNorm(1e-6) -> tanh, then Dense -> ELU x2.  Widths: multiples of 64, at most 1024 without a LayerNorm,
+ * 768 behind (LayerNorm, SiLU), 512 behind (LayerNorm, tanh) (the row-norm kernels hold a row in one wave).
+ * FLAT LAYOUTS: per hidden layer W[in, out] row-major, b[out], then ln_scale[out], ln_bias[out] where the layer has a LayerNorm;
+ * then the head W[in, out], b[out].  Policy head [H3, 2A] = [mean | std pre-activation] columns (policy.py:61-64: two Dense
+ * layers side by side); std = min_scale + softplus(raw) init_scale / softplus(0).  Critic input [critic obs | action]; with
+ * dual_critic the second critic's parameters follow the first's.  DUALS as MPO's: log_eta | log_alpha_mean[A] |
+ * log_alpha_stddev[A] | log_penalty_temperature.
+ * act_dim 1..64, nr_atoms 2..128, action_sampling_number 1..64.                                                               */
+typedef struct rlx_fastmpo_desc {
+  int32_t policy_obs_dim, critic_obs_dim, act_dim, nr_atoms;
+  int32_t dual_critic;                 /* two critics (critic.py:92-108) */
+  int32_t policy_kind, critic_kind;    /* 0 fastsac, 1 fasttd3, 2 mpo */
+  int32_t policy_hidden[3], critic_hidden[3];
+} rlx_fastmpo_desc;
+/* net 0: policy, 1: ONE critic, 2: duals; -1 on a bad descriptor */
+int64_t rlx_fastmpo_param_count(const rlx_fastmpo_desc*, int net);
+
+typedef struct rlx_fastmpo_hparams { /* fastmpo/flax_full_jit/default_config.py, what the update reads */
+  float gamma, v_min, v_max;
+  float max_grad_norm;               /* optax.clip_by_global_norm of all three optimisers (fastmpo.py:158, :168, :177); <= 0: none */
+  float policy_weight_decay, critic_weight_decay, dual_weight_decay;   /* optax.adamw */
+  float adam_b1, adam_b2, adam_eps;  /* adam_beta1, adam_beta2; optax's eps 1e-8 */
+  float critic_tau, policy_tau;      /* optax.incremental_update (fastmpo.py:593, :622) */
+  float epsilon_non_parametric, epsilon_parametric_mu, epsilon_parametric_sigma, epsilon_penalty;
+  float policy_init_scale, policy_min_scale;
+  float float_epsilon, min_log_temperature, min_log_alpha;
+  int32_t action_sampling_number;    /* K: 1..64 */
+  int32_t action_clipping;
+  int32_t action_rescaling;          /* 0 none, 1 normal, 2 fastsac (policy.py:127-138) */
+  int32_t clipped_double_q_learning; /* needs dual_critic */
+  int32_t nr_critic_updates_per_policy_update, nr_policy_updates_per_step;   /* G, P */
+} rlx_fastmpo_hparams;
+
+/* Acting (fastmpo.py:287-290, evaluation :678-680) on the normalised obs [N, O]: action = mean + std eps [N, A] (what the ring
+ * stores; deterministic: the mean, key untouched) from the GIVEN policy parameters -- online or target, as
+ * collect_data_with_online_policy says; processed_action = get_processed_action(action) (policy.py:127-138): clip to [-1, 1]
+ * (action_clipping), then action_rescaling 1: low + 0.5 (a + 1)(high - low), 2: a * action_scale (passed in `low`).  key, subkey =
+ * split(key); rlx_dbg_set_sac_noise(eps_next, .) injects the N(0, 1) draws [N, A].                                             */
+int rlx_fastmpo_act_f32(rlx_ctx*, const rlx_fastmpo_desc*, const float* pparams, const float* obs, int O, const int32_t* pidx,
+                        uint32_t key_io[2], int scheme, float* action, float* processed_action, const float* low, const float* high,
+                        int64_t N, int deterministic, const rlx_fastmpo_hparams* hp, void* stream);
+/* The optimisation of ONE learning iteration (fastmpo.py:572-627): P rounds; round p runs G critic steps on the batches u = p G ..
+ * p G + G - 1 of states, next_states [P G, B, O] (normalised), actions [P G, B, A], rewards, dones, truncations,
+ * effective_n_steps [P G, B] -- critic_loss_fn (:314-379), clip + adamw at critic_lr[u], and the critic's Polyak update inside the
+ * same Adam launch (:586-593) -- then one policy and dual step on the round's last batch against the updated target critic
+ * (policy_and_dual_loss_fn :381-482, :603-620) at policy_lr[p] / dual_lr[p], and the policy's Polyak update (:622).  The target
+ * policy is read on s' in the critic steps and on [s; s'] in the policy step.  qparams / qm / qv / target_qparams: the critics
+ * back to back (one optimiser over both).  critic_lr [P G], policy_lr [P], dual_lr [P]: HOST arrays.  opt_count_io: HOST
+ * int64[3] = optimiser steps so far of {critic, policy, duals}, advanced by P G, P, P when the call returns RLX_OK (untouched on an
+ * error).
+ * Noise: per-row keys as the reference draws them: row_keys = split(noise_key, P G B 3) (:513-514); the critic step u draws row
+ * b's normal of shape (K, A) from row_keys[(u B + b) 3], the policy step its (K, 2, A) from row_keys[(u B + b) 3 + 2] (:582-584;
+ * policy_and_dual_loss_fn takes two keys and draws from the second only).  rlx_dbg_set_sac_noise(eps_next, eps_cur) injects the
+ * draws instead: eps_next [P G, K, B, A] for the critic steps, eps_cur [P, K, 2B, A] for the policy steps.
+ * metrics_out: DEVICE float[28], the last critic step's {q_loss, q_mean, q_max, q_min, critic_learning_rate, critic_grad_norm}
+ * then the last policy step's {actor_loss, loss_pg_mean, loss_pg_std, loss_kl_mean, loss_kl_std, dual_loss, loss_alpha_mean,
+ * loss_alpha_std, loss_eta, eta, penalty_temperature, alpha_mean, alpha_std, mean_kl_mean, mean_kl_std, improvement_q_mean,
+ * std_min_mean, std_max_mean, policy_learning_rate, dual_variables_learning_rate, policy_grad_norm, dual_variables_grad_norm}
+ * (:372-377, :595-596, :461-480, :624-627).  No host synchronisation inside the call.
+ * RLX_EINVAL / RLX_EUNSUP outside the envelope: clipped_double_q_learning without dual_critic, K or act_dim outside 1..64, nr_atoms
+ * outside 2..128, a width that is no multiple of 64 or past its kind's limit, a kind outside 0..2, P or G < 1.                 */
+int rlx_fastmpo_update_f32(rlx_ctx*, const rlx_fastmpo_desc*, float* pparams, float* pm, float* pv, float* target_pparams,
+                           float* qparams, float* qm, float* qv, float* target_qparams, float* duals, float* dm, float* dv,
+                           const float* states, const float* next_states, int O, const int32_t* pidx, const int32_t* cidx,
+                           const float* actions, const float* rewards, const float* dones, const float* truncations,
+                           const float* effective_n_steps, int64_t B, const uint32_t noise_key[2], int scheme, int64_t* opt_count_io,
+                           const float* critic_lr, const float* policy_lr, const float* dual_lr, const rlx_fastmpo_hparams* hp,
+                           float* metrics_out, void* stream);
+
 /* =================================== PPO + LSTM =======================================
  * Recurrent policy (rl_x/algorithms/ppo_lstm/flax_full_jit/policy.py:32-142, "concat" and "film" decoders):
  *   lstm_obs_encode / obs_encode: Dense(E)+LN+ELU on obs; OptimizedLSTMCell(H); LN+ELU on h;

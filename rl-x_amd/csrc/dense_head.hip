@@ -240,11 +240,13 @@ __global__ __launch_bounds__(256) void k_rms_act(const float* __restrict__ Z, fl
   }
 }
 
-// LayerNorm(eps 1e-5) + tanh, forward / backward (ln_kernels.h with torch's eps and the activation as a compile-time constant)
+// LayerNorm + tanh, forward / backward (ln_kernels.h with the activation as a compile-time constant); eps is the block's: MPO's
+// torch.nn.LayerNorm 1e-5, FastMPO's `mpo` network kind flax's 1e-6
 template <bool BWD>
 __global__ __launch_bounds__(256) void k_mpo_ln_tanh(const float* __restrict__ Z, float* __restrict__ Y, const float* __restrict__ g,
-                                                     const float* __restrict__ be, float* __restrict__ partials, int64_t M, int D) {
-  ln_act_body<BWD, 8, RLX_ACT_TANH>(Z, Y, g, be, partials, M, D, RLX_ACT_TANH, MPO_LN_EPS);
+                                                     const float* __restrict__ be, float* __restrict__ partials, int64_t M, int D,
+                                                     float eps) {
+  ln_act_body<BWD, 8, RLX_ACT_TANH>(Z, Y, g, be, partials, M, D, RLX_ACT_TANH, eps);
 }
 
 // Dropout -> LayerNorm (flax: eps 1e-6, "fast variance") -> ReLU, forward / backward, over [M, D] (droq/flax/critic.py:27-30 and
@@ -434,8 +436,8 @@ static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, 
   RLX_REQUIRE(o.drop == 0.f, RLX_EUNSUP, "norm_act: dropout has a kernel in front of (LayerNorm eps 1e-6, ReLU) only");
   if (ln && o.act == RLX_ACT_SILU)      // (the activation as a run-time argument: k_ln_act_wide takes the switch once per launch)
     hipLaunchKernelGGL(k_ln_act_wide<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.act, o.eps);
-  else if (ln && th && o.eps == MPO_LN_EPS)
-    hipLaunchKernelGGL(k_mpo_ln_tanh<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D);
+  else if (ln && th)
+    hipLaunchKernelGGL(k_mpo_ln_tanh<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.eps);
   else if (o.norm == NORM_RMS && o.act == RLX_ACT_SILU)
     hipLaunchKernelGGL((k_rms_act<BWD, RLX_ACT_SILU>), dim3(grid), dim3(256), 4 * row, st, Z, Y, p + o.g, part, M, D, o.eps);
   else RLX_REQUIRE(false, RLX_EUNSUP, "norm_act: no kernel for this (norm, activation, eps)");

@@ -1,5 +1,5 @@
-// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip, droq.hip and
-// crossq.hip (the last five through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of brn.hip (batch
+// net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, fastmpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip,
+// droq.hip and crossq.hip (the last five through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of brn.hip (batch
 // renormalisation, the column-statistics layer), the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> [Dropout ->] {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list
@@ -29,7 +29,7 @@ int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int sch
 // ---- blocks: Linear W[in, out], b -> {no norm | LayerNorm scale g, bias be | RMSNorm scale g} -> act; W / b / g / be are
 // offsets in the flat parameter vector (-1: absent), in that order.  The flat layouts are ABI: make_block only advances `off`.
 enum NormKind { NORM_NONE = 0, NORM_LAYER = 1, NORM_RMS = 2 };
-constexpr float MPO_LN_EPS = 1e-5f;   // torch.nn.LayerNorm default (k_mpo_ln_tanh has it compiled in)
+constexpr float MPO_LN_EPS = 1e-5f;   // torch.nn.LayerNorm default (mpo.hip's blocks; k_mpo_ln_tanh takes the block's eps)
 // drop: the rate of a Dropout between the Linear and the norm (droq/flax/critic.py:27-30; 0: none).  It has no parameters.
 struct Block { int in, out; int64_t W, b, g, be; int norm, act; float eps; float drop; };
 static inline Block make_block(int64_t& off, int in, int out, int norm = NORM_NONE, int act = RLX_ACT_NONE, float eps = 0.f, float drop = 0.f) {

@@ -6,6 +6,7 @@ A subclass sets, in its __init__: torch, hiplib (rlx_amd.hip.lib), ctx (rlx_amd.
 learning_rate, anneal_learning_rate, learning_starts, capacity, n_steps, obs_norm (and then norm_mean / norm_var / norm_std /
 norm_count), obs_select (and then pidx), eval_env, train_env, horizon; its _alloc() creates ring, pos, size, idx_t, idx_e, total;
 it provides act(state, deterministic) -> the env's action, and the class attribute _NAME (the plugin's name)."""
+import numpy as np
 
 
 class FastOffPolicyLoop:
@@ -29,6 +30,19 @@ class FastOffPolicyLoop:
 
     def _columns(self, x, idx, out):
         return self.ctx.select_columns(x, idx, out) if self.obs_select else x
+
+    def _final_next_state(self, next_state, done, info):
+        """the observation an episode ENDED on where `done`, not the first one of the next episode that an auto-resetting env
+        returns (mpo.py:309-313 actual_next_state; fastmpo.py:247 env_state.actual_next_observation)"""
+        t = self.torch
+        dev = lambda x: (x if t.is_tensor(x) else t.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(self.device, t.float32)
+        fin = info.get("final_observation") if isinstance(info, dict) else None
+        if fin is not None and tuple(np.shape(fin)) == tuple(next_state.shape):
+            return t.where(done[:, None], dev(fin), next_state)
+        out = next_state.clone()
+        for i in t.nonzero(done).flatten().tolist():
+            out[i] = dev(self.train_env.get_final_observation_at_index(info, i))
+        return out
 
     def replay_add(self, state, next_state, action, reward, done, truncated):     # replay_buffer.py:23-31
         for dst, src in zip(self.ring, (state, next_state, action, reward, done, truncated)):

@@ -188,17 +188,6 @@ class MPO(FastOffPolicyLoop):
         self.sum_m += self.metrics
         self.n_met += 1
 
-    def _final_next_state(self, next_state, done, info):
-        """actual_next_state (mpo.py:309-313)"""
-        t = self.torch
-        fin = info.get("final_observation") if isinstance(info, dict) else None
-        if fin is not None and tuple(np.shape(fin)) == tuple(next_state.shape):
-            return t.where(done[:, None], self._dev(fin), next_state)
-        out = next_state.clone()
-        for i in t.nonzero(done).flatten().tolist():
-            out[i] = self._dev(self.train_env.get_final_observation_at_index(info, i))
-        return out
-
     # ------------------------------------------------------------------ training loop (mpo.py:272-500)
     def train(self):
         t = self.torch

@@ -159,6 +159,45 @@ class MpoHparams(Structure):
         ("action_sampling_number", c_int32), ("action_clipping", c_int32), ("action_rescaling", c_int32)]
 
 
+class FastMpoDesc(Structure):
+    """rlx_fastmpo_desc: FastMPO's policy and one or two critics (include/rlx_hip.h: kinds and flat layouts)."""
+    _fields_ = [(n, c_int32) for n in ("policy_obs_dim", "critic_obs_dim", "act_dim", "nr_atoms", "dual_critic", "policy_kind",
+                                       "critic_kind")] + [("policy_hidden", c_int32 * 3), ("critic_hidden", c_int32 * 3)]
+
+
+FASTMPO_KINDS = {"fastsac": 0, "fasttd3": 1, "mpo": 2}
+FASTMPO_RESCALING = {"none": 0, "normal": 1, "fastsac": 2}
+# the reference's widths (fastmpo/flax_full_jit/policy.py, critic.py)
+FASTMPO_POLICY_WIDTHS = {"fastsac": (512, 256, 128), "fasttd3": (512, 256, 128), "mpo": (512, 256, 128)}
+FASTMPO_CRITIC_WIDTHS = {"fastsac": (768, 384, 192), "fasttd3": (1024, 512, 256), "mpo": (512, 256, 128)}
+
+
+def fastmpo_desc(policy_obs_dim, critic_obs_dim, act_dim, nr_atoms, dual_critic=True, policy_kind="fastsac", critic_kind="fastsac",
+                 policy_hidden=None, critic_hidden=None):
+    d = FastMpoDesc()
+    d.policy_obs_dim, d.critic_obs_dim, d.act_dim, d.nr_atoms = int(policy_obs_dim), int(critic_obs_dim), int(act_dim), int(nr_atoms)
+    d.dual_critic = int(bool(dual_critic))
+    d.policy_kind = FASTMPO_KINDS[policy_kind] if isinstance(policy_kind, str) else int(policy_kind)
+    d.critic_kind = FASTMPO_KINDS[critic_kind] if isinstance(critic_kind, str) else int(critic_kind)
+    names = {v: k for k, v in FASTMPO_KINDS.items()}
+    ph = policy_hidden if policy_hidden is not None else FASTMPO_POLICY_WIDTHS[names[d.policy_kind]]
+    ch = critic_hidden if critic_hidden is not None else FASTMPO_CRITIC_WIDTHS[names[d.critic_kind]]
+    for i in range(3):
+        d.policy_hidden[i], d.critic_hidden[i] = int(ph[i]), int(ch[i])
+    return d
+
+
+class FastMpoHparams(Structure):
+    """rlx_fastmpo_hparams (fastmpo/flax_full_jit/default_config.py, what the update reads)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "v_min", "v_max", "max_grad_norm", "policy_weight_decay", "critic_weight_decay",
+                                       "dual_weight_decay", "adam_b1", "adam_b2", "adam_eps", "critic_tau", "policy_tau",
+                                       "epsilon_non_parametric", "epsilon_parametric_mu", "epsilon_parametric_sigma", "epsilon_penalty",
+                                       "policy_init_scale", "policy_min_scale", "float_epsilon", "min_log_temperature",
+                                       "min_log_alpha")] + [
+        (n, c_int32) for n in ("action_sampling_number", "action_clipping", "action_rescaling", "clipped_double_q_learning",
+                               "nr_critic_updates_per_policy_update", "nr_policy_updates_per_step")]
+
+
 class EspoHparams(Structure):
     """rlx_espo_hparams (espo/pytorch/default_config.py:18-24); delta_op: 0 mean, 1 median"""
     _fields_ = [(n, c_float) for n in ("max_ratio_delta", "entropy_coef", "critic_coef", "max_grad_norm", "adam_b1", "adam_b2",
@@ -372,6 +411,11 @@ _SIGNATURES = {
     "rlx_espo_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                     c_int, _I64P, c_float, POINTER(EspoHparams), c_void_p, POINTER(c_int32), c_void_p]),
+    "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
+    "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
+    "rlx_fastmpo_update_f32": (c_int, [c_void_p, POINTER(FastMpoDesc)] + [c_void_p] * 13 + [c_int, c_void_p, c_void_p] + [c_void_p] * 5 +
+                               [c_int64, _U32P, c_int, _I64P, _F32HP, _F32HP, _F32HP, POINTER(FastMpoHparams), c_void_p, c_void_p]),
     "rlx_dist_overflow_count": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "rlx_ppo_dist_prefetch": (c_int, [c_void_p, _U32P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rlx_ppo_update_dist_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p,
@@ -1334,6 +1378,45 @@ class Ctx:
             _ptr(cidx, i32, True), _ptr(a, f), _ptr(r, f), _ptr(d, f), _ptr(tr, f), _ptr(n, f), int(s.shape[0]), k, scheme, int(step),
             float(agent_lr), float(dual_lr), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_mpo_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32)
+
+    # ---- FastMPO (rl_x/algorithms/fastmpo/flax_full_jit)
+    def fastmpo_param_count(self, desc, net):
+        """net 0: policy, 1: ONE critic, 2: duals"""
+        return int(self.lib.rlx_fastmpo_param_count(ctypes.byref(desc), int(net)))
+
+    def fastmpo_act(self, desc, pparams, obs, key, action, processed, hp, low=None, high=None, deterministic=False, pidx=None,
+                    scheme=THREEFRY_PARTITIONABLE):
+        """action = mean + std eps from the given (online or target) policy parameters, and the processed action -> new key.
+        action_rescaling fastsac: `low` holds the action scale"""
+        f, k = self.torch.float32, _key_arr(key)
+        _check(self.lib.rlx_fastmpo_act_f32(self.h, ctypes.byref(desc), _ptr(pparams, f), _ptr(obs, f), int(obs.shape[1]),
+                                            _ptr(pidx, self.torch.int32, True), k, scheme, _ptr(action, f), _ptr(processed, f),
+                                            _ptr(low, f, True), _ptr(high, f, True), int(obs.shape[0]), int(bool(deterministic)),
+                                            ctypes.byref(hp), _stream()), "rlx_fastmpo_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def fastmpo_update(self, desc, nets, batch, noise_key, opt_counts, critic_lr, policy_lr, dual_lr, hp, metrics_out, pidx=None,
+                       cidx=None, scheme=THREEFRY_PARTITIONABLE):
+        """The optimisation of one learning iteration.  nets = (pparams, pm, pv, target_pparams, qparams, qm, qv, target_qparams, duals,
+        dm, dv); batch = (states, next_states [P G, B, O], actions [P G, B, A], rewards, dones, truncations, effective_n_steps
+        [P G, B]); opt_counts = (critic, policy, dual) optimiser steps so far; critic_lr [P G], policy_lr [P], dual_lr [P] host
+        arrays -> the new optimiser counts"""
+        f, i32 = self.torch.float32, self.torch.int32
+        s, s2, a, r, d, tr, n = batch
+        PG = int(hp.nr_policy_updates_per_step) * int(hp.nr_critic_updates_per_policy_update)
+        valid = int(hp.nr_policy_updates_per_step) >= 1 and int(hp.nr_critic_updates_per_policy_update) >= 1   # else the library refuses
+        if s.dim() != 3 or (valid and int(s.shape[0]) != PG):
+            raise RlxError(f"fastmpo_update: states must be [P G = {PG}, B, O], got {tuple(s.shape)}")
+        lrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (critic_lr, policy_lr, dual_lr)]
+        if valid and (lrs[0].size != PG or lrs[1].size != int(hp.nr_policy_updates_per_step) or lrs[2].size != lrs[1].size):
+            raise RlxError("fastmpo_update: critic_lr [P G], policy_lr [P], dual_lr [P]")
+        cnt = (c_int64 * 3)(*(int(x) for x in opt_counts))
+        _check(self.lib.rlx_fastmpo_update_f32(
+            self.h, ctypes.byref(desc), *(_ptr(x, f) for x in nets), _ptr(s, f), _ptr(s2, f), int(s.shape[2]), _ptr(pidx, i32, True),
+            _ptr(cidx, i32, True), _ptr(a, f), _ptr(r, f), _ptr(d, f), _ptr(tr, f), _ptr(n, f), int(s.shape[1]), _key_arr(noise_key), scheme,
+            cnt, lrs[0].ctypes.data_as(_F32HP), lrs[1].ctypes.data_as(_F32HP), lrs[2].ctypes.data_as(_F32HP), ctypes.byref(hp),
+            _ptr(metrics_out, f), _stream()), "rlx_fastmpo_update_f32")
+        return tuple(int(x) for x in cnt)
 
     # ---- ESPO (rl_x/algorithms/espo/pytorch)
     def espo_update(self, pdesc, pparams, pm, pv, cdesc, cparams, cm, cv, states, actions, log_probs, returns, advantages, idx,
