@@ -19,19 +19,11 @@ index vectors, as sac.hip's fully jitted flavour draws them -- and the acting no
 the reference addresses them), parameters initialised from numpy with the reference's schemes (flax Dense: lecun-normal weights,
 zero bias; LayerNorm 1 / 0; the heads as policy.py / critic.py give them), single GPU, nr_parallel_seeds == 1 (refused otherwise,
 as the reference refuses it)."""
-import json
-import logging
-import os
-import time
-
 import numpy as np
 
 from rlx_amd.algorithms.fast_offpolicy import FastOffPolicyLoop
 from rlx_amd.algorithms.fastmpo.hip.general_properties import GeneralProperties
-from rlx_amd.environments.data_interface_type import DataInterfaceType
-from rlx_amd.plugin import MetricSink, adopt_checkpoint_config
-
-rlx_logger = logging.getLogger("rl_x")
+from rlx_amd.algorithms.hip_model import TRUNC_NORMAL_STD, eval_means
 
 KINDS = ("fastsac", "fasttd3", "mpo")
 RESCALING = ("none", "normal", "fastsac")
@@ -42,7 +34,6 @@ POLICY_METRICS = ("loss/actor_loss", "loss/loss_pg_mean", "loss/loss_pg_std", "l
                   "policy/std_max_mean", "lr/policy_learning_rate", "lr/dual_variables_learning_rate", "gradients/policy_grad_norm",
                   "gradients/dual_variables_grad_norm")
 METRIC_NAMES = CRITIC_METRICS + POLICY_METRICS        # fastmpo.py:372-377, :595-596, :461-480, :624-627: rlx_fastmpo_update_f32's order
-TRUNC_NORMAL_STD = 0.87962566103423978               # std of a unit normal truncated at +-2 (jax.nn.initializers.variance_scaling)
 
 
 def _truncated_normal(rng, shape, std):
@@ -105,11 +96,11 @@ def critic_heads(kind, NA):
 
 class FastMPO(FastOffPolicyLoop):
     _NAME = "fastmpo.hip"
+    _STATE = ("pparams", "pm", "pv", "tpparams", "qparams", "qm", "qv", "tqparams", "duals", "dm", "dv")
+    _COUNTERS = ("opt_counts",)
 
     def __init__(self, config, train_env, eval_env, run_path, writer):
-        alg = config.algorithm
-        if alg.device != "gpu":
-            raise ValueError("fastmpo.hip runs on MI355X only: --algorithm.device must be 'gpu' (no CPU fallback)")
+        alg = self._read_flags(config, train_env, eval_env, run_path, writer)
         if int(alg.nr_parallel_seeds) > 1:                                                      # fastmpo.py:112-113
             raise ValueError("Parallel seeds are not supported yet.")
         if alg.policy_network_type not in KINDS or alg.critic_network_type not in KINDS:
@@ -120,10 +111,8 @@ class FastMPO(FastOffPolicyLoop):
             raise ValueError("fastmpo.hip: clipped_double_q_learning is only possible if dual_critic is True")
         if int(alg.learning_starts) < int(alg.n_steps):                                         # fastmpo.py:109-110
             raise ValueError("The replay buffer must at least be filled with n_steps transitions before learning starts.")
-        self.nr_envs = int(config.environment.nr_envs)
         self.logging_frequency = int(alg.logging_frequency)
         self.evaluation_and_save_frequency = int(alg.evaluation_and_save_frequency)
-        self.total_timesteps = int(alg.total_timesteps)
         if self.evaluation_and_save_frequency == -1:                                            # fastmpo.py:90-91
             self.evaluation_and_save_frequency = self.nr_envs * (self.total_timesteps // self.nr_envs)
         if self.evaluation_and_save_frequency % self.nr_envs != 0:                              # fastmpo.py:100-107
@@ -132,22 +121,6 @@ class FastMPO(FastOffPolicyLoop):
             raise ValueError("Logging frequency must be a multiple of nr envs.")
         if self.evaluation_and_save_frequency % self.logging_frequency != 0:
             raise ValueError("Evaluation and save frequency must be a multiple of logging frequency.")
-        import torch
-        from rlx_amd.hip import Ctx, FastMpoHparams, fastmpo_desc
-        from rlx_amd.hip import lib as hiplib
-        if train_env.general_properties.data_interface_type != DataInterfaceType.TORCH:
-            raise ValueError("fastmpo.hip needs a TORCH data-interface environment")
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise ValueError("fastmpo.hip is single-GPU (its normaliser statistics and gradients are not all-reduced)")
-        except ImportError:
-            pass
-        self.torch, self.hiplib = torch, hiplib
-        self.config, self.train_env, self.eval_env, self.writer = config, train_env, eval_env, writer
-        self.save_model = config.runner.save_model
-        self.save_path = os.path.join(run_path, "models")
-        self.seed = config.environment.seed
         self.lrs = tuple(float(alg[k]) for k in ("critic_learning_rate", "policy_learning_rate", "dual_learning_rate"))
         self.anneal = tuple(bool(alg[k]) for k in ("anneal_critic_learning_rate", "anneal_policy_learning_rate", "anneal_dual_learning_rate"))
         self.batch_size, self.capacity = int(alg.batch_size), int(alg.buffer_size_per_env)
@@ -156,28 +129,12 @@ class FastMPO(FastOffPolicyLoop):
         self.evaluation_active = bool(alg.evaluation_active)
         self.online_acting = bool(alg.collect_data_with_online_policy)
         self.obs_norm, self.norm_eps = bool(alg.enable_observation_normalization), float(alg.normalizer_epsilon)
-        self.scheme = 1 if alg.threefry_partitionable else 0
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.ctx = Ctx(self.device.index or 0)
-        self.sink = MetricSink(rlx_logger, writer, console=config.runner.track_console, tensorboard=config.runner.track_tb,
-                               wandb=config.runner.track_wandb, rank=0)
-        O = int(np.prod(train_env.single_observation_space.shape))
-        A = int(np.prod(train_env.single_action_space.shape))
-        self.obs_dim, self.act_dim = O, A
-        from rlx_amd.algorithms.ppo.hip.ppo import PPO as _PPO
-        pidx, cidx = _PPO._observation_indices(train_env, O)            # policy.py:18, critic.py:14
-        self.obs_select = pidx is not None
-        Op, Oc = (len(pidx), len(cidx)) if self.obs_select else (O, O)
-        self.pidx = torch.from_numpy(pidx).to(self.device) if self.obs_select else None
-        self.cidx = torch.from_numpy(cidx).to(self.device) if self.obs_select else None
-        # get_processed_action's operands (policy.py:28-37); spaces without center / scale: mid-point, 1
-        sp = train_env.single_action_space
-        low, high = (np.asarray(getattr(sp, k), np.float32).reshape(-1) for k in ("low", "high"))
-        center = np.asarray(getattr(sp, "center", 0.5 * (low + high)), np.float32).reshape(-1)
-        scale = np.asarray(getattr(sp, "scale", np.ones(A)), np.float32).reshape(-1)
+        self._open_device()
+        from rlx_amd.hip import FastMpoHparams, fastmpo_desc
+        torch = self.torch
+        A, Op, Oc = self.act_dim, self.policy_obs_dim, self.critic_obs_dim      # policy.py:18, critic.py:14
+        self._action_bounds()                                           # get_processed_action's operands (policy.py:28-37)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
-        self.act_low, self.act_high = t(low), t(high)
-        self.action_scale = t(np.maximum(np.abs(low - center), np.abs(high - center)) / scale)
         pk, ck, NA = str(alg.policy_network_type), str(alg.critic_network_type), int(alg.nr_atoms)
         self.E = 2 if bool(alg.dual_critic) else 1
         self.desc = fastmpo_desc(Op, Oc, A, NA, self.E == 2, pk, ck)    # the reference's widths (policy.py, critic.py)
@@ -194,11 +151,7 @@ class FastMPO(FastOffPolicyLoop):
         self.pm, self.pv, self.qm, self.qv, self.dm, self.dv = (z(x) for x in (self.pparams, self.pparams, self.qparams, self.qparams,
                                                                                self.duals, self.duals))
         self.opt_counts = (0, 0, 0)                                     # critic, policy, dual optimiser steps
-        self.key = hiplib.prng_key(self.seed)
-        if self.obs_norm:                                               # fastmpo.py:182-188
-            self.norm_mean, self.norm_var, self.norm_std = (torch.zeros(O, device=self.device), torch.ones(O, device=self.device),
-                                                            torch.ones(O, device=self.device))
-            self.norm_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._alloc_normalizer()                                        # fastmpo.py:182-188
         self.hp = hp = FastMpoHparams()
         for k in ("gamma", "v_min", "v_max", "max_grad_norm", "policy_weight_decay", "critic_weight_decay", "dual_weight_decay", "critic_tau",
                   "policy_tau", "epsilon_non_parametric", "epsilon_parametric_mu", "epsilon_parametric_sigma", "epsilon_penalty",
@@ -209,32 +162,15 @@ class FastMPO(FastOffPolicyLoop):
         hp.action_rescaling = RESCALING.index(alg.action_rescaling)
         hp.clipped_double_q_learning = int(bool(alg.clipped_double_q_learning))
         hp.nr_critic_updates_per_policy_update, hp.nr_policy_updates_per_step = self.G, self.P
-        self.horizon = getattr(train_env, "horizon", 1000)
-        if self.save_model:
-            os.makedirs(self.save_path, exist_ok=True)
 
     # ------------------------------------------------------------------ pieces
     def _alloc(self):
-        t = self.torch
-        N, O, A, cap = self.nr_envs, self.obs_dim, self.act_dim, self.capacity
-        f = dict(device=self.device, dtype=t.float32)
-        self.ring = (t.zeros(cap, N, O, **f), t.zeros(cap, N, O, **f), t.zeros(cap, N, A, **f), t.zeros(cap, N, **f), t.zeros(cap, N, **f),
-                     t.zeros(cap, N, **f))                                # states, next_states, actions, rewards, dones, truncations
-        self.pos = self.size = 0
-        T = self.P * self.G * self.batch_size
-        self.both = t.empty(2 * T, O, **f)                                # [states_all; next_states_all]: one normaliser merge
-        self.total = (self.both[:T], self.both[T:], t.empty(T, A, **f)) + tuple(t.empty(T, **f) for _ in range(4))
-        self.idx_t, self.idx_e = t.empty(T, dtype=t.int32, device=self.device), t.empty(T, dtype=t.int32, device=self.device)
+        t, T = self.torch, self.P * self.G * self.batch_size
+        f = self._alloc_ring(T)
+        self.both = t.empty(2 * T, self.obs_dim, **f)                     # [states_all; next_states_all]: one normaliser merge
+        self.total = (self.both[:T], self.both[T:]) + self.total[2:]
         n = len(METRIC_NAMES)
         self.metrics, self.sum_m, self.n_met = t.zeros(n, **f), t.zeros(n, **f), 0
-
-    def _act_buffers(self, n):
-        bufs = self.__dict__.setdefault("_act_bufs", {})
-        if n not in bufs:
-            t = self.torch
-            f = dict(device=self.device, dtype=t.float32)
-            bufs[n] = (t.empty(n, self.obs_dim, **f), t.empty(n, self.act_dim, **f), t.empty(n, self.act_dim, **f))
-        return bufs[n]
 
     def act_pair(self, state, deterministic=False, params=None):
         """normalise (statistics frozen) + mean + std eps -> (action for the ring, processed action)"""
@@ -305,61 +241,28 @@ class FastMPO(FastOffPolicyLoop):
         state = state.clone()
         for _ in range(self.learning_starts):                                                     # fastmpo.py:227-267
             state = self._vector_step(state)
-        global_step = nr_episodes = 0
-        last_log_time, last_log_step = time.time(), 0
+        global_step = 0
+        self._start_log()
         while global_step < self.total_timesteps:
             state = self._vector_step(state)
             self.optimize()
             global_step += self.nr_envs
             if global_step % self.logging_frequency == 0 or global_step >= self.total_timesteps:
-                now = time.time()
                 combined = {}
                 if self.n_met:
-                    m = (self.sum_m / self.n_met).cpu().tolist()                                 # one D2H per logging interval
-                    if not all(np.isfinite(v) for v in m):
-                        raise FloatingPointError("fastmpo.hip: non-finite loss / gradient norm since the last log " + str(m))
-                    combined.update(dict(zip(METRIC_NAMES, m)))
+                    combined.update(dict(zip(METRIC_NAMES, self._mean_metrics(self.sum_m))))        # one D2H per logging interval
                     self.sum_m.zero_()
                     self.n_met = 0
-                if hasattr(env, "pop_episode_stats"):
-                    n_done, mean_ret, mean_len = env.pop_episode_stats()
-                    nr_episodes += n_done
-                    if n_done:
-                        combined.update({"rollout/episode_return": mean_ret, "rollout/episode_length": mean_len})
+                self._episode_stats(combined)
                 combined.update({"steps/nr_env_steps": global_step, "steps/nr_policy_updates": self.opt_counts[1],
-                                 "steps/nr_critic_updates": self.opt_counts[0], "steps/nr_episodes": nr_episodes,
-                                 "time/sps": int((global_step - last_log_step) / max(now - last_log_time, 1e-9))})
-                last_log_time, last_log_step = now, global_step
+                                 "steps/nr_critic_updates": self.opt_counts[0], "steps/nr_episodes": self.nr_episodes,
+                                 "time/sps": self._sps(global_step)})
                 if global_step % self.evaluation_and_save_frequency == 0:                         # fastmpo.py:670-709
                     if self.evaluation_active:
-                        rets, lens = self.evaluate()
-                        combined.update({"eval/episode_return": float(np.mean(rets)) if rets else float("nan"),
-                                         "eval/episode_length": float(np.mean(lens)) if lens else float("nan")})
+                        combined.update(eval_means(*self.evaluate()))
                     if self.save_model:
                         self.save()
-                self.sink.write(global_step, combined)
-                self.last_metrics = combined
-
-    _STATE = ("pparams", "pm", "pv", "tpparams", "qparams", "qm", "qv", "tqparams", "duals", "dm", "dv")
-
-    def save(self):
-        """Native checkpoint: every network and target, the duals, all AdamW moments, the normaliser, the optimiser counts, the key
-        and the algorithm config (the reference stores its three train states and the normaliser, fastmpo.py:706-709)."""
-        path = os.path.join(self.save_path, "latest.model")
-        state = {k: getattr(self, k).cpu().numpy() for k in self._STATE + (self._NORM_STATE if self.obs_norm else ())}
-        np.savez(path + ".tmp.npz", opt_counts=np.asarray(self.opt_counts, np.int64), key=self.key,
-                 config_algorithm=json.dumps(self.config.algorithm.to_dict()), **state)
-        os.replace(path + ".tmp.npz", path)
-
-    def load(config, train_env, eval_env, run_path, writer, explicitly_set_algorithm_params):
-        ckpt = np.load(config.runner.load_model, allow_pickle=False)
-        adopt_checkpoint_config(config, json.loads(str(ckpt["config_algorithm"])), explicitly_set_algorithm_params)
-        model = FastMPO(config, train_env, eval_env, run_path, writer)
-        for k in FastMPO._STATE + (FastMPO._NORM_STATE if model.obs_norm else ()):
-            getattr(model, k).copy_(model.torch.from_numpy(ckpt[k]).to(model.device))
-        model.opt_counts = tuple(int(x) for x in ckpt["opt_counts"])
-        model.key = ckpt["key"].astype(np.uint32)
-        return model
+                self._write_log(global_step, combined)
 
     def general_properties():
         return GeneralProperties

@@ -14,19 +14,12 @@ numbers (torch / numpy generators there; the library's counter RNG here for the 
 numpy for the warm-up actions), fp32 instead of bf16 autocast, parameters initialised from numpy with the reference's own schemes
 (uniform +-sqrt(3 / fan_in) 0.333 hidden layers with zero bias, LayerNorm 1 / 0, heads N(0, std^2) with policy.py:61-68's variance
 scaling)."""
-import json
-import logging
-import os
-import time
-
 import numpy as np
 
 from rlx_amd.algorithms.fast_offpolicy import FastOffPolicyLoop
+from rlx_amd.algorithms.hip_model import TRUNC_NORMAL_STD, eval_means
 from rlx_amd.algorithms.mpo.hip.general_properties import GeneralProperties
 from rlx_amd.environments.data_interface_type import DataInterfaceType
-from rlx_amd.plugin import MetricSink, adopt_checkpoint_config
-
-rlx_logger = logging.getLogger("rl_x")
 
 METRIC_NAMES = ("loss/critic_loss", "loss/actor_loss", "loss/dual_loss", "loss/loss_eta", "loss/loss_alpha", "q/current_q_mean",
                 "dual/eta", "dual/penalty_temperature", "dual/alpha_mean", "dual/alpha_std", "kl/mean_kl_mean", "kl/mean_kl_std",
@@ -45,30 +38,19 @@ def init_params(rng, in_dim, H, out_dim, head_std):
         if li == 0:
             parts += [np.ones(H), np.zeros(H)]
         d = H
-    std = np.sqrt(head_std / H) / 0.87962566103423978
+    std = np.sqrt(head_std / H) / TRUNC_NORMAL_STD
     parts += [rng.normal(0.0, std, (H, out_dim)), np.zeros(out_dim)]
     return np.concatenate([p.reshape(-1) for p in parts]).astype(np.float32)
 
 
 class MPO(FastOffPolicyLoop):
     _NAME = "mpo.hip"
+    _FILE = "best.model"
+    _STATE = ("pparams", "pm", "pv", "tpparams", "qparams", "qm", "qv", "tqparams", "env_pparams", "duals", "dm", "dv")
+    _COUNTERS = ("nr_updates",)
 
     def __init__(self, config, train_env, eval_env, run_path, writer):
-        alg = config.algorithm
-        if alg.device != "gpu":
-            raise ValueError("mpo.hip runs on MI355X only: --algorithm.device must be 'gpu' (no CPU fallback)")
-        if bool(alg.bf16_mixed_precision_training):
-            raise ValueError("mpo.hip computes in fp32: set --algorithm.bf16_mixed_precision_training=False")
-        import torch
-        from rlx_amd.hip import Ctx, MpoHparams, mpo_desc
-        from rlx_amd.hip import lib as hiplib
-        self.torch, self.hiplib = torch, hiplib
-        self.config, self.train_env, self.eval_env, self.writer = config, train_env, eval_env, writer
-        self.save_model = config.runner.save_model
-        self.save_path = os.path.join(run_path, "models")
-        self.seed = config.environment.seed
-        self.nr_envs = int(config.environment.nr_envs)
-        self.total_timesteps = int(alg.total_timesteps)
+        alg = self._read_flags(config, train_env, eval_env, run_path, writer)
         self.agent_lr, self.dual_lr = float(alg.agent_learning_rate), float(alg.dual_learning_rate)
         self.anneal_agent, self.anneal_dual = bool(alg.anneal_agent_learning_rate), bool(alg.anneal_dual_learning_rate)
         self.learning_starts, self.batch_size, self.n_steps = int(alg.learning_starts), int(alg.batch_size), int(alg.n_steps)
@@ -78,24 +60,12 @@ class MPO(FastOffPolicyLoop):
         self.logging_frequency, self.evaluation_frequency = int(alg.logging_frequency), int(alg.evaluation_frequency)
         self.evaluation_episodes = int(alg.evaluation_episodes)
         self.obs_norm = bool(alg.enable_observation_normalization)
-        self.scheme = 1 if alg.threefry_partitionable else 0
+        self._open_device(torch_env_only=False)
+        from rlx_amd.hip import MpoHparams, mpo_desc
+        torch = self.torch
         self.numpy_env = train_env.general_properties.data_interface_type == DataInterfaceType.NUMPY
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.ctx = Ctx(self.device.index or 0)
-        self.sink = MetricSink(rlx_logger, writer, console=config.runner.track_console, tensorboard=config.runner.track_tb,
-                               wandb=config.runner.track_wandb, rank=0)
-        O = int(np.prod(train_env.single_observation_space.shape))
-        A = int(np.prod(train_env.single_action_space.shape))
-        self.obs_dim, self.act_dim = O, A
-        from rlx_amd.algorithms.ppo.hip.ppo import PPO as _PPO
-        pidx, cidx = _PPO._observation_indices(train_env, O)            # policy.py:13, q_network.py:10
-        self.obs_select = pidx is not None
-        Op, Oc = (len(pidx), len(cidx)) if self.obs_select else (O, O)
-        self.pidx = torch.from_numpy(pidx).to(self.device) if self.obs_select else None
-        self.cidx = torch.from_numpy(cidx).to(self.device) if self.obs_select else None
-        sp = train_env.single_action_space
-        self.low_np, self.high_np = (np.asarray(getattr(sp, k), np.float32).reshape(-1) for k in ("low", "high"))
-        self.act_low, self.act_high = (torch.from_numpy(x.copy()).to(self.device) for x in (self.low_np, self.high_np))
+        A, Op, Oc = self.act_dim, self.policy_obs_dim, self.critic_obs_dim              # policy.py:13, q_network.py:10
+        self.low_np, self.high_np = self._action_bounds()
         H, NA = int(alg.nr_hidden_units), int(alg.nr_atoms)
         self.desc = mpo_desc(Op, Oc, A, H, NA)
         rng = np.random.default_rng(self.seed)
@@ -110,11 +80,7 @@ class MPO(FastOffPolicyLoop):
         self.pm, self.pv, self.qm, self.qv, self.dm, self.dv = (z(x) for x in (self.pparams, self.pparams, self.qparams, self.qparams,
                                                                                self.duals, self.duals))
         self.nr_updates = 0
-        self.key = hiplib.prng_key(self.seed)
-        if self.obs_norm:     # observation_normalizer.py
-            self.norm_mean, self.norm_var, self.norm_std = (torch.zeros(O, device=self.device), torch.ones(O, device=self.device),
-                                                            torch.ones(O, device=self.device))
-            self.norm_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._alloc_normalizer()
         self.hp = hp = MpoHparams()
         for k in ("gamma", "v_min", "v_max", "max_grad_norm", "epsilon_non_parametric", "epsilon_parametric_mu", "epsilon_parametric_sigma",
                   "epsilon_penalty", "policy_init_scale", "policy_min_scale", "float_epsilon", "min_log_temperature", "min_log_alpha"):
@@ -122,35 +88,17 @@ class MPO(FastOffPolicyLoop):
         hp.adam_b1, hp.adam_b2, hp.adam_eps = 0.9, 0.999, 1e-8                      # torch.optim.Adam defaults (mpo.py:101-103)
         hp.action_sampling_number = int(alg.action_sampling_number)
         hp.action_clipping, hp.action_rescaling = int(bool(alg.action_clipping)), int(bool(alg.action_rescaling))
-        self.horizon = getattr(train_env, "horizon", 1000)
-        if self.save_model:
-            os.makedirs(self.save_path, exist_ok=True)
-            self.best_mean_return = -np.inf
+        self.best_mean_return = -np.inf
 
     # ------------------------------------------------------------------ pieces
     def _alloc(self):
-        t = self.torch
-        N, O, A, cap, B = self.nr_envs, self.obs_dim, self.act_dim, self.capacity, self.batch_size
-        f = dict(device=self.device, dtype=t.float32)
-        self.ring = (t.zeros(cap, N, O, **f), t.zeros(cap, N, O, **f), t.zeros(cap, N, A, **f), t.zeros(cap, N, **f), t.zeros(cap, N, **f),
-                     t.zeros(cap, N, **f))                                # states, next_states, actions, rewards, dones, truncations
-        self.pos = self.size = 0
-        self.total = (t.empty(B, O, **f), t.empty(B, O, **f), t.empty(B, A, **f)) + tuple(t.empty(B, **f) for _ in range(4))
-        self.idx_t, self.idx_e = t.empty(B, dtype=t.int32, device=self.device), t.empty(B, dtype=t.int32, device=self.device)
+        t, f = self.torch, self._alloc_ring(self.batch_size)
         self.metrics, self.sum_m, self.n_met = t.zeros(17, **f), t.zeros(17, **f), 0
 
     def _dev(self, x, dtype=None):
         t = self.torch
         x = x if t.is_tensor(x) else t.from_numpy(np.ascontiguousarray(np.asarray(x)))
         return x.to(self.device, dtype or t.float32).contiguous()
-
-    def _act_buffers(self, n):
-        bufs = self.__dict__.setdefault("_act_bufs", {})
-        if n not in bufs:
-            t = self.torch
-            f = dict(device=self.device, dtype=t.float32)
-            bufs[n] = (t.empty(n, self.obs_dim, **f), t.empty(n, self.act_dim, **f), t.empty(n, self.act_dim, **f))
-        return bufs[n]
 
     def act_pair(self, state, deterministic=False, params=None):
         """normalize(update=False) + sample_action / get_deterministic_action -> (action for the ring, processed action), on the device"""
@@ -195,8 +143,8 @@ class MPO(FastOffPolicyLoop):
         env = self.train_env
         state, _ = env.reset()
         state = self._dev(state)
-        global_step = nr_episodes = 0
-        last_log_time, last_log_step = time.time(), 0
+        global_step = 0
+        self._start_log()
         returns = []
         while global_step < self.total_timesteps:
             if global_step < self.learning_starts:                                            # mpo.py:298-300
@@ -225,37 +173,26 @@ class MPO(FastOffPolicyLoop):
             if started and iteration % self.optimize_every == 0:
                 self.optimize()
             if self.evaluation_frequency != -1 and global_step % self.evaluation_frequency == 0:
-                rets, lens = self.evaluate()
-                self.last_eval = {"eval/episode_return": float(np.mean(rets)) if rets else float("nan"),
-                                  "eval/episode_length": float(np.mean(lens)) if lens else float("nan")}
+                self.last_eval = eval_means(*self.evaluate())
             if global_step % self.logging_frequency == 0 or global_step >= self.total_timesteps:
-                now = time.time()
                 combined = {}
                 if hasattr(env, "pop_episode_stats"):
-                    n_done, mean_ret, mean_len = env.pop_episode_stats()
-                    nr_episodes += n_done
-                    if n_done:
-                        combined.update({"rollout/episode_return": mean_ret, "rollout/episode_length": mean_len})
+                    self._episode_stats(combined)
                 elif returns:
-                    nr_episodes += len(returns)
+                    self.nr_episodes += len(returns)
                     combined["rollout/episode_return"] = float(np.mean(returns))
                 if self.save_model and returns and float(np.mean(returns)) > self.best_mean_return and self.n_met:
                     self.best_mean_return = float(np.mean(returns))
                     self.save()
                 returns = []
                 combined.update(getattr(self, "last_eval", {}))
-                combined.update({"steps/nr_env_steps": global_step, "steps/nr_updates": self.nr_updates, "steps/nr_episodes": nr_episodes,
-                                 "time/sps": int((global_step - last_log_step) / max(now - last_log_time, 1e-9))})
+                combined.update({"steps/nr_env_steps": global_step, "steps/nr_updates": self.nr_updates,
+                                 "steps/nr_episodes": self.nr_episodes, "time/sps": self._sps(global_step)})
                 if self.n_met:
-                    m = (self.sum_m / self.n_met).cpu().tolist()                                 # one D2H per logging interval
-                    if not all(np.isfinite(v) for v in m):
-                        raise FloatingPointError("mpo.hip: non-finite loss / gradient norm since the last log " + str(m))
-                    combined.update(dict(zip(METRIC_NAMES, m)))
+                    combined.update(dict(zip(METRIC_NAMES, self._mean_metrics(self.sum_m))))        # one D2H per logging interval
                     self.sum_m.zero_()
                     self.n_met = 0
-                last_log_time, last_log_step = now, global_step
-                self.sink.write(global_step, combined)
-                self.last_metrics = combined
+                self._write_log(global_step, combined)
 
     def evaluate(self):
         """`horizon` deterministic steps of the online actor on the eval env -> (episode returns, lengths); NUMPY or TORCH env"""
@@ -284,27 +221,6 @@ class MPO(FastOffPolicyLoop):
         finally:
             if shared:
                 env.restore(snap)
-
-    _STATE = ("pparams", "pm", "pv", "tpparams", "qparams", "qm", "qv", "tqparams", "env_pparams", "duals", "dm", "dv")
-
-    def save(self):
-        """Native checkpoint: every network, target, the env actor, the duals, all Adam moments, the normaliser, counters and the
-        algorithm config (the reference stores the modules' and optimisers' state_dicts, mpo.py:532-548)."""
-        path = os.path.join(self.save_path, "best.model")
-        state = {k: getattr(self, k).cpu().numpy() for k in self._STATE + (self._NORM_STATE if self.obs_norm else ())}
-        np.savez(path + ".tmp.npz", nr_updates=self.nr_updates, key=self.key, config_algorithm=json.dumps(self.config.algorithm.to_dict()),
-                 **state)
-        os.replace(path + ".tmp.npz", path)
-
-    def load(config, train_env, eval_env, run_path, writer, explicitly_set_algorithm_params):
-        ckpt = np.load(config.runner.load_model, allow_pickle=False)
-        adopt_checkpoint_config(config, json.loads(str(ckpt["config_algorithm"])), explicitly_set_algorithm_params)
-        model = MPO(config, train_env, eval_env, run_path, writer)
-        for k in MPO._STATE + (MPO._NORM_STATE if model.obs_norm else ()):
-            getattr(model, k).copy_(model.torch.from_numpy(ckpt[k]).to(model.device))
-        model.nr_updates = int(ckpt["nr_updates"])
-        model.key = ckpt["key"].astype(np.uint32)
-        return model
 
     def general_properties():
         return GeneralProperties

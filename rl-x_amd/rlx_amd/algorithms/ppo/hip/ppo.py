@@ -27,6 +27,7 @@ import time
 
 import numpy as np
 
+from rlx_amd.algorithms.hip_model import observation_indices
 from rlx_amd.algorithms.ppo.hip.general_properties import GeneralProperties
 from rlx_amd.environments.action_space_type import ActionSpaceType
 from rlx_amd.environments.data_interface_type import DataInterfaceType
@@ -246,21 +247,7 @@ class PPO:
             self.best_mean_return = -np.inf
             self.best_model_file_name = "best.model"
 
-    @staticmethod
-    def _observation_indices(env, obs_dim):
-        """(policy columns, critic columns) as int32 arrays when the env defines either index set, else (None, None).
-        A missing set means all columns (`getattr(env, ..., jnp.arange(obs_dim))`, ppo/flax/policy.py:13)."""
-        pidx = getattr(env, "policy_observation_indices", None)
-        cidx = getattr(env, "critic_observation_indices", None)
-        if pidx is None and cidx is None:
-            return None, None
-        out = []
-        for name, idx in (("policy", pidx), ("critic", cidx)):
-            idx = np.arange(obs_dim) if idx is None else np.asarray(idx).reshape(-1)
-            if idx.size == 0 or idx.min() < 0 or idx.max() >= obs_dim:
-                raise ValueError(f"{name}_observation_indices must be non-empty and within [0, {obs_dim})")
-            out.append(np.ascontiguousarray(idx, dtype=np.int32))
-        return out[0], out[1]
+    _observation_indices = staticmethod(observation_indices)       # ppo_lstm.hip reaches it through `self`
 
     # ------------------------------------------------------------------ schedule
     def lr_schedule(self):

@@ -12,19 +12,13 @@ What differs from the reference, on purpose: random numbers (torch's CUDA genera
 instead of bf16 autocast, parameters initialised from numpy with torch's defaults (Linear uniform +-1/sqrt(fan_in), RMSNorm 1,
 zero_distribution from its erf formula, log of the initial coefficients) drawn from np.random.default_rng([seed, 1]) -- a stream
 separate from the permutation generator."""
-import json
-import logging
 import math
-import os
 import time
 
 import numpy as np
 
+from rlx_amd.algorithms.hip_model import HipModel, eval_means
 from rlx_amd.algorithms.reppo.hip.general_properties import GeneralProperties
-from rlx_amd.environments.data_interface_type import DataInterfaceType
-from rlx_amd.plugin import MetricSink, adopt_checkpoint_config
-
-rlx_logger = logging.getLogger("rl_x")
 
 METRIC_NAMES = ("loss/critic_loss", "loss/auxiliary_loss", "q/q_mean", "q/explained_variance", "gradients/critic_grad_norm",
                 "loss/policy_loss", "loss/entropy_coefficient_loss", "loss/kl_coefficient_loss", "entropy/entropy",
@@ -54,24 +48,19 @@ def init_params(rng, Op, Oc, A, Hp, Hc, nr_bins, v_min, v_max, init_entropy_coef
     return np.concatenate(p).astype(np.float32), np.concatenate(q).astype(np.float32)
 
 
-class REPPO:
+class REPPO(HipModel):
+    _NAME = "reppo.hip"
+    _FILE = "best.model"
+    _STATE = ("pparams", "pm", "pv", "qparams", "qm", "qv", "norm_mean", "norm_var", "norm_count")
+    _NORM_STATE = ()                # the float32-count normaliser below is part of _STATE whether or not it is applied
+    _COUNTERS = ("opt_count", "nr_iterations_done")
+
     def __init__(self, config, train_env, eval_env, run_path, writer):
-        import torch
-        from rlx_amd.hip import Ctx, ReppoHparams, reppo_desc
-        from rlx_amd.hip import lib as hiplib
-        self.torch, self.hiplib = torch, hiplib
-        self.config, self.train_env, self.eval_env, self.writer = config, train_env, eval_env, writer
-        alg = config.algorithm
-        self.save_model = config.runner.save_model
-        self.save_path = os.path.join(run_path, "models")
-        self.seed = config.environment.seed
-        self.nr_envs = int(config.environment.nr_envs)
-        self.total_timesteps = int(alg.total_timesteps)
+        alg = self._read_flags(config, train_env, eval_env, run_path, writer)
         self.learning_rate, self.anneal_learning_rate = float(alg.learning_rate), bool(alg.anneal_learning_rate)
         self.nr_steps, self.nr_epochs, self.nr_minibatches = int(alg.nr_steps), int(alg.nr_epochs), int(alg.nr_minibatches)
         self.evaluation_frequency, self.evaluation_episodes = int(alg.evaluation_frequency), int(alg.evaluation_episodes)
         self.obs_norm = bool(alg.normalize_observation)
-        self.scheme = 1 if alg.threefry_partitionable else 0
         self.batch_size = self.nr_envs * self.nr_steps
         self.nr_rollout_updates = self.total_timesteps // self.batch_size
         if self.nr_rollout_updates == 0:                                                          # reppo.py:65-70
@@ -80,30 +69,10 @@ class REPPO:
             raise ValueError("The rollout batch size must be divisible by the number of minibatches.")
         if self.evaluation_frequency != -1 and self.evaluation_frequency % self.batch_size != 0:
             raise ValueError("Evaluation frequency must be a multiple of the number of steps and environments.")
-        if alg.device != "gpu":
-            raise ValueError("reppo.hip runs on MI355X only: --algorithm.device must be 'gpu' (no CPU fallback)")
-        if bool(alg.bf16_mixed_precision_training):
-            raise ValueError("reppo.hip computes in fp32: set --algorithm.bf16_mixed_precision_training=False")
-        if train_env.general_properties.data_interface_type != DataInterfaceType.TORCH:
-            raise ValueError("reppo.hip needs a TORCH data-interface environment")
-        try:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise ValueError("reppo.hip is single-GPU (its normaliser statistics and gradients are not all-reduced)")
-        except ImportError:
-            pass
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        self.ctx = Ctx(self.device.index or 0)
-        self.sink = MetricSink(rlx_logger, writer, console=config.runner.track_console, tensorboard=config.runner.track_tb,
-                               wandb=config.runner.track_wandb, rank=0)
-        O = int(np.prod(train_env.single_observation_space.shape))
-        A = int(np.prod(train_env.single_action_space.shape))
-        self.obs_dim, self.act_dim = O, A
-        from rlx_amd.algorithms.ppo.hip.ppo import PPO as _PPO
-        pidx, cidx = _PPO._observation_indices(train_env, O)                   # policy.py:13, critic.py:11
-        Op, Oc = (len(pidx), len(cidx)) if pidx is not None else (O, O)
-        self.pidx = torch.from_numpy(np.asarray(pidx, np.int32)).to(self.device) if pidx is not None else None
-        self.cidx = torch.from_numpy(np.asarray(cidx, np.int32)).to(self.device) if pidx is not None else None
+        self._open_device()
+        from rlx_amd.hip import ReppoHparams, reppo_desc
+        torch = self.torch
+        O, A, Op, Oc = self.obs_dim, self.act_dim, self.policy_obs_dim, self.critic_obs_dim     # policy.py:13, critic.py:11
         sp = train_env.single_action_space                                     # policy.py:30-39
         low, high = (np.asarray(getattr(sp, k), np.float32).reshape(-1) for k in ("low", "high"))
         if hasattr(sp, "center") and hasattr(sp, "scale"):
@@ -120,7 +89,6 @@ class REPPO:
         self.pm, self.pv, self.qm, self.qv = z(self.pparams), z(self.pparams), z(self.qparams), z(self.qparams)
         self.opt_count = 0
         self.nr_iterations_done = 0
-        self.key = hiplib.prng_key(self.seed)
         self.rng = np.random.default_rng(self.seed)                            # reppo.py:84: the permutation generator
         self.norm_mean, self.norm_var = torch.zeros(O, device=self.device), torch.ones(O, device=self.device)
         self.norm_count = torch.full((1,), 1e-4, device=self.device)            # observation_normalizer.py:11
@@ -130,10 +98,7 @@ class REPPO:
         self.hp.target_entropy = A * float(alg.target_entropy_multiplier)       # reppo.py:63
         self.hp.adam_b1, self.hp.adam_b2, self.hp.adam_eps = 0.9, 0.999, 1e-8   # torch.optim.Adam defaults (reppo.py:97-98)
         self.hp.nr_kl_samples = int(alg.nr_kl_samples)
-        self.horizon = getattr(train_env, "horizon", 1000)
-        if self.save_model:
-            os.makedirs(self.save_path, exist_ok=True)
-            self.best_mean_return = -np.inf
+        self.best_mean_return = -np.inf
 
     # ------------------------------------------------------------------ pieces
     def current_lr(self, iteration):
@@ -150,16 +115,9 @@ class REPPO:
             self.ctx.reppo_obs_norm_update(obs, self.norm_mean, self.norm_var, self.norm_count)
         return self.ctx.reppo_obs_norm_apply(obs, self.norm_mean, self.norm_var, out)
 
-    def _bufs(self, n):
-        bufs = self.__dict__.setdefault("_act_bufs", {})
-        if n not in bufs:
-            t, f = self.torch, dict(device=self.device, dtype=self.torch.float32)
-            bufs[n] = (t.empty(n, self.obs_dim, **f), t.empty(n, self.act_dim, **f), t.empty(n, self.act_dim, **f))
-        return bufs[n]
-
     def act(self, state, deterministic=False):
         """normalize (no update) + rollout_act / deterministic_action -> the env's action (evaluation, test())"""
-        x, action, processed = self._bufs(int(state.shape[0]))
+        x, action, processed = self._act_buffers(int(state.shape[0]))
         self.normalize(state.contiguous(), x, False)
         self.key = self.ctx.reppo_act(self.desc, self.pparams, x, self.key, action, processed, self.act_low, self.act_high, self.hp,
                                       deterministic, pidx=self.pidx, scheme=self.scheme)
@@ -219,10 +177,7 @@ class REPPO:
                                                          self.qv, batch, perm, self.nr_minibatches, self.key, self.opt_count, lr, self.hp,
                                                          self.metrics, pidx=self.pidx, cidx=self.cidx, scheme=self.scheme)
         self.nr_iterations_done += 1
-        means = self.metrics.mean(0).cpu().tolist()                                # the iteration's one host read
-        if not all(np.isfinite(v) for v in means):
-            raise FloatingPointError("reppo.hip: non-finite loss / gradient norm in this iteration " + str(means))
-        out = dict(zip(METRIC_NAMES, means))
+        out = dict(zip(METRIC_NAMES, self._finite(self.metrics.mean(0).cpu().tolist(), "in this iteration")))    # the one host read
         out["lr/learning_rate"] = lr if not self.anneal_learning_rate else self.current_lr(self.nr_iterations_done)
         return out
 
@@ -231,7 +186,8 @@ class REPPO:
         self._alloc()
         state, _ = self.train_env.reset()
         state = state.clone()
-        global_step = nr_episodes = 0
+        global_step = 0
+        self._start_log()
         prev_end = None
         while global_step < self.total_timesteps:
             start = time.time()
@@ -242,80 +198,24 @@ class REPPO:
             metrics = self.optimize()
             optimizing_end = time.time()
             if self.evaluation_frequency != -1 and global_step % self.evaluation_frequency == 0:
-                rets, lens = self.evaluate(self.evaluation_episodes)
-                metrics.update({"eval/episode_return": float(np.mean(rets)) if rets else float("nan"),
-                                "eval/episode_length": float(np.mean(lens)) if lens else float("nan")})
-            if hasattr(self.train_env, "pop_episode_stats"):
-                n_done, mean_ret, mean_len = self.train_env.pop_episode_stats()
-                nr_episodes += n_done
-                if n_done:
-                    metrics.update({"rollout/episode_return": mean_ret, "rollout/episode_length": mean_len})
-                    if self.save_model and mean_ret > self.best_mean_return:
-                        self.best_mean_return = mean_ret
-                        self.save()
+                metrics.update(eval_means(*self.evaluate(self.evaluation_episodes)))
+            n_done, mean_ret = self._episode_stats(metrics)
+            if n_done and self.save_model and mean_ret > self.best_mean_return:
+                self.best_mean_return = mean_ret
+                self.save()
             end = time.time()
             metrics.update({"time/acting_time": acting_end - start, "time/optimizing_time": optimizing_end - acting_end,
-                            "steps/nr_env_steps": global_step, "steps/nr_updates": self.opt_count, "steps/nr_episodes": nr_episodes})
-            if prev_end is not None:
+                            "steps/nr_env_steps": global_step, "steps/nr_updates": self.opt_count, "steps/nr_episodes": self.nr_episodes})
+            if prev_end is not None:                                       # per iteration, end to end: absent from the first
                 metrics["time/sps"] = int(self.batch_size / max(end - prev_end, 1e-9))
             prev_end = end
-            self.sink.write(global_step, metrics)
-            self.last_metrics = metrics
-
-    def evaluate(self, episodes):
-        """deterministic episodes on the eval env until `episodes` have ended (reppo.py:413-450) -> (returns, lengths)"""
-        env, t = self.eval_env, self.torch
-        shared = env is self.train_env
-        if shared and not hasattr(env, "snapshot"):
-            raise ValueError("reppo.hip: evaluation on the training env needs env.snapshot()/restore(); "
-                             "set environment.copy_train_env_for_eval=False")
-        snap = env.snapshot() if shared else None
-        try:
-            state, _ = env.reset()
-            ne = state.shape[0]
-            ep_ret, ep_len = t.zeros(ne, device=self.device), t.zeros(ne, device=self.device)
-            returns, lengths = [], []
-            for _ in range(100 * int(self.horizon)):
-                state, reward, terminated, truncated, _ = env.step(self.act(state, deterministic=True))
-                ep_ret += reward
-                ep_len += 1
-                done = terminated | truncated
-                if bool(done.any()):
-                    returns.extend(ep_ret[done].cpu().tolist())
-                    lengths.extend(ep_len[done].cpu().tolist())
-                    ep_ret = t.where(done, t.zeros_like(ep_ret), ep_ret)
-                    ep_len = t.where(done, t.zeros_like(ep_len), ep_len)
-                    if len(returns) >= episodes:
-                        break
-            return returns[:episodes], lengths[:episodes]
-        finally:
-            if shared:
-                env.restore(snap)
+            self._write_log(global_step, metrics)
 
     def test(self, episodes):
         return self.evaluate(episodes)[0]
 
-    _STATE = ("pparams", "pm", "pv", "qparams", "qm", "qv", "norm_mean", "norm_var", "norm_count")
-
-    def save(self):
-        """Native checkpoint: flat parameter / Adam-moment vectors, normaliser statistics, counters, the algorithm config (the
-        reference stores the modules' and optimisers' state_dicts)."""
-        path = os.path.join(self.save_path, "best.model")
-        state = {k: getattr(self, k).cpu().numpy() for k in self._STATE}
-        np.savez(path + ".tmp.npz", opt_count=self.opt_count, nr_iterations_done=self.nr_iterations_done, key=self.key,
-                 config_algorithm=json.dumps(self.config.algorithm.to_dict()), **state)
-        os.replace(path + ".tmp.npz", path)
-
-    def load(config, train_env, eval_env, run_path, writer, explicitly_set_algorithm_params):
-        ckpt = np.load(config.runner.load_model, allow_pickle=False)
-        adopt_checkpoint_config(config, json.loads(str(ckpt["config_algorithm"])), explicitly_set_algorithm_params)
-        model = REPPO(config, train_env, eval_env, run_path, writer)
-        for k in REPPO._STATE:
-            getattr(model, k).copy_(model.torch.from_numpy(ckpt[k]).to(model.device))
-        model.old_pparams.copy_(model.pparams)
-        model.opt_count, model.nr_iterations_done = int(ckpt["opt_count"]), int(ckpt["nr_iterations_done"])
-        model.key = ckpt["key"].astype(np.uint32)
-        return model
+    def _after_load(self):
+        self.old_pparams.copy_(self.pparams)
 
     def general_properties():
         return GeneralProperties

@@ -123,8 +123,8 @@ class SAC:
         # Networks on a SUBSET of the observation (`x[..., self.policy_observation_indices]`, sac/flax/policy.py:14,31; the
         # critics: critic.py:11,23): the replay ring keeps the env's full rows; the columns are selected from the sampled batch
         # (and from the acting observation) with rlx_select_columns_f32.
-        from rlx_amd.algorithms.ppo.hip.ppo import PPO as _PPO
-        pidx, cidx = _PPO._observation_indices(train_env, O)
+        from rlx_amd.algorithms.hip_model import observation_indices
+        pidx, cidx = observation_indices(train_env, O)
         self.obs_select = pidx is not None
         self.policy_obs_dim, self.critic_obs_dim = (len(pidx), len(cidx)) if self.obs_select else (O, O)
         if self.obs_select:
