@@ -189,7 +189,9 @@ __global__ __launch_bounds__(L1_THREADS) void k_l1(const float* __restrict__ X, 
   const int64_t wave_g = (int64_t)blockIdx.x * NW + w, nwaves = (int64_t)gridDim.x * NW;
 #define RLX_L1_BODY(ACT, LNB) \
   l1_rows<BWD, ACT, LNB, (BWD ? L1_R_BWD : L1_R_FWD)>(a, Ws, bs, gs, bes, dg, dbe, lane, wave_g, nwaves)
-  if (ln) {
+  if (BWD && ln && act == RLX_ACT_NONE) {
+    RLX_L1_BODY(RLX_ACT_NONE, true);      // H holds dL/dy already (act' applied by the caller's head kernel): LayerNorm' only
+  } else if (ln) {
     if (act == RLX_ACT_ELU) RLX_L1_BODY(RLX_ACT_ELU, true);
     else if (act == RLX_ACT_TANH) RLX_L1_BODY(RLX_ACT_TANH, true);
     else RLX_L1_BODY(RLX_ACT_RELU, true);
@@ -1368,9 +1370,13 @@ int mlp_trunk_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const MlpLayout& L, const
   if (!fuse_l1 && !wide) {
     RLX_REQUIRE(pgrads, RLX_EUNSUP, "mlp bwd: input-gradient-only mode needs in_dim > 32");
     if (d.ln_first) { pLN = cur; cur += (size_t)l1_grid * 2 * o0.out; }
-    int rc1 = launch_l1<true>(x, params + o0.W, params + o0.b, o0.g >= 0 ? params + o0.g : nullptr,
-                              o0.be >= 0 ? params + o0.be : nullptr, acts[0], pLN, M, o0.in, o0.out, d.act,
-                              d.ln_first ? 1 : 0, l1_grid, st);
+    // One hidden layer: acts[0] holds dZ_last, i.e. act' is applied already (the head kernel's) -- k_l1<bwd> would apply it a second
+    // time.  Only LayerNorm' is left to do; without LayerNorm acts[0] is dZ0 as it stands.
+    const bool dz_in = d.n_hidden == 1;
+    int rc1 = (dz_in && !d.ln_first) ? RLX_OK
+                                     : launch_l1<true>(x, params + o0.W, params + o0.b, o0.g >= 0 ? params + o0.g : nullptr,
+                                                       o0.be >= 0 ? params + o0.be : nullptr, acts[0], pLN, M, o0.in, o0.out,
+                                                       dz_in ? RLX_ACT_NONE : d.act, d.ln_first ? 1 : 0, l1_grid, st);
     if (rc1) return rc1;
     if (d.ln_first) {
       tab.seg[tab.n++] = ReduceSeg{pLN, grads + o0.g, (int64_t)o0.out, (int64_t)2 * o0.out, l1_grid, 0, 1.f, 0.f, 1};

@@ -15,6 +15,10 @@ constexpr float LOG_2PI = 1.8378770664093453f;
 constexpr float HALF_LOG_2PIE = 1.4189385332046727f;  // 0.5 * log(2*pi*e)
 constexpr int HEAD_ROWS = 64;
 
+// row stride of gathered observation rows of width O: wide rows (O > 32: the GEMM first layer, 16-byte row loads) are zero padded to a
+// multiple of 4 (gae.hip gathers the next-value rows the same way, rlx_mlp_fwd_f32 re-pitches its input)
+static inline int row_pitch(int O) { return (O > 32 && O % 4 != 0) ? ((O + 3) & ~3) : O; }
+
 // ---------------------------------------------------------------------------------------
 // K5: gather the minibatch rows (flattened index i = t*N + n, ppo.py:180-184) into dense
 // [mb, O] / [mb, A] / [mb, 3] buffers (coalesced writes; reads are 68-B / 24-B row pieces)
@@ -26,27 +30,28 @@ __global__ __launch_bounds__(256) void k_gather(const float* __restrict__ states
                                                 float* __restrict__ mb_x, float* __restrict__ mb_a,
                                                 float* __restrict__ aux, const int32_t* __restrict__ valid_rows,
                                                 int64_t mb, int O, int A, const float* __restrict__ cstates,
-                                                float* __restrict__ mb_xc, int Oc) {
+                                                float* __restrict__ mb_xc, int Oc, int ldx, int ldxc) {
   // cstates (optional, [B, Oc]): the critic's own observation rows -- an env with critic_observation_indices !=
   // policy_observation_indices (ppo/flax/critic.py:12,24 vs policy.py:13,33): the same rows idx[] gathered into mb_xc
+  // ldx / ldxc: row strides of mb_x / mb_xc (>= O / Oc; the columns past the width are written as zeros)
   // valid_rows (device, optional): rows [*valid_rows, mb) are PADDING of a rank-local minibatch (data-parallel update):
   // they gather row 0 of the rollout (finite values; the head/loss kernels give them zero weight).
   // The advantage statistics of ppo.py:199-200 are NOT accumulated here: k_mb_adv_sums (dist.hip) produces them for all
   // minibatches of an update call at once, one workgroup per minibatch in a fixed order -- reproducible bit for bit
   // (no floating-point atomics) and off the per-update critical path.
   const int64_t nv = valid_rows ? (int64_t)*valid_rows : mb;
-  const int64_t nx = mb * O, na = mb * A, nxc = cstates ? mb * Oc : 0;
+  const int64_t nx = mb * ldx, na = mb * A, nxc = cstates ? mb * ldxc : 0;
   const int64_t total = nx + na + mb + nxc;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     if (e >= nx + na + mb) {
       const int64_t f = e - nx - na - mb;
-      const int64_t r = f / Oc;
-      const int d = (int)(f - r * Oc);
-      mb_xc[f] = cstates[(int64_t)(r < nv ? idx[r] : 0) * Oc + d];
+      const int64_t r = f / ldxc;
+      const int d = (int)(f - r * ldxc);
+      mb_xc[f] = d < Oc ? cstates[(int64_t)(r < nv ? idx[r] : 0) * Oc + d] : 0.f;
     } else if (e < nx) {
-      const int64_t r = e / O;
-      const int d = (int)(e - r * O);
-      mb_x[e] = states[(int64_t)(r < nv ? idx[r] : 0) * O + d];
+      const int64_t r = e / ldx;
+      const int d = (int)(e - r * ldx);
+      mb_x[e] = d < O ? states[(int64_t)(r < nv ? idx[r] : 0) * O + d] : 0.f;
     } else if (e < nx + na) {
       const int64_t f = e - nx;
       const int64_t r = f / A;
@@ -96,12 +101,14 @@ __global__ __launch_bounds__(256) void k_pack_rows(const float* __restrict__ sta
 __global__ __launch_bounds__(256) void k_gather_rec(const float4* __restrict__ rec, const int32_t* __restrict__ idx,
                                                     float* __restrict__ mb_x, float* __restrict__ mb_a, float* __restrict__ aux,
                                                     const int32_t* __restrict__ valid_rows, int64_t mb, int O, int A, int lg4,
-                                                    int grp_rows) {
+                                                    int grp_rows, int ldx) {
   const int64_t total = mb << lg4;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t r = e >> lg4;
     const int q = (int)(e & ((1 << lg4) - 1));
     if (4 * q >= O + A + 3) continue;
+    if (q == 0)
+      for (int p = O; p < ldx; ++p) mb_x[r * ldx + p] = 0.f;      // (a padded row stride: at most three columns)
     bool live = true;
     if (valid_rows) {
       if (grp_rows > 0) {
@@ -117,7 +124,7 @@ __global__ __launch_bounds__(256) void k_gather_rec(const float4* __restrict__ r
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int p = 4 * q + j;
-      if (p < O) mb_x[r * O + p] = v[j];
+      if (p < O) mb_x[r * ldx + p] = v[j];
       else if (p < O + A) mb_a[r * A + (p - O)] = v[j];
       else if (p < O + A + 3) aux[r * 3 + (p - O - A)] = v[j];
     }
@@ -386,21 +393,22 @@ static int launch_gather(rlx_ctx* ctx, const float* states, const float* actions
                          const float* cstates = nullptr, int Oc = 0, int grp_rows = 0) {
   // grp_rows > 0 (record source only): mb = several updates of grp_rows rows, valid_rows = their counts
   if (!s.mb_xc) cstates = nullptr;
+  const int ldx = s.ldx > 0 ? s.ldx : O, ldxc = s.ldxc > 0 ? s.ldxc : Oc;
   if (s.rec && !cstates) {
     const int64_t total = mb << s.rec_lg4;
     int grid = div_up(total, 256);
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(k_gather_rec, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float4*>(s.rec), idx, s.mb_x, s.mb_a,
-                       s.aux, valid_rows, mb, O, A_act, s.rec_lg4, grp_rows);
+                       s.aux, valid_rows, mb, O, A_act, s.rec_lg4, grp_rows, ldx);
     RLX_LAUNCH_CHECK();
     if (stats) return dist_adv_sums(advantages, idx, valid_rows, 1, (int)mb, (int)mb, stats, st);
     return RLX_OK;
   }
-  const int64_t total = mb * (O + A_act + 1 + (cstates ? Oc : 0));
+  const int64_t total = mb * (ldx + A_act + 1 + (cstates ? ldxc : 0));
   int grid = div_up(total, 256);
   if (grid > 2048) grid = 2048;
   hipLaunchKernelGGL(k_gather, dim3(grid), dim3(256), 0, st, states, actions, log_probs, returns, advantages, idx, s.mb_x,
-                     s.mb_a, s.aux, valid_rows, mb, O, A_act, cstates, s.mb_xc, Oc);
+                     s.mb_a, s.aux, valid_rows, mb, O, A_act, cstates, s.mb_xc, Oc, ldx, ldxc);
   RLX_LAUNCH_CHECK();
   if (stats) return dist_adv_sums(advantages, idx, valid_rows, 1, (int)mb, (int)mb, stats, st);
   return RLX_OK;
@@ -430,16 +438,18 @@ static int pack_rollout_rows(rlx_ctx* ctx, const float* states, const float* act
 static int mb_scratch(rlx_ctx* ctx, const rlx_mlp_desc& pd, const rlx_mlp_desc& cd, int64_t mb, MbScratch* s,
                       bool critic_rows = false) {
   const int O = pd.in_dim, A = pd.out_dim;
-  s->mb_x = (float*)scratch(ctx, SL_MB_X, (size_t)mb * (O + A) * sizeof(float));
+  s->ldx = row_pitch(O);
+  s->ldxc = row_pitch(cd.in_dim);
+  s->mb_x = (float*)scratch(ctx, SL_MB_X, (size_t)mb * (s->ldx + A) * sizeof(float));
   s->mb_xc = nullptr;
   if (critic_rows) {
-    s->mb_xc = (float*)scratch(ctx, SL_MB_XC, (size_t)mb * cd.in_dim * sizeof(float));
+    s->mb_xc = (float*)scratch(ctx, SL_MB_XC, (size_t)mb * s->ldxc * sizeof(float));
     if (!s->mb_xc) return RLX_ENOMEM;
   }
   s->aux = (float*)scratch(ctx, SL_MB_AUX, (size_t)mb * 3 * sizeof(float));
   s->stats = (double*)scratch(ctx, SL_STATS, 64);
   if (!s->mb_x || !s->aux || !s->stats) return RLX_ENOMEM;
-  s->mb_a = s->mb_x + (size_t)mb * O;
+  s->mb_a = s->mb_x + (size_t)mb * s->ldx;
   const int nh = pd.n_hidden > cd.n_hidden ? pd.n_hidden : cd.n_hidden;
   for (int l = 0; l < nh; ++l) {
     int h = 0;
@@ -1589,20 +1599,23 @@ static int launch_head_loss(float* H, const float* W, const float* b, const floa
                             int64_t mb, int K, int A, int PS, float inv_mb, const rlx_ppo_hparams& hp, int act, hipStream_t st,
                             rlx_ctx* prof_ctx = nullptr) {
   const int nb = div_up(mb, HEAD_ROWS);
+  // every refusal in front of the profiler scope: a scope whose events are never stamped leaves prof_end an invalid-handle error
+  const bool discrete = POLICY && hp.discrete_actions;
+  const bool fast = !discrete && A <= 8 && (K == 64 || K == 128 || K == 256);
+  RLX_REQUIRE(!discrete || (A >= 2 && A <= 8), RLX_EUNSUP, "ppo: the Categorical head supports 2..8 actions");
+  const size_t ldsd = ((size_t)HEAD_ROWS * (K + 1) + (size_t)K * A + 2 * (size_t)HEAD_ROWS * A + 2 * A) * sizeof(float);   // LDS-staged forms
+  RLX_REQUIRE(fast || ldsd <= 160 * 1024, RLX_EUNSUP, "ppo head: last hidden layer too wide for the LDS-staged head kernel");
   // algorithmic bytes: H_last in, dZ_last out (in place), the gathered per-row scalars, the per-block partial slabs
   ProfScope prof(s.valid_rows ? nullptr : prof_ctx, PK_HEAD_LOSS, 0.0, st,
                  4.0 * ((double)mb * (2 * K + A + 3) + (double)nb * PS + (double)K * A), mb, K, A, PROF_ENGINE_HBM);
-  if (POLICY && hp.discrete_actions) {
-    RLX_REQUIRE(A >= 2 && A <= 8, RLX_EUNSUP, "ppo: the Categorical head supports 2..8 actions");
-    const size_t ldsd = ((size_t)HEAD_ROWS * (K + 1) + (size_t)K * A + 2 * (size_t)HEAD_ROWS * A + 2 * A) * sizeof(float);
-    RLX_REQUIRE(ldsd <= 160 * 1024, RLX_EUNSUP, "ppo head: last hidden layer too wide for the LDS-staged head kernel");
-    hipLaunchKernelGGL((k_head_loss<POLICY, true>), dim3(nb), dim3(256), ldsd, st, H, W, b, logstd, s.mb_a, s.aux, s.stats,
-                       s.head_part, metrics, mb, K, A, PS, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, act,
-                       s.valid_rows);
+  if (discrete) {
+    RLX_PLAUNCH((k_head_loss<POLICY, true>), dim3(nb), dim3(256), ldsd, st, H, W, b, logstd, s.mb_a, s.aux, s.stats,
+                s.head_part, metrics, mb, K, A, PS, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, act,
+                s.valid_rows);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
   }
-  if (A <= 8 && (K == 64 || K == 128 || K == 256)) {
+  if (fast) {
     const int NP = 256 / K > 0 ? 256 / K : 1;
     const size_t lds = ((size_t)K * 8 + 2 * HEAD_ROWS * 8 + (size_t)HEAD_ROWS * (K + 1) + (size_t)NP * K * 8 + 16) * sizeof(float);
 #define RLX_HL_FAST(KQV)                                                                                        \
@@ -1624,10 +1637,9 @@ static int launch_head_loss(float* H, const float* W, const float* b, const floa
     RLX_LAUNCH_CHECK();
     return RLX_OK;
   }
-  const size_t lds = ((size_t)HEAD_ROWS * (K + 1) + (size_t)K * A + 2 * (size_t)HEAD_ROWS * A + 2 * A) * sizeof(float);
-  RLX_REQUIRE(lds <= 160 * 1024, RLX_EUNSUP, "ppo head: last hidden layer too wide for the LDS-staged head kernel");
-  hipLaunchKernelGGL(k_head_loss<POLICY>, dim3(nb), dim3(256), lds, st, H, W, b, logstd, s.mb_a, s.aux, s.stats, s.head_part,
-                     metrics, mb, K, A, PS, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, act, s.valid_rows);
+  // (launched inside the profiler scope like the fast form)
+  RLX_PLAUNCH((k_head_loss<POLICY>), dim3(nb), dim3(256), ldsd, st, H, W, b, logstd, s.mb_a, s.aux, s.stats, s.head_part,
+              metrics, mb, K, A, PS, inv_mb, hp.clip_range, hp.entropy_coef, hp.critic_coef, act, s.valid_rows);
   RLX_LAUNCH_CHECK();
   return RLX_OK;
 }
@@ -1652,6 +1664,8 @@ static int net_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const float* params,
   if (rc) return rc;
   struct BxScope { rlx_ctx* c; ~BxScope() { if (!c->bx_keep[c->bank]) bx_release(c); } } bx_scope{ctx};
   const float* x_in = (!POLICY && s.mb_xc) ? s.mb_xc : s.mb_x;   // the critic's own observation columns, if it has them
+  const int ld_in = (!POLICY && s.mb_xc) ? s.ldxc : s.ldx;
+  const int ldx = ld_in > d.in_dim ? ld_in : 0;                   // padded row stride of wide observation rows (row_pitch), 0: in_dim
   const int K = L.head.in, A = L.head.out;
   const int PS = K * A + 2 * A + 8;
   int nb = div_up(mb, HEAD_ROWS);
@@ -1689,7 +1703,7 @@ static int net_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const float* params,
     ctx->l1_hand_req = (float*)scratch(ctx, SL_LN_P, (size_t)2 * mb * sizeof(float));
     if (!ctx->l1_hand_req) return RLX_ENOMEM;
   }
-  rc = mlp_trunk_fwd(ctx, d, L, params, x_in, s.acts, mb, st, 0, false, nullptr, tail ? d.n_hidden - 1 : -1);
+  rc = mlp_trunk_fwd(ctx, d, L, params, x_in, s.acts, mb, st, ldx, false, nullptr, tail ? d.n_hidden - 1 : -1);
   if (rc) return rc;
   if (ev_after_fwd) RLX_HIP_TRY(hipEventRecord(ev_after_fwd, st));
   if (tail) {
@@ -1722,7 +1736,8 @@ static int net_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& d, const float* params,
   GradScaleScope gscope(ctx, bx_grad_scale(mb_global));   // dZ ~ 1 / mb_global
   TrunkOpts topt;
   topt.dz_below_last = dz2;
-  return mlp_trunk_bwd(ctx, d, L, params, x_in, s.acts, grads, mb, extra, ne, sumsq, n_sumsq, st, tail ? &topt : nullptr);
+  topt.ldx = ldx;
+  return mlp_trunk_bwd(ctx, d, L, params, x_in, s.acts, grads, mb, extra, ne, sumsq, n_sumsq, st, (tail || ldx) ? &topt : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2069,8 +2084,8 @@ static int minibatch_core(rlx_ctx* ctx, const rlx_mlp_desc& pd, const float* ppa
       if (rc) return rc;
       if (!prezeroed_stats && ctx->gemm_bx && phase != 0 && phase != 5) {
         // single-minibatch entries: max |x| of the rows just gathered (the whole-update calls take it over their rollout once)
-        rc = x_max_update(ctx, s.mb_x, (int64_t)mb_local * O, 0, st, &ctx->xmax_slot[0]);
-        if (!rc && s.mb_xc) rc = x_max_update(ctx, s.mb_xc, (int64_t)mb_local * cd.in_dim, 1, st, &ctx->xmax_slot[1]);
+        rc = x_max_update(ctx, s.mb_x, (int64_t)mb_local * s.ldx, 0, st, &ctx->xmax_slot[0]);      // (pad columns are zeros)
+        if (!rc && s.mb_xc) rc = x_max_update(ctx, s.mb_xc, (int64_t)mb_local * s.ldxc, 1, st, &ctx->xmax_slot[1]);
         if (rc) return rc;
       }
     }
@@ -2339,7 +2354,7 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
     // running.  The two chains drift out of phase and one net's bandwidth-bound kernels (first layer, head/loss,
     // slab reduction, Adam) run under the other net's MFMA kernels instead of next to their twins.  Same kernels, same
     // inputs, same order per net: the results are those of the joined schedule bit for bit.
-    const int O = pdesc->in_dim, A = pdesc->out_dim;
+    const int O = pdesc->in_dim, A = pdesc->out_dim, LDX = row_pitch(O);   // LDX: row stride of the gathered observation rows
     MbScratch sb[2];
     for (int b = 0; b < 2; ++b) {
       ctx->bank = b;
@@ -2393,10 +2408,10 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
         MbScratch grp = sb[0];
         if (G > 1) {
           const int64_t rows = (int64_t)G * minibatch_size;
-          grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (O + A) * sizeof(float));
+          grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A) * sizeof(float));
           grp.aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
           if (!grp.mb_x || !grp.aux) return RLX_ENOMEM;
-          grp.mb_a = grp.mb_x + (size_t)rows * O;
+          grp.mb_a = grp.mb_x + (size_t)rows * LDX;
           grp.mb_xc = nullptr;
         }
         for (int u = 0; u < n_upd; ++u) {
@@ -2404,13 +2419,13 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
           const int j = u % G;
           if (j == 0) {
             const int g = n_upd - u < G ? n_upd - u : G;
-            grp.mb_a = grp.mb_x + (size_t)g * minibatch_size * O;                 // (a shorter last group: [g*mb, O] then [g*mb, A])
+            grp.mb_a = grp.mb_x + (size_t)g * minibatch_size * LDX;                 // (a shorter last group: [g*mb, O] then [g*mb, A])
             r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, grp,
                               nullptr, nullptr, (int64_t)g * minibatch_size, O, A, s0);
             if (r) return r;
           }
           MbScratch sp = sb[0], sc = sb[1];
-          sp.mb_x = grp.mb_x + (size_t)j * minibatch_size * O;
+          sp.mb_x = grp.mb_x + (size_t)j * minibatch_size * LDX;
           sp.mb_a = grp.mb_a + (size_t)j * minibatch_size * A;
           sp.aux = grp.aux + (size_t)j * minibatch_size * 3;
           sp.stats = sc.stats = stats_all + (int64_t)u * 4;
@@ -2446,7 +2461,7 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
         const int64_t rows = (int64_t)G * minibatch_size;
         for (int b = 0; b < 2; ++b) {
           ctx->bank = b;
-          grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (O + A_act) * sizeof(float));
+          grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
           grp[b].aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
           ctx->bank = 0;
           if (!grp[b].mb_x || !grp[b].aux) return RLX_ENOMEM;
@@ -2465,7 +2480,7 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
           if (gi >= 2 && !own_rows) RLX_HIP_TRY(hipStreamWaitEvent(s0, ctx->ev_cdone[par], 0));   // critic done with the rows of group gi - 2
           if (G > 1) {
             const int g = n_upd - u < G ? n_upd - u : G;
-            grp[par].mb_a = grp[par].mb_x + (size_t)g * minibatch_size * O;
+            grp[par].mb_a = grp[par].mb_x + (size_t)g * minibatch_size * LDX;
             r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, grp[par],
                               nullptr, nullptr, (int64_t)g * minibatch_size, O, A_act, s0);
           } else {
@@ -2477,7 +2492,7 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
         }
         MbScratch rows_u = sb[par];           // where this update's rows are
         if (G > 1) {
-          rows_u.mb_x = grp[par].mb_x + (size_t)j * minibatch_size * O;
+          rows_u.mb_x = grp[par].mb_x + (size_t)j * minibatch_size * LDX;
           rows_u.mb_a = grp[par].mb_a + (size_t)j * minibatch_size * A_act;
           rows_u.aux = grp[par].aux + (size_t)j * minibatch_size * 3;
           rows_u.mb_xc = nullptr;
@@ -2696,7 +2711,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     rc = dist_sum_dropped(ctx, stats_all, n_upd, st);
     if (rc) return rc;
   }
-  const int O = pdesc->in_dim, A = pdesc->out_dim, A_act = hp->discrete_actions ? 1 : A;
+  const int O = pdesc->in_dim, A = pdesc->out_dim, A_act = hp->discrete_actions ? 1 : A, LDX = row_pitch(O);
   MbScratch sb[2];
   for (int b = 0; b < 2; ++b) {
     ctx->bank = b;
@@ -2717,7 +2732,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     MbScratch grp = sb[0];
     if (G > 1) {
       const int64_t rows = (int64_t)G * cap;
-      grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (O + A_act) * sizeof(float));
+      grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
       grp.aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
       if (!grp.mb_x || !grp.aux) return RLX_ENOMEM;
       grp.mb_xc = nullptr;
@@ -2728,13 +2743,13 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
       const int j = u % G;
       if (j == 0) {
         const int g = n_upd - u < G ? n_upd - u : G;
-        grp.mb_a = grp.mb_x + (size_t)g * cap * O;
+        grp.mb_a = grp.mb_x + (size_t)g * cap * LDX;
         rc = launch_gather(ctx, states, actions, log_probs, returns, advantages, lidx + (int64_t)u * cap, grp, nullptr, cnt_u,
                            (int64_t)g * cap, O, A_act, st, nullptr, 0, G > 1 ? cap : 0);
         if (rc) return rc;
       }
       MbScratch sp = sb[0], sc = sb[1];
-      sp.mb_x = grp.mb_x + (size_t)j * cap * O;
+      sp.mb_x = grp.mb_x + (size_t)j * cap * LDX;
       sp.mb_a = grp.mb_a + (size_t)j * cap * A_act;
       sp.aux = grp.aux + (size_t)j * cap * 3;
       sp.stats = sc.stats = stats_all + (int64_t)u * 4;
@@ -2774,7 +2789,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     const int64_t rows = (int64_t)G * cap;
     for (int b = 0; b < 2; ++b) {
       ctx->bank = b;
-      grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (O + A_act) * sizeof(float));
+      grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
       grp[b].aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
       ctx->bank = 0;
       if (!grp[b].mb_x || !grp[b].aux) return RLX_ENOMEM;
@@ -2792,7 +2807,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
       if (gi >= 2) RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_cdone[par], 0));   // the critic is done with the rows of group gi - 2
       if (G > 1) {
         const int g = n_upd - u < G ? n_upd - u : G;
-        grp[par].mb_a = grp[par].mb_x + (size_t)g * cap * O;
+        grp[par].mb_a = grp[par].mb_x + (size_t)g * cap * LDX;
         rc = launch_gather(ctx, states, actions, log_probs, returns, advantages, lidx + (int64_t)u * cap, grp[par], nullptr, cnt_u,
                            (int64_t)g * cap, O, A_act, st, nullptr, 0, cap);
       } else {
@@ -2804,7 +2819,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     }
     MbScratch rows_u = sb[par];               // where this update's rows are
     if (G > 1) {
-      rows_u.mb_x = grp[par].mb_x + (size_t)j * cap * O;
+      rows_u.mb_x = grp[par].mb_x + (size_t)j * cap * LDX;
       rows_u.mb_a = grp[par].mb_a + (size_t)j * cap * A_act;
       rows_u.aux = grp[par].aux + (size_t)j * cap * 3;
       rows_u.mb_xc = nullptr;

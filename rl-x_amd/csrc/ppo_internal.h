@@ -5,9 +5,13 @@
 namespace rlx {
 
 struct MbScratch {
-  float* mb_x;     // [mb, O]  gathered observations
+  float* mb_x;     // [mb, O]  gathered observations (row stride ldx when that is set)
   float* mb_xc = nullptr;   // [mb, Oc] gathered CRITIC observations when the critic reads its own observation columns
                             // (rlx_ppo_hparams.critic_states; nullptr: the critic reads mb_x like the policy)
+  int ldx = 0, ldxc = 0;    // row strides of mb_x / mb_xc (0: the observation width).  Observations wider than 32 go through the GEMM first
+                            // layer, whose 16-byte row loads need a stride that is a multiple of 4: ppo.hip's mb_scratch gathers such
+                            // rows zero padded.  ppo_mb_scratch (the recurrent variants) leaves both at 0: their encoders read mb_x at
+                            // stride O, so their MLP critic still refuses a wide width that is no multiple of 4
   float* mb_a;     // [mb, A]  gathered actions
   float* aux;      // [mb, 3]  log_prob, return, advantage
   double* stats;   // {sum adv, sum adv^2, count}

@@ -323,3 +323,280 @@ def check_engines(rows, expected):
     bad = {k: (sorted(v), expected.get(k)) for k, v in seen.items() if v != {expected.get(k)}}
     assert not bad, bad
     assert set(expected) <= set(seen), sorted(set(expected) - set(seen))
+
+
+# ------------------------------------------------- PPO minibatch pass (ppo.hip, l1fused.hip, gemm_bx.hip, mlp.hip: net_fwd_bwd / twin_fwd_bwd)
+ACT_TANH, ACT_ELU, ACT_RELU = 0, 1, 2          # rlx_hip.h
+ENGINE_EXACT, ENGINE_SPLIT, ENGINE_HBM = 0, 1, 2   # profiler rows: exact-fp32 GEMM, split-operand fp16 pipe, bandwidth-bound launch (common.h)
+HEAD_ROWS, T32_ROWS, TL_K3 = 64, 32, 128       # ppo.hip
+LF_PFX = 2                                     # l1fused.hip RLX_LF_PFX
+PPO_DEFAULTS = dict(ppo_twin=-1, ppo_tail=-1, l12_fused=1, dw_merge=1, dw_recompute=1, gemm_bx=1, l1fwd_mfma=1, disable_l1fused=0)
+
+
+def ppo_opts(options=None):
+    o = dict(PPO_DEFAULTS)
+    o.update(options or {})
+    assert set(o) == set(PPO_DEFAULTS), sorted(set(o) - set(PPO_DEFAULTS))
+    return o
+
+
+def row_pitch(O):
+    """ppo.hip row_pitch: the stride of gathered observation rows -- wide rows are zero padded to a multiple of 4"""
+    return pad4(O) if O > 32 and O % 4 else O
+
+
+def mlp_check_desc(O, hidden, A, act, ln_first):
+    """mlp.hip check_desc -> None, or the message of the RLX_EUNSUP / RLX_EINVAL it raises"""
+    if not 1 <= len(hidden) <= 3:
+        return "mlp: n_hidden must be 1..3"
+    if not 1 <= O <= 8192:
+        return "mlp: in_dim must be 1..8192"
+    if not (O <= 32 or not ln_first or len(hidden) >= 2):
+        return "mlp: LayerNorm after a wide first layer needs at least two hidden layers"
+    if not (hidden[0] % 64 == 0 and 64 <= hidden[0] <= 512):
+        return "mlp: hidden[0] must be a multiple of 64 in [64, 512]"
+    if any(h % 4 or h < 4 for h in hidden[1:]):
+        return "mlp: hidden dims must be multiples of 4"
+    if not 1 <= A <= 64:
+        return "mlp: out_dim must be 1..64"
+    if act not in (ACT_TANH, ACT_ELU, ACT_RELU):
+        return "mlp: unknown activation"
+    return None
+
+
+def mlp_blocks(O, hidden, A, ln_first, has_logstd):
+    """the flat parameter layout (rlx_hip.h; make_layout) -> ([(name, offset, length)], n_params)"""
+    out, off, d = [], 0, O
+    for l, h in enumerate(hidden):
+        blocks = [(f"W{l}", d * h), (f"b{l}", h)] + ([(f"ln_scale{l}", h), (f"ln_bias{l}", h)] if ln_first and l == 0 else [])
+        for name, n in blocks:
+            out.append((name, off, n))
+            off += n
+        d = h
+    for name, n in (("Wh", d * A), ("bh", A)) + ((("logstd", A),) if has_logstd else ()):
+        out.append((name, off, n))
+        off += n
+    return out, off
+
+
+def l1fwd_mfma_supported(O, hidden, act, ln_first):
+    return hidden[0] == 512 and act == ACT_ELU and ln_first and O <= 32
+
+
+def l12fwd_supported(O, hidden, act, ln_first):
+    return l1fwd_mfma_supported(O, hidden, act, ln_first) and len(hidden) >= 2 and hidden[1] in (256, 512)
+
+
+def l1fused_supported(O, hidden, act, ln_first):
+    combo = (hidden[0] == 512 and act == ACT_ELU and ln_first) or (hidden[0] == 256 and act in (ACT_TANH, ACT_RELU) and not ln_first)
+    return combo and len(hidden) >= 2 and O <= 32 and hidden[1] % 32 == 0 and hidden[1] <= 512
+
+
+def bx_mlp_images(O, hidden, act, ln_first, on):
+    """gemm_bx.hip bx_prepare_mlp(with_bwd): {(layer, transposed)} of the split weight images a pass of `on` (gemm_bx and >= SPLIT_ROWS
+    rows) registers: both images of every hidden layer l >= 1 with aligned widths, the first layer's forward image for the fused
+    first-layer backward"""
+    have = set()
+    if not on:
+        return have
+    for l in range(1, len(hidden)):
+        if hidden[l - 1] % 4 == 0 and hidden[l] % 4 == 0:
+            have |= {(l, 0), (l, 1)}
+    if have and O <= 32 and l1fused_supported(O, hidden, act, ln_first):
+        have.add((0, 0))
+    return have
+
+
+def l1fused_bx(O, hidden, act, ln_first, have):
+    """l1fused.hip l1fused_bx_images: the fused first-layer backward runs its main product on the split engine"""
+    N2 = hidden[1]
+    return N2 % 128 == 0 and N2 % (16 * LF_PFX) == 0 and (1, 1) in have and (0, 0) in have
+
+
+def tail_rows(hidden, act, mb, opts):
+    """ppo.hip tail_rows: rows per workgroup of the tail form a minibatch takes"""
+    can32 = hidden[1] == 256 and act == ACT_ELU and mb % T32_ROWS == 0
+    want32 = opts["ppo_tail"] == 2 or (opts["ppo_tail"] < 0 and (mb <= 8192 or mb > 16384))
+    return T32_ROWS if can32 and want32 else HEAD_ROWS
+
+
+def tail_shape_ok(hidden, A, mb, opts):
+    """ppo.hip tail_shape_ok (Gaussian policy or critic): last hidden layer + head + loss + both input gradients in one launch"""
+    return bool(opts["ppo_tail"] and opts["gemm_bx"] and len(hidden) == 3 and hidden[2] == TL_K3 and hidden[1] % G_BN == 0 and
+                hidden[1] <= 512 and A <= 8 and mb >= 4096 and mb % HEAD_ROWS == 0)
+
+
+def head_kernel(hidden, A, tail):
+    """which kernel evaluates head and loss of one network: inside the tail, k_head_loss_fast<K / 4> or the LDS-staged k_head_loss"""
+    K = hidden[-1]
+    return "tail" if tail else f"fast{K}" if A <= 8 and K in (64, 128, 256) else "generic"
+
+
+def dw_merge_ok(hidden, mb, opts):
+    on = bool(opts["gemm_bx"])
+    return bool(opts["dw_merge"]) and len(hidden) == 3 and bx_dw_usable(on, mb, hidden[1], hidden[1], hidden[2]) and \
+        bx_dw_usable(on, mb, hidden[0], hidden[0], hidden[1])
+
+
+def twin_shapes_ok(O, hidden, A, act, ln_first, mb, opts):
+    """ppo.hip twin_shapes_ok for one process, a Gaussian policy and a critic of the policy's trunk reading the policy's rows through
+    rlx_ppo_minibatch_fwd_bwd_f32 (which takes the twin pass only at ppo_twin = 1; at -1 the whole-update entries decide by size:
+    twin_default)"""
+    if opts["ppo_twin"] == 0 or (opts["ppo_twin"] < 0 and mb > 16384):
+        return False
+    if not opts["gemm_bx"] or opts["disable_l1fused"] or not opts["l1fwd_mfma"]:
+        return False
+    if len(hidden) < 2 or A > 8 or any(h % 4 for h in hidden[1:]) or hidden[-1] not in (64, 128, 256):
+        return False
+    if mb < SPLIT_ROWS or not l1fwd_mfma_supported(O, hidden, act, ln_first) or not l1fused_supported(O, hidden, act, ln_first):
+        return False
+    return all(bx_dw_usable(True, mb, hidden[l - 1], hidden[l - 1], hidden[l]) for l in range(1, len(hidden)))
+
+
+def twin_default(O, hidden, A, act, ln_first, mb, gather_group_rows=524288, gather_records=True):
+    """what rlx_ppo_update_f32 picks at ppo_twin = -1 on one GPU: twin launches from 6144 (grouped gathers below) to 16384 rows"""
+    o = ppo_opts()
+    if mb < 6144 and gather_records and gather_group_rows > mb and O + A + 3 <= 128:
+        return False
+    return twin_shapes_ok(O, hidden, A, act, ln_first, mb, o)
+
+
+def ppo_refusal(O, hidden, A, act, ln_first, mb, repitch=True):
+    """(code, message) of the error the minibatch pass answers a shape with, None when it runs.  repitch: the pass gathers wide rows
+    at row_pitch(O) (without it a wide O that is no multiple of 4 is refused by mlp_trunk_fwd)"""
+    msg = mlp_check_desc(O, hidden, A, act, ln_first) or mlp_check_desc(O, hidden, 1, act, ln_first)
+    if msg:
+        return (-1 if "unknown activation" in msg else -4), msg
+    if O > 32 and (O if not repitch else row_pitch(O)) % 4:
+        return -4, "mlp: wide inputs need a row stride that is a multiple of 4"
+    for out in (A, 1):                  # launch_head_loss: the LDS-staged kernel holds 64 rows of the last hidden layer and the head
+        K = hidden[-1]
+        if head_kernel(hidden, out, tail_shape_ok(hidden, out, mb, ppo_opts())) == "generic" and \
+                (HEAD_ROWS * (K + 1) + K * out + 2 * HEAD_ROWS * out + 2 * out) * 4 > 160 * 1024:
+            return -4, "ppo head: last hidden layer too wide for the LDS-staged head kernel"
+    return None
+
+
+def _net_rows(O, hidden, A, act, ln_first, mb, opts, policy):
+    """net_fwd_bwd of ONE network -> (paths dict, [(kernel, engine, M, N, K)] one entry per launch)"""
+    nh, on = len(hidden), bool(opts["gemm_bx"]) and mb >= SPLIT_ROWS
+    have = bx_mlp_images(O, hidden, act, ln_first, on)
+    tail = tail_shape_ok(hidden, A, mb, opts) and {(2, 0), (2, 1)} <= have
+    wide, rows = O > 32, []
+    nl = nh - 1 if tail else nh
+    # ---- forward (mlp_trunk_fwd)
+    l12 = bool(opts["l12_fused"]) and not wide and nl >= 2 and mb >= SPLIT_ROWS and l12fwd_supported(O, hidden, act, ln_first) and \
+        {(0, 0), (1, 0)} <= have
+    if l12:
+        first, l_next = "l12fwd", 2
+        rows.append(("k_l12fwd", ENGINE_SPLIT, mb, hidden[1], 512))
+    elif not wide:
+        l_next = 1
+        if opts["l1fwd_mfma"] and mb >= 1024 and l1fwd_mfma_supported(O, hidden, act, ln_first):
+            first = "l1fwd_mfma"
+            rows.append(("k_l1fwd_mfma", ENGINE_HBM, mb, 512, 0))
+        else:
+            first = "l1"                                 # k_l1: no profiler row
+    else:
+        first, l_next = "wide_ln" if ln_first else "wide", 1
+        rows.append(("k_gemm_fwd", ENGINE_EXACT, mb, hidden[0], O))      # (no image of a wide first layer)
+    for l in range(l_next, nl):
+        rows.append(("k_gemm_fwd", ENGINE_SPLIT if (l, 0) in have else ENGINE_EXACT, mb, hidden[l], hidden[l - 1]))
+    # ---- head and loss
+    head = head_kernel(hidden, A, tail)
+    rows.append(("k_tail", ENGINE_SPLIT, mb, TL_K3, hidden[1]) if tail else ("k_head_loss", ENGINE_HBM, mb, hidden[-1], A))
+    # ---- backward (mlp_trunk_bwd)
+    fuse_l1 = not wide and l1fused_supported(O, hidden, act, ln_first) and not opts["disable_l1fused"]
+    merge = tail and dw_merge_ok(hidden, mb, opts)
+    ldx = row_pitch(O)
+    merge2 = bool(opts["dw_merge"]) and nh == 2 and wide and not ln_first and not fuse_l1 and (1, 1) in have and \
+        bx_dw_usable(on, mb, hidden[0], hidden[0], hidden[1]) and bx_dw_usable(on, mb, O, ldx, hidden[0])
+    l1bwd = ("k_dx_l1bwd", ENGINE_SPLIT if fuse_l1 and l1fused_bx(O, hidden, act, ln_first, have) else ENGINE_EXACT, mb, hidden[0],
+             hidden[1] if nh >= 2 else 0)
+    if merge2:
+        rows.append(("k_gemm_dx", ENGINE_SPLIT, mb, hidden[0], hidden[1]))
+        rows.append(("k_gemm_dw", ENGINE_SPLIT, O + hidden[0], hidden[0] + hidden[1], mb))
+        dw = "merge2"
+    else:
+        if merge and fuse_l1:
+            rows.append(l1bwd)
+        for l in range(nh - 1, 0, -1):
+            d_in, d_out = hidden[l - 1], hidden[l]
+            if merge:
+                if l == 1:
+                    rows.append(("k_gemm_dw", ENGINE_SPLIT, hidden[0] + hidden[1], hidden[1] + hidden[2], mb))
+            else:
+                rows.append(("k_gemm_dw", ENGINE_SPLIT if bx_dw_usable(on, mb, d_in, d_in, d_out) else ENGINE_EXACT, d_in, d_out, mb))
+            if (l == 1 and fuse_l1) or (tail and l == nh - 1):
+                continue
+            rows.append(("k_gemm_dx", ENGINE_SPLIT if (l, 1) in have else ENGINE_EXACT, mb, d_in, d_out))
+        if fuse_l1 and not merge:
+            rows.append(l1bwd)
+        if wide:
+            rows.append(("k_gemm_dw", ENGINE_SPLIT if bx_dw_usable(on, mb, O, ldx, hidden[0]) else ENGINE_EXACT, O, hidden[0], mb))
+        dw = "merged" if merge else "separate"
+    n_params = mlp_blocks(O, hidden, A, ln_first, policy)[1]
+    segs = 2 * nh + (2 if ln_first else 0) + 2 + (4 if policy else 1)
+    rows.append(("k_reduce_segments", ENGINE_HBM, n_params + (3 if policy else 1), segs, 0))
+    no_h1 = bool(opts["dw_recompute"]) and tail and l12 and merge and hidden[0] == 512 and act == ACT_ELU
+    paths = dict(tail=(tail_rows(hidden, act, mb, opts) if tail else 0), first=first, l1bwd="fused" if fuse_l1 else "unfused",
+                 l1bwd_split=fuse_l1 and l1bwd[1] == ENGINE_SPLIT, dw=dw, head=head, h1_stored=not no_h1)
+    return paths, rows
+
+
+def _twin_rows(O, hidden, A, act, ln_first, mb, opts):
+    """twin_fwd_bwd: every launch covers both networks"""
+    nh = len(hidden)
+    have = bx_mlp_images(O, hidden, act, ln_first, True)
+    tail = tail_shape_ok(hidden, A, mb, opts)
+    rows = []
+    l12 = bool(opts["l12_fused"]) and l12fwd_supported(O, hidden, act, ln_first)
+    rows.append(("k_l12fwd", ENGINE_SPLIT, mb, hidden[1], 512) if l12 else ("k_l1fwd_mfma", ENGINE_HBM, mb, 512, 0))
+    for l in range(2 if l12 else 1, nh - 1 if tail else nh):
+        rows.append(("k_gemm_fwd", ENGINE_SPLIT, mb, hidden[l], hidden[l - 1]))
+    if tail:
+        rows.append(("k_tail", ENGINE_SPLIT, mb, TL_K3, hidden[1]))      # (the twin head kernel k_head_loss_pc has no profiler row)
+    merge = bool(opts["dw_merge"]) and tail and nh == 3
+    for l in range(nh - 1, 0, -1):
+        if merge:
+            if l == 1:
+                rows.append(("k_gemm_dw", ENGINE_SPLIT, hidden[0] + hidden[1], hidden[1] + hidden[2], mb))
+        else:
+            rows.append(("k_gemm_dw", ENGINE_SPLIT, hidden[l - 1], hidden[l], mb))
+        if l == 1:
+            break
+        if not (tail and l == nh - 1):
+            rows.append(("k_gemm_dx", ENGINE_SPLIT, mb, hidden[l - 1], hidden[l]))
+    rows.append(("k_dx_l1bwd", ENGINE_SPLIT, mb, hidden[0], hidden[1]))
+    np_, nc_ = mlp_blocks(O, hidden, A, ln_first, True)[1], mlp_blocks(O, hidden, 1, ln_first, False)[1]
+    rows.append(("k_reduce_segments", ENGINE_HBM, np_ + 3 + nc_ + 1, 2 * (2 * nh + (2 if ln_first else 0) + 2) + 5, 0))
+    no_h1 = l12 and bool(opts["dw_recompute"]) and merge and hidden[0] == 512 and act == ACT_ELU
+    paths = dict(tail=(tail_rows(hidden, act, mb, opts) if tail else 0), first="l12fwd" if l12 else "l1fwd_mfma", l1bwd="fused",
+                 l1bwd_split=True, dw="merged" if merge else "separate", head=head_kernel(hidden, A, tail), h1_stored=not no_h1)
+    return paths, rows, have
+
+
+def ppo_pass(O, hidden, A, act, ln_first, mb, options=None):
+    """One rlx_ppo_minibatch_fwd_bwd_f32 call on mb rows (policy [O -> hidden -> A] with logstd, critic of the same trunk) ->
+    dict(twin: the twin pass runs, twin_ok: it is admissible, policy / critic: the paths of each network (tail: 0 / 32 / 64 rows,
+    first: l12fwd / l1fwd_mfma / l1 / wide / wide_ln, l1bwd: fused / unfused, dw: merged / separate / merge2, head: tail / fast64 /
+    fast128 / fast256 / generic), rows: {(kernel, engine, M, N, K): launches} the profiler must show)."""
+    hidden, opts = tuple(hidden), ppo_opts(options)
+    assert ppo_refusal(O, hidden, A, act, ln_first, mb) is None
+    admissible = twin_shapes_ok(O, hidden, A, act, ln_first, mb, dict(opts, ppo_twin=1))
+    twin = False
+    if opts["ppo_twin"] == 1 and admissible:
+        tp, trows, have = _twin_rows(O, hidden, A, act, ln_first, mb, opts)
+        # twin_images: both networks need every image of the pass, the fused first-layer backward's included
+        twin = l1fused_bx(O, hidden, act, ln_first, have) and all({(l, 0), (l, 1)} <= have for l in range(1, len(hidden)))
+    out = {}
+    if twin:
+        pp = cp = tp
+        launches = trows
+    else:
+        pp, prow = _net_rows(O, hidden, A, act, ln_first, mb, opts, True)
+        cp, crow = _net_rows(O, hidden, 1, act, ln_first, mb, opts, False)
+        launches = prow + crow
+    for r in launches:
+        out[r] = out.get(r, 0) + 1
+    return dict(twin=twin, twin_ok=admissible, policy=pp, critic=cp, rows=out)

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import nets, ppo as oppo, prng, sac as osac
+from ppo_cases import blocks as _blocks, kink_entries as _kink_entries      # (shared with test_gpu_ppo_shapes.py)
 from rlx_amd.hip import PpoHparams, mlp_desc
 
 pytestmark = pytest.mark.gpu
@@ -27,35 +28,6 @@ def _t(a, dev):
 
 def _desc(spec):
     return mlp_desc(spec.in_dim, spec.hidden, spec.out_dim, spec.act, spec.ln_first, spec.has_logstd)
-
-
-def _kink_entries(spec, params, x, tau):
-    """(layer, row, unit, |z| / rms) of every ReLU pre-activation of the batch within tau of zero, relative to the row's RMS
-    pre-activation (float64): a unit within fp32 rounding (a few 1e-7 relative for a 256-term fp32 dot product) of its kink has an
-    UNDEFINED fp32 gradient -- any fp32 evaluation may land on either side."""
-    h, out = x.astype(np.float64), []
-    for li, L in enumerate(spec.layers):
-        z = h @ params[L["W"]:L["W"] + L["in"] * L["out"]].reshape(L["in"], L["out"]) + params[L["b"]:L["b"] + L["out"]]
-        m = np.abs(z) / np.sqrt((z * z).mean(axis=1, keepdims=True))
-        out += [(li, int(i), int(j), float(m[i, j])) for i, j in zip(*np.nonzero(m < tau))]
-        h = np.maximum(z, 0.0)
-    return out
-
-
-def _blocks(spec):
-    """(name, offset, length) of every parameter block of the flat layout."""
-    out = []
-    for li, L in enumerate(spec.layers):
-        out.append((f"W{li}", L["W"], L["in"] * L["out"]))
-        out.append((f"b{li}", L["b"], L["out"]))
-        if "g" in L:
-            out.append((f"ln_scale{li}", L["g"], L["out"]))
-            out.append((f"ln_bias{li}", L["be"], L["out"]))
-    out.append(("Wh", spec.head["W"], spec.head["in"] * spec.head["out"]))
-    out.append(("bh", spec.head["b"], spec.head["out"]))
-    if spec.has_logstd:
-        out.append(("logstd", spec.logstd, spec.out_dim))
-    return out
 
 
 @pytest.mark.parametrize("MB,twin,obs_scale,tail,l12", [(32768, 0, 1.0, 1, 1), (32768, 0, 1.0, 0, 0), (32768, 0, 1.0, 1, 0),
