@@ -172,7 +172,9 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   gathers read two cache lines per sampled row instead of six; bit-identical results; 0: gather from the five arrays).
  *   "gather_group_rows" (524288: in the two-chain schedules of rlx_ppo_update_f32 / rlx_ppo_update_dist_f32 the rows of that many samples -- one epoch at
  *   configs[1] -- are gathered by ONE launch into one of two alternating buffers, and the chains meet once per group instead of once
- *   per update; 0: one gather per update; needs "gather_records").
+ *   per update; needs "gather_records").  0, or at most one minibatch, means one gather per update in the two-chain schedule of
+ *   rlx_ppo_update_f32 ONLY: the twin schedule and both schedules of rlx_ppo_update_dist_f32 have a floor of 32768 rows per gather
+ *   launch, so any value up to 32768 (0 included) still groups 32768 / rows-per-update updates there.
  * Round 7: "tail32_waves" (8 default; 4 or 8, anything else is RLX_EINVAL): waves per 32-row tile of k_tail32_bx, in its single,
  *   twin (grid.y = 2) and valid-rows launches alike.  8 runs the same tile with the same LDS on 512 threads -- four waves per SIMD
  *   instead of two -- with the same arithmetic in the same order: bit-identical results (tests/test_gpu_tail32_waves.py); 4 is

@@ -2223,6 +2223,255 @@ int ppo_critic_fwd_bwd(rlx_ctx* ctx, const rlx_mlp_desc& cd, const float* cparam
   return net_fwd_bwd<false>(ctx, cd, cparams, cgrads, metrics, s, mb, mb_global, hp, sumsq, nsq, st);
 }
 
+// ---------------------------------------------------------------------------------------
+// The whole-update calls (rlx_ppo_update_f32, rlx_ppo_update_dist_f32).  Each entry checks its arguments, makes its index table
+// and advantage statistics, describes the call as an UpdateRun and hands it to one schedule: run_twin or run_two_chains.
+// ---------------------------------------------------------------------------------------
+
+// scope of a whole-update call: the acting nets' weight images go stale with it; the weight images of the two networks persist
+// over its updates (re-emitted by clip + Adam) and are dropped at its end
+struct BxKeep {
+  rlx_ctx* c;
+  explicit BxKeep(rlx_ctx* ctx) : c(ctx) {
+    if (!c) return;
+    c->ro_img.valid = false;
+    if (c->adam_emit && c->gemm_bx) c->bx_keep[0] = c->bx_keep[1] = true;
+  }
+  ~BxKeep() {
+    if (!c) return;
+    c->bx_keep[0] = c->bx_keep[1] = false;
+    bx_release_all(c);
+  }
+};
+
+struct UpdateNet {
+  const rlx_mlp_desc* desc;
+  float *params, *m, *v;
+  float* grads;
+  int64_t n;
+};
+
+struct UpdateRun {
+  rlx_ctx* ctx;
+  UpdateNet p, c;                 // policy, critic
+  const float *states, *actions, *log_probs, *returns, *advantages;
+  const int32_t* idx;             // [n_upd, stride] row indices: the permutation, or this rank's rows padded to the capacity
+  int stride;                     // rows per update in idx and in the row buffers: minibatch_size / the rank's row capacity
+  int mb_global;
+  const int32_t* counts;          // [n_upd] valid rows per update; nullptr: every row is valid
+  bool collective;                // gradients are all-reduced before clip + Adam
+  const float* sched_dev;         // [n_upd, 4] device table of {lr, 1 - b1^step, 1 - b2^step}; nullptr: scalars
+  int n_upd;
+  int64_t step0;                  // optimiser steps taken before this call
+  const float* lr_schedule;
+  const rlx_ppo_hparams* hp;
+  float* metrics_out;
+  double* stats_all;              // [n_upd, 4] advantage statistics
+  float *psq, *csq;               // sum-of-squares partials
+  const MbScratch* sb;            // [2] arenas of scratch bank 0 (policy) and 1 (critic), with the row records when there are any
+  int O, A_act, LDX;              // LDX: row stride of the gathered observation rows
+};
+
+// the arenas of scratch banks 0 and 1 for minibatches of mb rows
+static int mb_scratch_banks(rlx_ctx* ctx, const rlx_mlp_desc& pd, const rlx_mlp_desc& cd, int64_t mb, bool critic_rows,
+                            MbScratch sb[2]) {
+  for (int b = 0; b < 2; ++b) {
+    ctx->bank = b;
+    const int rc = mb_scratch(ctx, pd, cd, mb, &sb[b], critic_rows);
+    ctx->bank = 0;
+    if (rc) return rc;
+  }
+  return RLX_OK;
+}
+
+// the next permutation prefetch may overwrite the index buffers once what `st` holds so far has run
+static int record_perm_free(rlx_ctx* ctx, hipStream_t st) {
+  if (!ctx->ev_perm_free) RLX_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_perm_free, hipEventDisableTiming));
+  RLX_HIP_TRY(hipEventRecord(ctx->ev_perm_free, st));
+  ctx->perm_free_recorded = true;
+  return RLX_OK;
+}
+
+// G: consecutive updates whose rows ONE gather launch fetches (their index ranges are adjacent).  Option "gather_group_rows"
+// gives the rows per launch and needs the record source (`rec`); critic-only observation rows are gathered per update.
+//   floor_32768 (the twin schedule and both data-parallel schedules): at least 32768 rows per launch, whatever the option says
+//     -- 0 does NOT switch grouping off there.  Without records G = 1, except that plain_groups (the local twin schedule, no
+//     valid-row counts) then groups 32768 rows through the five-array gather.
+//   otherwise (the local two-chain schedule): the option as given; at most one update's rows (0 included) means G = 1.
+static int gather_group_updates(const rlx_ctx* ctx, int stride, int n_upd, bool rec, bool critic_rows, bool floor_32768,
+                                bool plain_groups) {
+  if (critic_rows) return 1;
+  int rows = ctx->gather_group_rows;
+  if (floor_32768) {
+    if (!rec && !plain_groups) return 1;
+    if (!rec || ctx->gather_group_rows < 32768) rows = 32768;
+  } else if (!rec || rows <= stride) {
+    return 1;
+  }
+  const int G = rows / stride > 0 ? rows / stride : 1;
+  return n_upd < G ? n_upd : G;
+}
+
+// row buffers of `banks` gather groups of G updates each; G == 1: the banks' own row buffers
+static int group_buffers(const UpdateRun& r, int G, int banks, MbScratch* grp) {
+  rlx_ctx* ctx = r.ctx;
+  const int64_t rows = (int64_t)G * r.stride;
+  for (int b = 0; b < banks; ++b) {
+    grp[b] = r.sb[b];
+    if (G == 1) continue;
+    ctx->bank = b;
+    grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (r.LDX + r.A_act) * sizeof(float));
+    grp[b].aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
+    ctx->bank = 0;
+    if (!grp[b].mb_x || !grp[b].aux) return RLX_ENOMEM;
+    grp[b].mb_xc = nullptr;
+  }
+  return RLX_OK;
+}
+
+// the rows of the g updates from u on into grp: [g * stride, O] then [g * stride, A_act] (a last group may be shorter than G).
+// The critic's own observation rows go along only into a bank's own buffers (G == 1: a group buffer has no mb_xc); the rows per
+// update tell the record gather of a group which count belongs to which row.
+static int gather_group(const UpdateRun& r, int u, int g, int G, MbScratch& grp, hipStream_t st) {
+  grp.mb_a = grp.mb_x + (size_t)g * r.stride * r.LDX;
+  return launch_gather(r.ctx, r.states, r.actions, r.log_probs, r.returns, r.advantages, r.idx + (int64_t)u * r.stride, grp, nullptr,
+                       r.counts ? r.counts + u : nullptr, (int64_t)g * r.stride, r.O, r.A_act, st, r.hp->critic_states,
+                       r.c.desc->in_dim, G > 1 ? r.stride : 0);
+}
+
+// where update j of a gathered group has its rows
+static void group_rows(const UpdateRun& r, const MbScratch& grp, int j, MbScratch* s) {
+  s->mb_x = grp.mb_x + (size_t)j * r.stride * r.LDX;
+  s->mb_a = grp.mb_a + (size_t)j * r.stride * r.A_act;
+  s->aux = grp.aux + (size_t)j * r.stride * 3;
+}
+
+// Policy || critic as twin launches on ONE stream (twin_shapes_ok); the rows of G consecutive updates are gathered by ONE launch
+// (at 4096 rows the gather was 5.7 of the update's 107 us, a dependent launch of its own).  With `collective` the two gradient
+// vectors are one buffer [policy | pad to 16 B | critic] (the caller's layout; the pad is zero): one all-reduce per update.
+static int run_twin(const UpdateRun& r, const TwinImages& tim, hipStream_t st, bool plain_groups) {
+  rlx_ctx* ctx = r.ctx;
+  const rlx_ppo_hparams& hp = *r.hp;
+  const MlpLayout LP = make_layout(*r.p.desc), LC = make_layout(*r.c.desc);
+  const int G = gather_group_updates(ctx, r.stride, r.n_upd, r.sb[0].rec != nullptr, hp.critic_states != nullptr, true, plain_groups);
+  MbScratch grp;
+  int rc = group_buffers(r, G, 1, &grp);
+  if (rc) return rc;
+  for (int u = 0; u < r.n_upd; ++u) {
+    float* met = r.metrics_out + (int64_t)u * 10;
+    const int j = u % G;
+    if (j == 0) {
+      rc = gather_group(r, u, r.n_upd - u < G ? r.n_upd - u : G, G, grp, st);
+      if (rc) return rc;
+    }
+    MbScratch sp = r.sb[0], sc = r.sb[1];
+    group_rows(r, grp, j, &sp);
+    sp.stats = sc.stats = r.stats_all + (int64_t)u * 4;
+    sp.valid_rows = sc.valid_rows = r.counts ? r.counts + u : nullptr;
+    int npb = 0, ncb = 0;
+    rc = twin_fwd_bwd(ctx, *r.p.desc, LP, r.p.params, r.p.grads, *r.c.desc, LC, r.c.params, r.c.grads, tim, met, sp, sc, r.stride,
+                      r.mb_global, hp, r.psq, &npb, &ncb, st);
+    if (rc) return rc;
+    const float* csq = r.psq + npb;
+    if (r.collective) {
+      rc = dist_allreduce(ctx, r.p.grads, (r.c.grads - r.p.grads) + r.c.n, 0, st);   // policy, pad and critic in one
+      if (rc) return rc;
+      rc = launch_sumsq_partials2(r.p.grads, r.p.n, r.psq, &npb, r.c.grads, r.c.n, r.csq, &ncb, st);   // norms of the REDUCED gradients
+      if (rc) return rc;
+      csq = r.csq;
+    }
+    ctx->bank = 0;
+    const BxEmit pe = bx_emit_table(ctx, *r.p.desc, r.p.params);
+    ctx->bank = 1;
+    const BxEmit ce = bx_emit_table(ctx, *r.c.desc, r.c.params);
+    ctx->bank = 0;
+    rc = launch_clip_adam2(r.p.params, r.p.grads, r.p.m, r.p.v, r.p.n, r.psq, npb, met + 8, &pe, r.c.params, r.c.grads, r.c.m, r.c.v,
+                           r.c.n, csq, ncb, met + 9, &ce, r.step0 + u + 1, r.lr_schedule[u], hp.max_grad_norm, hp.adam_b1, hp.adam_b2,
+                           hp.adam_eps, st, r.sched_dev ? r.sched_dev + 4 * u : nullptr);
+    if (rc) return rc;
+  }
+  return RLX_OK;
+}
+
+// clip + Adam of one network on its chain's stream; with `collective` its gradient is all-reduced first
+static int chain_step(const UpdateRun& r, const UpdateNet& n, const float* sq, int nsq, int u, float* norm_out, const BxEmit& emit,
+                      hipStream_t st) {
+  const rlx_ppo_hparams& hp = *r.hp;
+  const int64_t step = r.step0 + u + 1;
+  if (r.collective) {
+    const int rc = dist_allreduce(r.ctx, n.grads, n.n, 0, st);
+    if (rc) return rc;
+    return clip_adam_step(r.ctx, n.params, n.grads, n.m, n.v, n.n, step, r.lr_schedule[u], hp.max_grad_norm, hp.adam_b1, hp.adam_b2,
+                          hp.adam_eps, norm_out, st, &emit);
+  }
+  return launch_clip_adam(n.params, n.grads, n.m, n.v, n.n, sq, nsq, step, r.lr_schedule[u], hp.max_grad_norm, hp.adam_b1, hp.adam_b2,
+                          hp.adam_eps, norm_out, st, r.sched_dev ? r.sched_dev + 4 * u : nullptr, &emit);
+}
+
+// Policy chain on `st`, critic chain on `st_c`, and NO join between updates: gather(u+1) and policy(u+1) start while critic(u) is
+// still running.  The two chains drift out of phase and one net's bandwidth-bound kernels (first layer, head/loss, slab
+// reduction, Adam) run under the other net's MFMA kernels instead of next to their twins.  Same kernels, same inputs, same order
+// per net: the results are those of the joined schedule bit for bit.
+// Row buffers.  G > 1: the rows of G consecutive updates are gathered by ONE launch into one of two alternating group buffers and
+// the chains meet once per group (the critic waits for the group's rows, the gather of group g + 2 for the critic's last read of
+// group g).  G == 1: one gather per update into the two row buffers by update parity -- or, where the caller allows it
+// (own_rows_ok) and for minibatches of at most 8192 rows, each chain gathers ITS OWN copy of the rows on its own stream.  Such
+// updates are ~11 dependent kernels of 5-17 us per chain and bound by the issuing thread (measured: 2.9 us per launch, 4.4 us per
+// event record, ~4 us per stream wait; tools/probes/launch_cost.hip): one more 4 us kernel, four event operations fewer per
+// update, and nothing couples the chains between the fork and the final join.
+static int run_two_chains(const UpdateRun& r, hipStream_t st, hipStream_t st_c, bool floor_32768, bool own_rows_ok) {
+  rlx_ctx* ctx = r.ctx;
+  const rlx_ppo_hparams& hp = *r.hp;
+  const int G = gather_group_updates(ctx, r.stride, r.n_upd, r.sb[0].rec != nullptr, hp.critic_states != nullptr, floor_32768, false);
+  MbScratch grp[2];
+  int rc = group_buffers(r, G, 2, grp);
+  if (rc) return rc;
+  const bool own_rows = own_rows_ok && G == 1 && r.stride <= 8192;
+  for (int u = 0; u < r.n_upd; ++u) {
+    const int gi = u / G, j = u % G;
+    const int par = own_rows ? 0 : (G > 1 ? (gi & 1) : (u & 1));
+    const bool group_start = j == 0, group_end = j == G - 1 || u == r.n_upd - 1;
+    float* met = r.metrics_out + (int64_t)u * 10;
+    if (group_start) {
+      if (gi >= 2 && !own_rows) RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_cdone[par], 0));   // critic done with the rows of group gi - 2
+      rc = gather_group(r, u, r.n_upd - u < G ? r.n_upd - u : G, G, grp[par], st);
+      if (rc) return rc;
+      if (!own_rows) RLX_HIP_TRY(hipEventRecord(ctx->ev_rows[par], st));
+    }
+    MbScratch sp = r.sb[0], sc = r.sb[1];   // policy: activation / slab arenas of bank 0; critic: of bank 1; rows of this update
+    group_rows(r, grp[par], j, &sp);
+    sp.stats = sc.stats = r.stats_all + (int64_t)u * 4;
+    sp.valid_rows = sc.valid_rows = r.counts ? r.counts + u : nullptr;
+    int npb = 0, ncb = 0;
+    // the first critic pass starts when the first policy pass has finished its forward half: from then on the two
+    // chains stay about half an update apart (nothing joins them before the end of the call)
+    rc = net_fwd_bwd<true>(ctx, *r.p.desc, r.p.params, r.p.grads, met, sp, r.stride, r.mb_global, hp, r.psq, &npb, st,
+                           u == 0 ? ctx->ev_fork : nullptr);
+    if (rc) return rc;
+    const BxEmit pe = bx_emit_table(ctx, *r.p.desc, r.p.params);
+    rc = chain_step(r, r.p, r.psq, npb, u, met + 8, pe, st);
+    if (rc) return rc;
+    if (u == 0 || (!own_rows && group_start)) RLX_HIP_TRY(hipStreamWaitEvent(st_c, u == 0 ? ctx->ev_fork : ctx->ev_rows[par], 0));
+    if (own_rows) {
+      rc = gather_group(r, u, 1, 1, sc, st_c);
+      if (rc) return rc;
+    } else {
+      sc.mb_x = sp.mb_x; sc.mb_xc = grp[par].mb_xc; sc.mb_a = sp.mb_a; sc.aux = sp.aux;
+    }
+    ctx->bank = 1;
+    rc = net_fwd_bwd<false>(ctx, *r.c.desc, r.c.params, r.c.grads, met, sc, r.stride, r.mb_global, hp, r.csq, &ncb, st_c);
+    const BxEmit ce = bx_emit_table(ctx, *r.c.desc, r.c.params);   // (bank 1 still selected)
+    ctx->bank = 0;
+    if (rc) return rc;
+    rc = chain_step(r, r.c, r.csq, ncb, u, met + 9, ce, st_c);
+    if (rc) return rc;
+    if (!own_rows && group_end) RLX_HIP_TRY(hipEventRecord(ctx->ev_cdone[par], st_c));
+  }
+  RLX_HIP_TRY(hipEventRecord(ctx->ev_join, st_c));     // the call's work completes on the caller's stream
+  RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
+  return RLX_OK;
+}
+
 }  // namespace rlx
 
 using namespace rlx;
@@ -2287,17 +2536,7 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
                        int T, int N, int nr_epochs, int minibatch_size, uint32_t key_io[2], int scheme,
                        int64_t* opt_count_io, const float* lr_schedule, const rlx_ppo_hparams* hp, float* metrics_out,
                        void* stream) {
-  if (ctx) ctx->ro_img.valid = false;   // the acting nets' weight images go stale with this call
-  // weight images of the two networks persist over the updates of this call (re-emitted by clip + Adam), dropped at its end
-  struct BxKeep {
-    rlx_ctx* c;
-    ~BxKeep() {
-      if (!c) return;
-      c->bx_keep[0] = c->bx_keep[1] = false;
-      bx_release_all(c);
-    }
-  } bx_keep_scope{ctx};
-  if (ctx && ctx->adam_emit && ctx->gemm_bx) ctx->bx_keep[0] = ctx->bx_keep[1] = true;
+  BxKeep bx_keep_scope(ctx);
   RLX_REQUIRE(ctx && pdesc && pparams && pm && pv && cdesc && cparams && cm && cv && states && actions && log_probs &&
                   returns && advantages && key_io && opt_count_io && lr_schedule && hp && metrics_out,
               RLX_EINVAL, "rlx_ppo_update_f32: NULL pointer");
@@ -2348,25 +2587,18 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
     rc = twin_images(ctx, *pdesc, LPt, pparams, *cdesc, LCt, cparams, st, &tim, &twin);
     if (rc) return rc;
   }
-  if (twin || (st_c != st && ctx->pipeline_updates)) {
-    // Policy chain on the main stream, critic chain on the side stream, and NO join between updates: the gathered rows are
-    // double buffered (scratch banks 0 / 1 by update parity), so gather(u+1) and policy(u+1) start while critic(u) is still
-    // running.  The two chains drift out of phase and one net's bandwidth-bound kernels (first layer, head/loss,
-    // slab reduction, Adam) run under the other net's MFMA kernels instead of next to their twins.  Same kernels, same
-    // inputs, same order per net: the results are those of the joined schedule bit for bit.
-    const int O = pdesc->in_dim, A = pdesc->out_dim, LDX = row_pitch(O);   // LDX: row stride of the gathered observation rows
-    MbScratch sb[2];
-    for (int b = 0; b < 2; ++b) {
-      ctx->bank = b;
-      rc = mb_scratch(ctx, *pdesc, *cdesc, minibatch_size, &sb[b], hp->critic_states != nullptr);
-      ctx->bank = 0;
-      if (rc) return rc;
-    }
-    rc = pack_rollout_rows(ctx, states, actions, log_probs, returns, advantages, B, O, hp->discrete_actions ? 1 : A,
-                           hp->critic_states != nullptr, sb, 2, st);
+  // twin launches or two free-running chains (run_twin / run_two_chains); otherwise one joined pass per update (minibatch_core)
+  const bool pipelined = twin || (st_c != st && ctx->pipeline_updates);
+  const int O = pdesc->in_dim, A_act = hp->discrete_actions ? 1 : pdesc->out_dim;
+  MbScratch sb[2];
+  float* sched_dev = nullptr;
+  if (pipelined) {
+    rc = mb_scratch_banks(ctx, *pdesc, *cdesc, minibatch_size, hp->critic_states != nullptr, sb);
+    if (rc) return rc;
+    rc = pack_rollout_rows(ctx, states, actions, log_probs, returns, advantages, B, O, A_act, hp->critic_states != nullptr, sb, 2, st);
     if (rc) return rc;
     // per-update {lr, 1 - b1^step, 1 - b2^step} in a device table (pinned staging ring -> one H2D copy per call)
-    float* sched_dev = (float*)scratch(ctx, SL_SCHED, (size_t)n_upd * 4 * sizeof(float));
+    sched_dev = (float*)scratch(ctx, SL_SCHED, (size_t)n_upd * 4 * sizeof(float));
     if (!sched_dev) return RLX_ENOMEM;
     {
       const size_t need = (size_t)n_upd * 4 * sizeof(float);
@@ -2391,161 +2623,21 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
       RLX_HIP_TRY(hipMemcpyAsync(sched_dev, h, need, hipMemcpyHostToDevice, st));
       RLX_HIP_TRY(hipEventRecord(ctx->sched_ev[slot], st));
     }
-    auto issue = [&](hipStream_t s0) -> int {
-      // advantage statistics of all E*M minibatches: one workgroup each, fixed summation order (dist.hip)
-      int r = dist_adv_sums(advantages, perm, nullptr, n_upd, minibatch_size, minibatch_size, stats_all, s0);
-      if (r) return r;
-      RLX_HIP_TRY(hipMemsetAsync(metrics_out, 0, (size_t)n_upd * 10 * sizeof(float), s0));
-      // Small minibatches (the per-rank share of a sharded job): ~11 dependent kernels of 5-17 us per chain, and the update is
-      // bound by the issuing thread (measured on this box: 2.9 us per launch, 4.4 us per event record, ~4 us per stream wait;
-      // tools/probes/launch_cost.hip).  Each chain then gathers ITS OWN copy of the rows on its own stream: one more 4 us
-      // kernel, four event operations fewer per update, and nothing couples the chains between the fork and the final join.
-      if (twin) {
-        // The rows of G consecutive updates are gathered by ONE launch (the permutation of the whole call exists up front and the
-        // updates' index ranges are adjacent): at 4096 rows the gather was 5.7 of the update's 107 us, a dependent launch of its own.
-        const int grp_rows = ctx->gather_group_rows > 32768 && sb[0].rec ? ctx->gather_group_rows : 32768;
-        const int G = n_upd < grp_rows / minibatch_size ? n_upd : (grp_rows / minibatch_size > 0 ? grp_rows / minibatch_size : 1);
-        MbScratch grp = sb[0];
-        if (G > 1) {
-          const int64_t rows = (int64_t)G * minibatch_size;
-          grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A) * sizeof(float));
-          grp.aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
-          if (!grp.mb_x || !grp.aux) return RLX_ENOMEM;
-          grp.mb_a = grp.mb_x + (size_t)rows * LDX;
-          grp.mb_xc = nullptr;
-        }
-        for (int u = 0; u < n_upd; ++u) {
-          float* met = metrics_out + (int64_t)u * 10;
-          const int j = u % G;
-          if (j == 0) {
-            const int g = n_upd - u < G ? n_upd - u : G;
-            grp.mb_a = grp.mb_x + (size_t)g * minibatch_size * LDX;                 // (a shorter last group: [g*mb, O] then [g*mb, A])
-            r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, grp,
-                              nullptr, nullptr, (int64_t)g * minibatch_size, O, A, s0);
-            if (r) return r;
-          }
-          MbScratch sp = sb[0], sc = sb[1];
-          sp.mb_x = grp.mb_x + (size_t)j * minibatch_size * LDX;
-          sp.mb_a = grp.mb_a + (size_t)j * minibatch_size * A;
-          sp.aux = grp.aux + (size_t)j * minibatch_size * 3;
-          sp.stats = sc.stats = stats_all + (int64_t)u * 4;
-          int npb = 0, ncb = 0;
-          r = twin_fwd_bwd(ctx, *pdesc, LPt, pparams, pg, *cdesc, LCt, cparams, cg, tim, met, sp, sc, minibatch_size,
-                           minibatch_size, *hp, psq, &npb, &ncb, s0);
-          if (r) return r;
-          ctx->bank = 0;
-          const BxEmit pe = bx_emit_table(ctx, *pdesc, pparams);
-          ctx->bank = 1;
-          const BxEmit ce = bx_emit_table(ctx, *cdesc, cparams);
-          ctx->bank = 0;
-          r = launch_clip_adam2(pparams, pg, pm, pv, np_, psq, npb, met + 8, &pe, cparams, cg, cm, cv, nc_, psq + npb, ncb, met + 9,
-                                &ce, *opt_count_io + u + 1, lr_schedule[u], hp->max_grad_norm, hp->adam_b1, hp->adam_b2,
-                                hp->adam_eps, s0, sched_dev + 4 * u);
-          if (r) return r;
-        }
-        return RLX_OK;
-      }
-      // Row buffers.  G > 1 (record source, option "gather_group_rows"): the rows of G consecutive updates are gathered by ONE launch
-      // into one of two alternating group buffers and the chains meet once per group (the critic waits for the group's rows, the
-      // gather of group g + 2 for the critic's last read of group g).  G == 1: one gather per update into the two row buffers by
-      // update parity -- or, for minibatches of at most 8192 rows, each chain gathers its own copy (own_rows; nothing couples the
-      // chains between the fork and the final join).
-      const int A_act = hp->discrete_actions ? 1 : A;
-      int G = 1;
-      if (sb[0].rec && !hp->critic_states && ctx->gather_group_rows > minibatch_size) {
-        G = ctx->gather_group_rows / minibatch_size;
-        if (G > n_upd) G = n_upd;
-      }
-      MbScratch grp[2] = {sb[0], sb[1]};
-      if (G > 1) {
-        const int64_t rows = (int64_t)G * minibatch_size;
-        for (int b = 0; b < 2; ++b) {
-          ctx->bank = b;
-          grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
-          grp[b].aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
-          ctx->bank = 0;
-          if (!grp[b].mb_x || !grp[b].aux) return RLX_ENOMEM;
-          grp[b].mb_xc = nullptr;
-        }
-      }
-      const bool own_rows = G == 1 && minibatch_size <= 8192;
-      for (int u = 0; u < n_upd; ++u) {
-        const int gi = u / G, j = u % G;
-        const int par = own_rows ? 0 : (G > 1 ? (gi & 1) : (u & 1));
-        const bool group_start = j == 0, group_end = j == G - 1 || u == n_upd - 1;
-        float* met = metrics_out + (int64_t)u * 10;
-        double* stats = stats_all + (int64_t)u * 4;
-        const float* sch = sched_dev + 4 * u;
-        if (group_start) {
-          if (gi >= 2 && !own_rows) RLX_HIP_TRY(hipStreamWaitEvent(s0, ctx->ev_cdone[par], 0));   // critic done with the rows of group gi - 2
-          if (G > 1) {
-            const int g = n_upd - u < G ? n_upd - u : G;
-            grp[par].mb_a = grp[par].mb_x + (size_t)g * minibatch_size * LDX;
-            r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, grp[par],
-                              nullptr, nullptr, (int64_t)g * minibatch_size, O, A_act, s0);
-          } else {
-            r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, sb[par],
-                              nullptr, nullptr, (int64_t)minibatch_size, O, A_act, s0, hp->critic_states, cdesc->in_dim);
-          }
-          if (r) return r;
-          if (!own_rows) RLX_HIP_TRY(hipEventRecord(ctx->ev_rows[par], s0));
-        }
-        MbScratch rows_u = sb[par];           // where this update's rows are
-        if (G > 1) {
-          rows_u.mb_x = grp[par].mb_x + (size_t)j * minibatch_size * LDX;
-          rows_u.mb_a = grp[par].mb_a + (size_t)j * minibatch_size * A_act;
-          rows_u.aux = grp[par].aux + (size_t)j * minibatch_size * 3;
-          rows_u.mb_xc = nullptr;
-        }
-        int npb = 0, ncb = 0;
-        const int64_t step = *opt_count_io + u + 1;
-        MbScratch sp = sb[0];                 // policy: activation / slab arenas of bank 0, rows of this update
-        sp.mb_x = rows_u.mb_x; sp.mb_a = rows_u.mb_a; sp.aux = rows_u.aux; sp.stats = stats;
-        // the first critic pass starts when the first policy pass has finished its forward half: from then on the two
-        // chains stay about half an update apart (nothing joins them before the end of the call)
-        r = net_fwd_bwd<true>(ctx, *pdesc, pparams, pg, met, sp, minibatch_size, minibatch_size, *hp, psq, &npb, s0,
-                              u == 0 ? ctx->ev_fork : nullptr);
-        if (r) return r;
-        const BxEmit pe = bx_emit_table(ctx, *pdesc, pparams);
-        r = launch_clip_adam(pparams, pg, pm, pv, np_, psq, npb, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                             hp->adam_b2, hp->adam_eps, met + 8, s0, sch, &pe);
-        if (r) return r;
-        if (u == 0 || (!own_rows && group_start)) RLX_HIP_TRY(hipStreamWaitEvent(st_c, u == 0 ? ctx->ev_fork : ctx->ev_rows[par], 0));
-        MbScratch sc = sb[1];                 // critic: arenas of bank 1
-        if (own_rows) {
-          r = launch_gather(ctx, states, actions, log_probs, returns, advantages, perm + (int64_t)u * minibatch_size, sb[1],
-                            nullptr, nullptr, (int64_t)minibatch_size, O, A_act, st_c, hp->critic_states, cdesc->in_dim);
-          if (r) return r;
-        } else {
-          sc.mb_x = rows_u.mb_x; sc.mb_xc = rows_u.mb_xc; sc.mb_a = rows_u.mb_a; sc.aux = rows_u.aux;
-        }
-        sc.stats = stats;
-        ctx->bank = 1;
-        r = net_fwd_bwd<false>(ctx, *cdesc, cparams, cg, met, sc, minibatch_size, minibatch_size, *hp, csq, &ncb, st_c);
-        const BxEmit ce = bx_emit_table(ctx, *cdesc, cparams);   // (bank 1 still selected)
-        ctx->bank = 0;
-        if (r) return r;
-        r = launch_clip_adam(cparams, cg, cm, cv, nc_, csq, ncb, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                             hp->adam_b2, hp->adam_eps, met + 9, st_c, sch, &ce);
-        if (r) return r;
-        if (!own_rows && group_end) RLX_HIP_TRY(hipEventRecord(ctx->ev_cdone[par], st_c));
-      }
-      RLX_HIP_TRY(hipEventRecord(ctx->ev_join, st_c));     // the call's work completes on the main stream
-      RLX_HIP_TRY(hipStreamWaitEvent(s0, ctx->ev_join, 0));
-      return RLX_OK;
-    };
-    rc = issue(st);
-    if (rc) return rc;
-    *opt_count_io += (int64_t)nr_epochs * M;
-    if (!ctx->ev_perm_free) RLX_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_perm_free, hipEventDisableTiming));
-    RLX_HIP_TRY(hipEventRecord(ctx->ev_perm_free, st));
-    ctx->perm_free_recorded = true;
-    return RLX_OK;
   }
   // advantage statistics of all E*M minibatches: one workgroup each, fixed summation order (dist.hip)
   rc = dist_adv_sums(advantages, perm, nullptr, n_upd, minibatch_size, minibatch_size, stats_all, st);
   if (rc) return rc;
   RLX_HIP_TRY(hipMemsetAsync(metrics_out, 0, (size_t)n_upd * 10 * sizeof(float), st));
+  if (pipelined) {
+    const UpdateRun r = {ctx, {pdesc, pparams, pm, pv, pg, np_}, {cdesc, cparams, cm, cv, cg, nc_}, states, actions, log_probs, returns,
+                         advantages, perm, minibatch_size, minibatch_size, /*counts=*/nullptr, /*collective=*/false, sched_dev, n_upd,
+                         *opt_count_io, lr_schedule, hp, metrics_out, stats_all, psq, csq, sb, O, A_act, row_pitch(O)};
+    // two chains: the option "gather_group_rows" as given (0: one gather per update), a gather per chain for small minibatches
+    rc = twin ? run_twin(r, tim, st, /*plain_groups=*/true) : run_two_chains(r, st, st_c, /*floor_32768=*/false, /*own_rows_ok=*/true);
+    if (rc) return rc;
+    *opt_count_io += n_upd;
+    return record_perm_free(ctx, st);
+  }
   ctx->bx_keep[0] = ctx->bx_keep[1] = false;   // this schedule lays the weight images out per pass (its Adam launches do not emit)
   for (int u = 0; u < n_upd; ++u) {
     float* met = metrics_out + (int64_t)u * 10;
@@ -2566,11 +2658,8 @@ int rlx_ppo_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams, 
       RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
     }
   }
-  *opt_count_io += (int64_t)nr_epochs * M;
-  if (!ctx->ev_perm_free) RLX_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_perm_free, hipEventDisableTiming));
-  RLX_HIP_TRY(hipEventRecord(ctx->ev_perm_free, st));
-  ctx->perm_free_recorded = true;
-  return RLX_OK;
+  *opt_count_io += n_upd;
+  return record_perm_free(ctx, st);
 }
 
 void* rlx_ctx_side_stream(rlx_ctx* ctx) {
@@ -2630,17 +2719,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
                             int T, int n_local, int n_global, int env_id_offset, int nr_epochs, int minibatch_size,
                             uint32_t key_io[2], int scheme, int64_t* opt_count_io, const float* lr_schedule,
                             const rlx_ppo_hparams* hp, float* metrics_out, void* stream) {
-  if (ctx) ctx->ro_img.valid = false;   // the acting nets' weight images go stale with this call
-  // weight images of the two networks persist over the updates of this call (re-emitted by clip + Adam), dropped at its end
-  struct BxKeep {
-    rlx_ctx* c;
-    ~BxKeep() {
-      if (!c) return;
-      c->bx_keep[0] = c->bx_keep[1] = false;
-      bx_release_all(c);
-    }
-  } bx_keep_scope{ctx};
-  if (ctx && ctx->adam_emit && ctx->gemm_bx) ctx->bx_keep[0] = ctx->bx_keep[1] = true;
+  BxKeep bx_keep_scope(ctx);
   RLX_REQUIRE(ctx && pdesc && pparams && pm && pv && cdesc && cparams && cm && cv && states && actions && log_probs &&
                   returns && advantages && key_io && opt_count_io && lr_schedule && hp && metrics_out,
               RLX_EINVAL, "rlx_ppo_update_dist_f32: NULL pointer");
@@ -2711,160 +2790,28 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     rc = dist_sum_dropped(ctx, stats_all, n_upd, st);
     if (rc) return rc;
   }
-  const int O = pdesc->in_dim, A = pdesc->out_dim, A_act = hp->discrete_actions ? 1 : A, LDX = row_pitch(O);
+  const int O = pdesc->in_dim, A_act = hp->discrete_actions ? 1 : pdesc->out_dim;
   MbScratch sb[2];
-  for (int b = 0; b < 2; ++b) {
-    ctx->bank = b;
-    rc = mb_scratch(ctx, *pdesc, *cdesc, cap, &sb[b], hp->critic_states != nullptr);
-    ctx->bank = 0;
-    if (rc) return rc;
-  }
+  rc = mb_scratch_banks(ctx, *pdesc, *cdesc, cap, hp->critic_states != nullptr, sb);
+  if (rc) return rc;
   rc = pack_rollout_rows(ctx, states, actions, log_probs, returns, advantages, (int64_t)T * n_local, O, A_act,
                          hp->critic_states != nullptr, sb, 2, st);
   if (rc) return rc;
   RLX_HIP_TRY(hipMemsetAsync(metrics_out, 0, (size_t)n_upd * 10 * sizeof(float), st));
+  // a rank that holds every row has no padding: no counts.  No device schedule table: the Adam launches take scalars.
+  const UpdateRun r = {ctx, {pdesc, pparams, pm, pv, pg, np_}, {cdesc, cparams, cm, cv, cg, nc_}, states, actions, log_probs, returns,
+                       advantages, lidx, cap, minibatch_size, whole ? nullptr : counts, collective, /*sched_dev=*/nullptr, n_upd,
+                       *opt_count_io, lr_schedule, hp, metrics_out, stats_all, psq, csq, sb, O, A_act, row_pitch(O)};
   if (twin) {
     if (np4 > np_) RLX_HIP_TRY(hipMemsetAsync(pg + np_, 0, (size_t)(np4 - np_) * sizeof(float), st));
-    // the rows of G consecutive updates by ONE gather launch, as in rlx_ppo_update_f32 (lidx is [n_upd, cap]: adjacent ranges;
-    // the per-update valid counts go along as an array) -- needs the record source (k_gather_rec)
-    const int grp_rows = ctx->gather_group_rows > 32768 ? ctx->gather_group_rows : 32768;
-    const int G = !sb[0].rec ? 1 : (n_upd < grp_rows / cap ? n_upd : (grp_rows / cap > 0 ? grp_rows / cap : 1));
-    MbScratch grp = sb[0];
-    if (G > 1) {
-      const int64_t rows = (int64_t)G * cap;
-      grp.mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
-      grp.aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
-      if (!grp.mb_x || !grp.aux) return RLX_ENOMEM;
-      grp.mb_xc = nullptr;
-    }
-    for (int u = 0; u < n_upd; ++u) {
-      float* met = metrics_out + (int64_t)u * 10;
-      const int32_t* cnt_u = whole ? nullptr : counts + u;
-      const int j = u % G;
-      if (j == 0) {
-        const int g = n_upd - u < G ? n_upd - u : G;
-        grp.mb_a = grp.mb_x + (size_t)g * cap * LDX;
-        rc = launch_gather(ctx, states, actions, log_probs, returns, advantages, lidx + (int64_t)u * cap, grp, nullptr, cnt_u,
-                           (int64_t)g * cap, O, A_act, st, nullptr, 0, G > 1 ? cap : 0);
-        if (rc) return rc;
-      }
-      MbScratch sp = sb[0], sc = sb[1];
-      sp.mb_x = grp.mb_x + (size_t)j * cap * LDX;
-      sp.mb_a = grp.mb_a + (size_t)j * cap * A_act;
-      sp.aux = grp.aux + (size_t)j * cap * 3;
-      sp.stats = sc.stats = stats_all + (int64_t)u * 4;
-      sp.valid_rows = sc.valid_rows = cnt_u;
-      int npb = 0, ncb = 0;
-      rc = twin_fwd_bwd(ctx, *pdesc, LPt, pparams, pg, *cdesc, LCt, cparams, cg, tim, met, sp, sc, cap, minibatch_size, *hp, psq,
-                        &npb, &ncb, st);
-      if (rc) return rc;
-      const float *pp_ = psq, *cp_ = psq + npb;
-      if (collective) {
-        rc = dist_allreduce(ctx, pg, np4 + nc_, 0, st);
-        if (rc) return rc;
-        rc = launch_sumsq_partials2(pg, np_, psq, &npb, cg, nc_, csq, &ncb, st);   // norms of the REDUCED gradients
-        if (rc) return rc;
-        cp_ = csq;
-      }
-      ctx->bank = 0;
-      const BxEmit pe = bx_emit_table(ctx, *pdesc, pparams);
-      ctx->bank = 1;
-      const BxEmit ce = bx_emit_table(ctx, *cdesc, cparams);
-      ctx->bank = 0;
-      rc = launch_clip_adam2(pparams, pg, pm, pv, np_, pp_, npb, met + 8, &pe, cparams, cg, cm, cv, nc_, cp_, ncb, met + 9, &ce,
-                             *opt_count_io + u + 1, lr_schedule[u], hp->max_grad_norm, hp->adam_b1, hp->adam_b2, hp->adam_eps, st);
-      if (rc) return rc;
-    }
+    rc = run_twin(r, tim, st, /*plain_groups=*/false);   // grouped gathers need the record source here (k_gather_rec)
   } else {
-  // the side stream starts after everything queued on `stream` so far (statistics, index plumbing)
-  RLX_HIP_TRY(hipEventRecord(ctx->ev_join, st));
-  RLX_HIP_TRY(hipStreamWaitEvent(st_c, ctx->ev_join, 0));
-  // The rows of G consecutive updates are gathered by ONE launch into one of two alternating group buffers (as in the twin
-  // schedule above): the chains then meet once per group instead of once per update -- the critic waits for the group's rows, the
-  // gather of group g + 2 for the critic's last read of group g.  (G = 1 without the record source or with critic-only rows.)
-  const int grp_rows2 = ctx->gather_group_rows > 32768 ? ctx->gather_group_rows : 32768;
-  const int G = (!sb[0].rec || hp->critic_states) ? 1 : (n_upd < grp_rows2 / cap ? n_upd : (grp_rows2 / cap > 0 ? grp_rows2 / cap : 1));
-  MbScratch grp[2] = {sb[0], sb[1]};
-  if (G > 1) {
-    const int64_t rows = (int64_t)G * cap;
-    for (int b = 0; b < 2; ++b) {
-      ctx->bank = b;
-      grp[b].mb_x = (float*)scratch(ctx, SL_MB_GROUP_X, (size_t)rows * (LDX + A_act) * sizeof(float));
-      grp[b].aux = (float*)scratch(ctx, SL_MB_GROUP_AUX, (size_t)rows * 3 * sizeof(float));
-      ctx->bank = 0;
-      if (!grp[b].mb_x || !grp[b].aux) return RLX_ENOMEM;
-      grp[b].mb_xc = nullptr;
-    }
+    // the side stream starts after everything queued on `stream` so far (statistics, index plumbing)
+    RLX_HIP_TRY(hipEventRecord(ctx->ev_join, st));
+    RLX_HIP_TRY(hipStreamWaitEvent(st_c, ctx->ev_join, 0));
+    rc = run_two_chains(r, st, st_c, /*floor_32768=*/true, /*own_rows_ok=*/false);
   }
-  for (int u = 0; u < n_upd; ++u) {
-    const int gi = u / G, j = u % G;
-    const int par = G > 1 ? (gi & 1) : (u & 1);
-    const bool group_start = j == 0, group_end = j == G - 1 || u == n_upd - 1;
-    float* met = metrics_out + (int64_t)u * 10;
-    double* stats = stats_all + (int64_t)u * 4;
-    const int32_t* cnt_u = whole ? nullptr : counts + u;   // a rank that holds every row has no padding
-    if (group_start) {
-      if (gi >= 2) RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_cdone[par], 0));   // the critic is done with the rows of group gi - 2
-      if (G > 1) {
-        const int g = n_upd - u < G ? n_upd - u : G;
-        grp[par].mb_a = grp[par].mb_x + (size_t)g * cap * LDX;
-        rc = launch_gather(ctx, states, actions, log_probs, returns, advantages, lidx + (int64_t)u * cap, grp[par], nullptr, cnt_u,
-                           (int64_t)g * cap, O, A_act, st, nullptr, 0, cap);
-      } else {
-        rc = launch_gather(ctx, states, actions, log_probs, returns, advantages, lidx + (int64_t)u * cap, sb[par],
-                           nullptr, cnt_u, (int64_t)cap, O, A_act, st, hp->critic_states, cdesc->in_dim);
-      }
-      if (rc) return rc;
-      RLX_HIP_TRY(hipEventRecord(ctx->ev_rows[par], st));
-    }
-    MbScratch rows_u = sb[par];               // where this update's rows are
-    if (G > 1) {
-      rows_u.mb_x = grp[par].mb_x + (size_t)j * cap * LDX;
-      rows_u.mb_a = grp[par].mb_a + (size_t)j * cap * A_act;
-      rows_u.aux = grp[par].aux + (size_t)j * cap * 3;
-      rows_u.mb_xc = nullptr;
-    }
-    int npb = 0, ncb = 0;
-    const int64_t step = *opt_count_io + u + 1;
-    MbScratch sp = sb[0];
-    sp.mb_x = rows_u.mb_x; sp.mb_a = rows_u.mb_a; sp.aux = rows_u.aux; sp.stats = stats; sp.valid_rows = cnt_u;
-    rc = net_fwd_bwd<true>(ctx, *pdesc, pparams, pg, met, sp, cap, minibatch_size, *hp, psq, &npb, st,
-                           u == 0 ? ctx->ev_fork : nullptr);
-    if (rc) return rc;
-    const BxEmit pe = bx_emit_table(ctx, *pdesc, pparams);
-    if (collective) {
-      rc = dist_allreduce(ctx, pg, np_, 0, st);
-      if (rc) return rc;
-      rc = clip_adam_step(ctx, pparams, pg, pm, pv, np_, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                          hp->adam_b2, hp->adam_eps, met + 8, st, &pe);
-    } else {
-      rc = launch_clip_adam(pparams, pg, pm, pv, np_, psq, npb, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                            hp->adam_b2, hp->adam_eps, met + 8, st, nullptr, &pe);
-    }
-    if (rc) return rc;
-    if (group_start) RLX_HIP_TRY(hipStreamWaitEvent(st_c, u == 0 ? ctx->ev_fork : ctx->ev_rows[par], 0));
-    MbScratch sc = sb[1];
-    sc.mb_x = rows_u.mb_x; sc.mb_xc = rows_u.mb_xc; sc.mb_a = rows_u.mb_a; sc.aux = rows_u.aux; sc.stats = stats; sc.valid_rows = cnt_u;
-    ctx->bank = 1;
-    rc = net_fwd_bwd<false>(ctx, *cdesc, cparams, cg, met, sc, cap, minibatch_size, *hp, csq, &ncb, st_c);
-    const BxEmit ce = bx_emit_table(ctx, *cdesc, cparams);   // (bank 1 still selected)
-    ctx->bank = 0;
-    if (rc) return rc;
-    if (collective) {
-      rc = dist_allreduce(ctx, cg, nc_, 0, st_c);
-      if (rc) return rc;
-      rc = clip_adam_step(ctx, cparams, cg, cm, cv, nc_, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                          hp->adam_b2, hp->adam_eps, met + 9, st_c, &ce);
-    } else {
-      rc = launch_clip_adam(cparams, cg, cm, cv, nc_, csq, ncb, step, lr_schedule[u], hp->max_grad_norm, hp->adam_b1,
-                            hp->adam_b2, hp->adam_eps, met + 9, st_c, nullptr, &ce);
-    }
-    if (rc) return rc;
-    if (group_end) RLX_HIP_TRY(hipEventRecord(ctx->ev_cdone[par], st_c));
-  }
-  RLX_HIP_TRY(hipEventRecord(ctx->ev_join, st_c));
-  RLX_HIP_TRY(hipStreamWaitEvent(st, ctx->ev_join, 0));
-  }
+  if (rc) return rc;
   if (collective) {
     // per-update metrics: partial sums over this rank's rows -> ONE all-reduce per iteration
     rc = dist_mask_metrics(metrics_out, n_upd, ctx->rank, hp->discrete_actions, st);
@@ -2873,10 +2820,7 @@ int rlx_ppo_update_dist_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* ppar
     if (rc) return rc;
   }
   *opt_count_io += n_upd;
-  if (!ctx->ev_perm_free) RLX_HIP_TRY(hipEventCreateWithFlags(&ctx->ev_perm_free, hipEventDisableTiming));
-  RLX_HIP_TRY(hipEventRecord(ctx->ev_perm_free, st));
-  ctx->perm_free_recorded = true;
-  return RLX_OK;
+  return record_perm_free(ctx, st);
 }
 
 int rlx_actor_critic_fwd_sample_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, const float* pparams,
