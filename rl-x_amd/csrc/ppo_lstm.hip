@@ -66,8 +66,11 @@ static int check_lstm_desc(const rlx_lstm_policy_desc& d) {
   RLX_REQUIRE(d.combine == RLX_COMBINE_CONCAT || d.combine == RLX_COMBINE_FILM, RLX_EINVAL,
               "ppo_lstm: combine must be RLX_COMBINE_CONCAT or RLX_COMBINE_FILM");
   RLX_REQUIRE(d.enc_dim % 64 == 0 && d.enc_dim >= 64 && d.enc_dim <= 512, RLX_EUNSUP, "ppo_lstm: obs_encoding_dim must be a multiple of 64");
-  RLX_REQUIRE(d.torso[0] % 64 == 0 && d.torso[0] <= 512 && d.torso[1] % 4 == 0 && d.torso[2] % 4 == 0 && d.torso[2] >= 4, RLX_EUNSUP,
-              "ppo_lstm: torso widths unsupported");
+  // (x % 64 == 0 and x % 4 == 0 hold for 0 and for negative multiples: every width is bounded from below as well)
+  RLX_REQUIRE(d.torso[0] % 64 == 0 && d.torso[0] >= 64 && d.torso[0] <= 512, RLX_EUNSUP,
+              "ppo_lstm: torso[0] must be a multiple of 64 in [64, 512]");
+  RLX_REQUIRE(d.torso[1] % 4 == 0 && d.torso[1] >= 4, RLX_EUNSUP, "ppo_lstm: torso[1] must be a positive multiple of 4");
+  RLX_REQUIRE(d.torso[2] % 4 == 0 && d.torso[2] >= 4, RLX_EUNSUP, "ppo_lstm: torso[2] must be a positive multiple of 4");
   RLX_REQUIRE(d.act_dim >= 1 && d.act_dim <= 64, RLX_EUNSUP, "ppo_lstm: act_dim must be 1..64");
   RLX_REQUIRE((d.enc_dim + d.lstm_hidden) % 4 == 0, RLX_EUNSUP, "ppo_lstm: enc_dim + lstm_hidden must be a multiple of 4");
   return RLX_OK;
@@ -76,6 +79,7 @@ static int check_lstm_desc(const rlx_lstm_policy_desc& d) {
 struct LstmBufs {
   float *El, *Eo, *GA, *hout, *cout, *hin, *cin, *Lat, *Xc, *Z1, *H1, *H2, *H3, *done, *c0, *h0;
   float* GB;                // FiLM: [gamma | beta] [M, 2E] (backward: their gradients)
+  float* dEo;               // backward: d obs_latent [M, E] -- Eo itself (in place), with a shared encoder the slot Eo does not use
   float *GX, *dGRZ, *dHN;   // GRU: x-projection [M,3H] (backward: d x-projection), (dr_pre|dz_pre) [M,2H], d hnp [M,H]
   float *D2, *D1, *DX;      // backward of the torso, OUT OF PLACE: dZ2 [M,D2], dH1 -> dZ1 [M,D1], d(concat input) [M,E+H]
   int32_t* idx_flat;
@@ -93,7 +97,7 @@ static int lstm_bufs(rlx_ctx* ctx, const LstmLayout& L, int64_t M, int64_t ne, L
   float* base = (float*)scratch(ctx, SL_LSTM, off * sizeof(float));
   b->idx_flat = (int32_t*)scratch(ctx, SL_LSTM_IDX, (size_t)M * sizeof(int32_t));
   if (!base || !b->idx_flat) return RLX_ENOMEM;
-  b->El = base + oEl; b->Eo = L.share ? b->El : base + oEo; b->GA = base + oGA; b->hout = base + oho; b->cout = base + oco;
+  b->El = base + oEl; b->Eo = L.share ? b->El : base + oEo; b->dEo = base + oEo; b->GA = base + oGA; b->hout = base + oho; b->cout = base + oco;
   b->hin = base + ohi; b->cin = base + oci; b->Lat = base + oLat; b->Xc = base + oXc; b->Z1 = base + oZ1;
   b->H1 = base + oH1; b->H2 = base + oH2; b->H3 = base + oH3; b->done = base + odn; b->c0 = base + oc0; b->h0 = base + oh0;
   b->GX = base + oGX; b->dGRZ = base + oRZ; b->dHN = base + oHN; b->GB = base + oGB;
@@ -271,7 +275,8 @@ static int lstm_policy_bwd(rlx_ctx* ctx, const LstmLayout& L, const float* p, fl
   rc = stage_dx(ctx, b.D1, p + L.t1_W, b.DX, M, L.D1, L.K1, L.K1, RLX_ACT_NONE, 0, st); if (rc) return rc;
   if (!side) { rc = torso_dw(st); if (rc) return rc; }
   // d[obs_latent], d[cell latent]; with a shared encoder dE_o is added to dE_l further down
-  float* dEo = L.share ? b.Z1 : b.Eo;  // Z1 is free now ([M, D1] >= [M, E])
+  // (its own [M, E] slot: Z1 is free here but holds only M * D1 floats, and enc_dim may exceed torso[0])
+  float* dEo = b.dEo;
   if (L.film) {
     // x = obs_latent * gamma + beta: d obs_latent = dx * gamma; d gamma = dx * obs_latent; d beta = dx; then the two Dense
     // layers on the cell latent as ONE [H, 2E] GEMM pair (weight gradient, input gradient -> d cell latent)

@@ -600,3 +600,111 @@ def ppo_pass(O, hidden, A, act, ln_first, mb, options=None):
     for r in launches:
         out[r] = out.get(r, 0) + 1
     return dict(twin=twin, twin_ok=admissible, policy=pp, critic=cp, rows=out)
+
+
+# ------------------------------------------------- recurrent PPO (ppo_lstm.hip: check_lstm_desc, lstm_minibatch; rollout.hip: the decoder)
+LSTM_H, LSTM_ROWS = 64, 16                     # lstm_kernels.h: hidden units of the cell, envs per workgroup of the sequence kernels
+CELL_LSTM, CELL_GRU, COMBINE_CONCAT, COMBINE_FILM = 0, 1, 0, 1      # rlx_hip.h
+RLX_EINVAL, RLX_EUNSUP = -1, -4
+RO_ROWS, RO_MAXH, RO_MAXN = 32, 512, 256       # rollout.hip
+LSTM_DEFAULTS = dict(gemm_bx=1, bx_debug=0)
+GEMM_KERNELS = ("k_gemm_fwd", "k_gemm_dx", "k_gemm_dw")
+
+
+def lstm_check_desc(O, A, E, H, torso, cell, combine):
+    """ppo_lstm.hip check_lstm_desc, clause by clause in its order -> None, or (code, message) of the refusal"""
+    D1, D2, D3 = torso
+    if not 1 <= O <= 32:
+        return RLX_EUNSUP, "ppo_lstm: obs_dim must be 1..32 (encoders use the small-K fused layer)"
+    if H != LSTM_H:
+        return RLX_EUNSUP, "ppo_lstm: lstm_hidden_dim must be 64 in this build"
+    if cell not in (CELL_LSTM, CELL_GRU):
+        return RLX_EINVAL, "ppo_lstm: cell must be RLX_CELL_LSTM or RLX_CELL_GRU"
+    if combine not in (COMBINE_CONCAT, COMBINE_FILM):
+        return RLX_EINVAL, "ppo_lstm: combine must be RLX_COMBINE_CONCAT or RLX_COMBINE_FILM"
+    if not (E % 64 == 0 and 64 <= E <= 512):
+        return RLX_EUNSUP, "ppo_lstm: obs_encoding_dim must be a multiple of 64"
+    if not (D1 % 64 == 0 and 64 <= D1 <= 512):
+        return RLX_EUNSUP, "ppo_lstm: torso[0] must be a multiple of 64 in [64, 512]"
+    if not (D2 % 4 == 0 and D2 >= 4):
+        return RLX_EUNSUP, "ppo_lstm: torso[1] must be a positive multiple of 4"
+    if not (D3 % 4 == 0 and D3 >= 4):
+        return RLX_EUNSUP, "ppo_lstm: torso[2] must be a positive multiple of 4"
+    if not 1 <= A <= 64:
+        return RLX_EUNSUP, "ppo_lstm: act_dim must be 1..64"
+    return None
+
+
+def lstm_blocks(O, A, E, torso, share, gru, film):
+    """the flat layout of the recurrent policy (rlx_hip.h; lstm_layout) -> ([(name, offset, length)], n_params)"""
+    H, (D1, D2, D3) = LSTM_H, torso
+    K1 = E if film else E + H
+    names = []
+    for enc in (["enc_l"] if share else ["enc_l", "enc_o"]):
+        names += [(enc + ".W", O * E), (enc + ".b", E), (enc + ".g", E), (enc + ".be", E)]
+    if gru:
+        names += [("gru.Wi", E * 3 * H), ("gru.bi", 3 * H), ("gru.Wh_rz", H * 2 * H), ("gru.Wh_n", H * H), ("gru.bhn", H)]
+    else:
+        names += [("lstm.Wi", E * 4 * H), ("lstm.Wh", H * 4 * H), ("lstm.bh", 4 * H)]
+    names += [("lstm_ln.g", H), ("lstm_ln.be", H)]
+    if film:
+        names += [("film.W", H * 2 * E), ("film.b", 2 * E)]
+    names += [("t1.W", K1 * D1), ("t1.b", D1), ("t1.g", D1), ("t1.be", D1), ("t2.W", D1 * D2), ("t2.b", D2), ("t3.W", D2 * D3), ("t3.b", D3),
+              ("head.W", D3 * A), ("head.b", A), ("logstd", A)]
+    out, off = [], 0
+    for name, n in names:
+        out.append((name, off, n))
+        off += n
+    return out, off
+
+
+def rollout_net_ok(in_dim, hidden, out_dim):
+    """rollout.hip fill_net: a feed-forward net the fused acting kernels take"""
+    if not (1 <= len(hidden) <= 3 and 1 <= in_dim <= 32 and out_dim >= 1):
+        return False
+    if hidden[0] < 64 or hidden[0] % 64 or hidden[0] > RO_MAXH:
+        return False
+    for l in range(1, len(hidden)):
+        if hidden[l] not in (128, 256) or hidden[l - 1] % (2 * G_BK):
+            return False
+    return out_dim * RO_ROWS <= 1024
+
+
+def lstm_act_fused(E, torso, A, film, c_in, c_hidden, fused_recurrent_act=1):
+    """rlx_ppo_lstm_act_f32: the decoder (latent LayerNorm, torso, head, sampling) and the critic run as ONE k_rollout_step launch
+    (rollout_decoder_supported); otherwise layer by layer on the generic path"""
+    K0, (D1, D2, D3) = E + LSTM_H, torso
+    dec = K0 % 64 == 0 and 64 <= K0 <= RO_MAXN and D1 % 256 == 0 and D1 <= RO_MAXH and D2 in (128, 256) and D3 in (128, 256) and \
+        A * RO_ROWS <= 1024
+    return bool(fused_recurrent_act) and not film and dec and rollout_net_ok(c_in, c_hidden, 1)
+
+
+def ppo_lstm_pass(O, A, E, torso, share, gru, film, T, ne, c_in=None, c_hidden=(512, 256, 128), options=None):
+    """One rlx_ppo_lstm_minibatch_fwd_bwd_f32 call on T * ne rows with the critic [c_in -> c_hidden -> 1] (ELU, LayerNorm first) ->
+    dict(rows: {(kernel, engine, M, N, K): launches} of the GEMM kernels (GEMM_KERNELS) the profiler must show -- the policy's dense
+    layers through launch_gemm_fwd / stage_dx / stage_dw, the critic's through net_fwd_bwd --, split: the policy's images exist,
+    recurrent: "split" / "exact" product in k_lstm_seq_* (None for the GRU), full_tiles: every 16-env tile of the recurrence is full)."""
+    o = dict(LSTM_DEFAULTS)
+    o.update(options or {})
+    assert set(o) == set(LSTM_DEFAULTS)
+    H, (D1, D2, D3), M = LSTM_H, torso, T * ne
+    K1, gates = (E if film else E + H), (3 if gru else 4)
+    bx = bool(o["gemm_bx"])
+    split = bx and M >= SPLIT_ROWS            # bx_prepare_mats: t1, t2, t3 and Wi, both images (every width is a multiple of 4)
+    e = ENGINE_SPLIT if split else ENGINE_EXACT
+    launches = [("k_gemm_fwd", e, M, gates * H, E), ("k_gemm_fwd", e, M, D1, K1), ("k_gemm_fwd", e, M, D2, D1), ("k_gemm_fwd", e, M, D3, D2),
+                ("k_gemm_dx", e, M, D2, D3), ("k_gemm_dx", e, M, D1, D2), ("k_gemm_dx", e, M, K1, D1), ("k_gemm_dx", e, M, E, gates * H)]
+    dws = [(D2, D3), (D1, D2), (K1, D1)]
+    if film:          # the FiLM Dense pair has no image: exact engine whatever the size
+        launches += [("k_gemm_fwd", ENGINE_EXACT, M, 2 * E, H), ("k_gemm_dx", ENGINE_EXACT, M, H, 2 * E)]
+        dws.append((H, 2 * E))
+    dws += [(H, 2 * H), (H, H), (E, 3 * H)] if gru else [(H, 4 * H), (E, 4 * H)]
+    launches += [("k_gemm_dw", ENGINE_SPLIT if bx_dw_usable(bx, M, Kd, Kd, N) else ENGINE_EXACT, Kd, N, M) for Kd, N in dws]
+    if M >= SPLIT_ROWS:       # (the critic's rows: mirrored from 4096 rows on only, like ppo_pass)
+        _, crow = _net_rows(O if c_in is None else c_in, tuple(c_hidden), 1, ACT_ELU, True, M, ppo_opts(dict(gemm_bx=o["gemm_bx"])), False)
+        launches += [r for r in crow if r[0] in GEMM_KERNELS]
+    rows = {}
+    for r in launches:
+        rows[r] = rows.get(r, 0) + 1
+    recurrent = None if gru else ("split" if bx and not (o["bx_debug"] & 256) else "exact")
+    return dict(rows=rows, split=split, recurrent=recurrent, full_tiles=ne % LSTM_ROWS == 0)
