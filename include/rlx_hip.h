@@ -1364,6 +1364,56 @@ int rlx_ppo_lstm_update_f32(rlx_ctx*, const rlx_lstm_policy_desc* desc, float* p
                             int minibatch_size, uint32_t key_io[2], int scheme, int64_t* opt_count_io,
                             const float* lr_schedule, const rlx_ppo_hparams* hp, float* metrics_out, void* stream);
 
+/* ---- TD3 and DDPG: deterministic policy gradients (rl_x/algorithms/td3/flax, rl_x/algorithms/ddpg/flax) ----------------------
+ * SAC's host loop and replay ring (td3/flax/replay_buffer.py and ddpg/flax/replay_buffer.py are sac/flax's file) with a tanh
+ * policy that has no log-std (policy.py:22-44: Dense(H) -> ReLU -> Dense(H) -> ReLU -> Dense(act_dim) -> tanh, the tanh applied
+ * by the entry points below) AND a target copy of it, and nr_critics scalar critics (td3/flax/critic.py:17-53: two, BACK TO BACK
+ * in one flat vector like rlx_redq_update_f32's; ddpg/flax/critic.py: one).  Networks: rlx_mlp_desc with act = RLX_ACT_RELU,
+ * ln_first = 0, has_logstd = 0; FLAT LAYOUT of a network: FastTD3's (above).  Q values are laid out [E, B], critic-major.
+ * Envelope: 1..3 hidden layers, widths multiples of 64 up to 1024, act_dim = pdesc->out_dim in 1..64, qdesc->out_dim = 1,
+ * nr_critics 1 or 2, joint only with nr_critics == 1, smoothing_epsilon == 0 and policy_step, B > 0, a context of world size 1; a
+ * descriptor or size outside it is RLX_EUNSUP, every other bad argument RLX_EINVAL, rlx_last_error() names the rule, and nothing
+ * is written when a check fails.                                                                                                */
+typedef struct rlx_td3_hparams {               /* td3/flax/default_config.py:9-27, ddpg/flax/default_config.py:9-24 */
+  float gamma, tau;
+  float smoothing_epsilon, smoothing_clip_value;   /* target-policy smoothing (td3.py:126-127) */
+  float lr_policy, lr_critic;                  /* host evaluates linear_schedule at each optimiser's OWN count (td3.py:72-79) */
+  float adam_b1, adam_b2, adam_eps;            /* optax.adam defaults 0.9, 0.999, 1e-8 (td3.py:88, :95) */
+  int32_t nr_critics;                          /* 2: TD3 (critic.py:13), 1: DDPG */
+  int32_t joint;                               /* DDPG's order (ddpg.py:118-156): both gradients at the pre-step parameters, no key */
+  int32_t policy_step;                         /* 0: the critic step only, the targets stay (td3.py:266: the delayed policy step) */
+  const float *critic_states, *critic_next_states;   /* as in rlx_redq_hparams: the critics' own observation columns of s / s' */
+} rlx_td3_hparams;
+
+/* get_action (td3.py:107-112, ddpg.py:105-110) and get_deterministic_action (td3.py:203-205): action [N, A] = clip(tanh(policy(obs))
+ * + epsilon normal(subkey, (N, A)), -1, 1) with key, subkey = split(key) -- ONE shape-wide draw, element (n, j) from bits n A + j of
+ * N A; processed_action = low + 0.5 (clip(action, -1, 1) + 1)(high - low) (policy.py:39-44; low / high DEVICE float[A]).
+ * epsilon == 0: the deterministic action, key_io untouched.  rlx_dbg_set_sac_noise(eps_next, .) injects the N(0, 1) draws [N, A]. */
+int rlx_td3_act_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, const float* obs, uint32_t key_io[2], int scheme,
+                    float epsilon, float* action, float* processed_action, int N, const float* low, const float* high, void* stream);
+
+/* the critic loss on given values (td3.py:130-134, meaned over batch and critics, :145): q, q_next DEVICE [E, B], E = nr_critics;
+ * y_out [B] (or NULL) = r + gamma (1 - term) min_e q_next[e]; dq_out [E, B] = 2 (q - y) / (E B); loss_out DEVICE [1] = mean (q -
+ * y)^2, double accumulators in a fixed order. */
+int rlx_td3_losses_f32(rlx_ctx*, const float* q /*[E,B]*/, const float* q_next /*[E,B]*/, const float* rewards,
+                       const float* terminations, int64_t B, const rlx_td3_hparams* hp, float* y_out, float* dq_out, float* loss_out,
+                       void* stream);
+
+/* ONE vector step's optimisation in one call, no host synchronisation: update_critic (td3.py:116-160) and, with hp->policy_step,
+ * update_policy_and_targets (:164-199) -- or, with hp->joint, DDPG's `update` (ddpg.py:114-166).  Critic step: keys = split(key,
+ * B + 1), key = keys[0], row b's smoothing noise from keys[1 + b] (td3.py:149-150; hp->joint: no key is taken);
+ * rlx_dbg_set_sac_noise(eps_next, .) injects the N(0, 1) draws [B, A] instead.  The policy step evaluates the critics AFTER the
+ * critic step's Adam (hp->joint: before it), steps the policy, then moves BOTH targets by tau (ptarget, qtarget); without a policy
+ * step neither target moves.  qparams / qm / qv / qtarget: [E * nq].  states / next_states: the policy's columns [B, pdesc->in_dim].
+ * q_opt_count_io / pi_opt_count_io (HOST): the two optax counts, advanced by 1 and by hp->policy_step.  metrics_out DEVICE
+ * float[5] = {loss/q_loss, gradients/critic_grad_norm, loss/policy_loss, q_value/q_value, gradients/policy_grad_norm}; [2..4] are
+ * left alone without a policy step. */
+int rlx_td3_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, float* ptarget,
+                       const rlx_mlp_desc* qdesc, float* qparams /*[E*nq]*/, float* qm, float* qv, float* qtarget, const float* states,
+                       const float* next_states, const float* actions, const float* rewards, const float* terminations, int64_t B,
+                       uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_td3_hparams* hp,
+                       float* metrics_out /*DEVICE [5]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

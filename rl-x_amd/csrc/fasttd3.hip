@@ -20,7 +20,7 @@
 // like rlx_fastsac_*), and rlx_dbg_set_sac_noise(eps_next, .) injects the given N(0, 1) draws of the exploration noise
 // (rlx_fasttd3_act_f32, [N, A]) and of the smoothing noise (rlx_fasttd3_critic_update_f32, [B, A]) for parity tests.
 // CPU twin: tests/fasttd3_twin.py, pinned by outputs of the reference's own modules and closures (tests/golden/fasttd3_reference.npz).
-#include "net_pass.h"
+#include "dpg.h"
 
 namespace rlx {
 
@@ -146,19 +146,6 @@ __global__ __launch_bounds__(256) void k_td3_policy_seed(const float* __restrict
   if (lane == 0) s_loss[w] = loss;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-}
-
-// d loss / d head [M, A] of the policy through its tanh: (da1 + da2) (1 - a^2), a = the action the critics saw (their input
-// columns [c0, c0 + A), row stride lda), da_k = the critics' input gradients on those columns
-__global__ __launch_bounds__(256) void k_td3_tanh_bwd(const float* __restrict__ x, const float* __restrict__ da1, const float* __restrict__ da2,
-                                                      int lda, int c0, float* __restrict__ dhead, int64_t M, int A) {
-  const int64_t n = M * A;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const int64_t i = e / A;
-    const int j = (int)(e - i * A);
-    const float a = x[i * lda + c0 + j];
-    dhead[e] = (da1[i * lda + c0 + j] + da2[i * lda + c0 + j]) * (1.0f - a * a);
-  }
 }
 
 __global__ __launch_bounds__(256) void k_td3_policy_loss(const float* __restrict__ partial, int n, float inv_b, float* __restrict__ metrics) {
@@ -397,10 +384,8 @@ int rlx_fasttd3_policy_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float
     if (!rc) rc = chain_bwd(ctx, LQ, qparams, xp, ldc, b1, d1, nullptr, dx1, ldc, B, fk.main(), Oc, A);
     if (!rc) rc = fk.join();
     if (rc) return rc;
-    hipLaunchKernelGGL(k_td3_tanh_bwd, dim3(elem_grid(B * A)), dim3(256), 0, st, (const float*)xp, (const float*)dx1, (const float*)dx2, ldc, Oc,
-                       dhead, B, A);
-    RLX_LAUNCH_CHECK();
-    rc = chain_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
+    rc = dpg_tanh_bwd(xp, dx1, dx2, ldc, Oc, dhead, B, A, st);   // (dpg.h: shared with td3.hip)
+    if (!rc) rc = chain_bwd(ctx, LP, pparams, xs, ldp, bp, dhead, gp, nullptr, 0, B, st);
     if (!rc) rc = bwd.finish(st);
     if (rc) return rc;
   }

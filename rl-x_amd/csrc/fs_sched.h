@@ -1,4 +1,4 @@
-// fs_sched.h -- the stream fork / join of the distributional off-policy updates (fastsac.hip, fasttd3.hip: a critic pair whose two
+// fs_sched.h -- the stream fork / join of the twin-critic off-policy updates (fastsac.hip, fasttd3.hip, td3.hip: a critic pair whose two
 // halves go to two streams; espo.hip: the critic step of an epoch) and the deferred parameter-gradient reduction (those three,
 // reppo.hip and mpo.hip: the backward passes of a step gather all their slab partials into one reduction launch).  Nothing here
 // touches the arithmetic; the epilogue rule of the input gradients is net_pass.h's, which includes this file.

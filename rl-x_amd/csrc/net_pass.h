@@ -1,5 +1,6 @@
 // net_pass.h -- the network passes of fastsac.hip, fasttd3.hip, reppo.hip, mpo.hip, fastmpo.hip, espo.hip, tqc.hip, redq.hip, aqe.hip,
-// droq.hip and crossq.hip (the last five through sac_ens.h / sac_ens.hip, the layer they share) on the host side: the launchers of brn.hip (batch
+// droq.hip, crossq.hip and td3.hip (tqc ... crossq through sac_ens.h / sac_ens.hip, the layer they share; td3.hip takes its descriptor
+// rules and row keys from sac_ens.h) on the host side: the launchers of brn.hip (batch
 // renormalisation, the column-statistics layer), the launchers of dense_head.hip, grid sizes, the scratch-arena carve, key splitting, the split-operand weight images of a pass, and the passes
 // themselves -- a Block (Linear -> [Dropout ->] {no norm | LayerNorm | RMSNorm} -> activation) with its forward, backward, input gradient and
 // stage-arena size, and a Chain of up to four blocks plus a dense head.  An algorithm's file keeps its descriptor check, the list

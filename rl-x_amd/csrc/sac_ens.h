@@ -4,6 +4,7 @@
 // descriptor rules, the shapes of a call, host key splitting, and the policy pass that ends in a sample.  An algorithm's file keeps
 // its critic target and loss and its hyper-parameter check; the arena carve and the schedule are tqc.hip's own and, for the other three,
 // redq.hip's redq_loop (redq_loop.h).
+// (td3.hip, whose policy is deterministic, takes the descriptor rules -- det_prologue -- the row keys and the host key split only.)
 #pragma once
 #include "net_pass.h"
 #include "sac_sample.h"
@@ -106,6 +107,19 @@ struct EnsDims {
   int A, Op, Oc, ldc, ldp;
   const float *cs, *cn;
 };
+// the rules below the policy head's, at act_dim A
+static inline int ens_dims(const std::string& f, int A, const rlx_mlp_desc& pd, const rlx_mlp_desc& qd, int q_out, const char* q_out_rule,
+                           const float* states, const float* next_states, const float* critic_states, const float* critic_next_states,
+                           EnsDims* d) {
+  RLX_REQUIRE(qd.out_dim == q_out, RLX_EINVAL, f + ": qdesc->out_dim " + q_out_rule);
+  RLX_REQUIRE(qd.in_dim > A, RLX_EINVAL, f + ": qdesc->in_dim must be critic obs + act_dim");
+  const int Op = pd.in_dim, Oc = qd.in_dim - A;
+  const bool asym = critic_states != nullptr;
+  RLX_REQUIRE((critic_states != nullptr) == (critic_next_states != nullptr) && (asym || Oc == Op), RLX_EINVAL,
+              f + ": critic obs width != policy obs width needs hp->critic_states AND hp->critic_next_states");
+  *d = EnsDims{A, Op, Oc, (Oc + A + 3) & ~3, (Op + 3) & ~3, asym ? critic_states : states, asym ? critic_next_states : next_states};
+  return RLX_OK;
+}
 // The descriptor rules that tie the policy to the critics, under the entry point's name fn; q_out / q_out_rule: the critics' output
 // width and how the message states it.  critic_states / critic_next_states: hp's (both or neither).
 static inline int ens_prologue(const char* fn, const rlx_mlp_desc& pd, const rlx_mlp_desc& qd, int q_out, const char* q_out_rule,
@@ -115,14 +129,14 @@ static inline int ens_prologue(const char* fn, const rlx_mlp_desc& pd, const rlx
   RLX_REQUIRE(pd.out_dim % 2 == 0, RLX_EINVAL, f + ": pdesc->out_dim must be 2 * act_dim");
   const int A = pd.out_dim / 2;
   RLX_REQUIRE(A <= 64, RLX_EUNSUP, f + ": act_dim (pdesc->out_dim / 2) at most 64");
-  RLX_REQUIRE(qd.out_dim == q_out, RLX_EINVAL, f + ": qdesc->out_dim " + q_out_rule);
-  RLX_REQUIRE(qd.in_dim > A, RLX_EINVAL, f + ": qdesc->in_dim must be critic obs + act_dim");
-  const int Op = pd.in_dim, Oc = qd.in_dim - A;
-  const bool asym = critic_states != nullptr;
-  RLX_REQUIRE((critic_states != nullptr) == (critic_next_states != nullptr) && (asym || Oc == Op), RLX_EINVAL,
-              f + ": critic obs width != policy obs width needs hp->critic_states AND hp->critic_next_states");
-  *d = EnsDims{A, Op, Oc, (Oc + A + 3) & ~3, (Op + 3) & ~3, asym ? critic_states : states, asym ? critic_next_states : next_states};
-  return RLX_OK;
+  return ens_dims(f, A, pd, qd, q_out, q_out_rule, states, next_states, critic_states, critic_next_states, d);
+}
+// The same for a deterministic policy (td3.hip): the head is the action's pre-activation, out_dim == act_dim, no log-std half
+static inline int det_prologue(const char* fn, const rlx_mlp_desc& pd, const rlx_mlp_desc& qd, const float* states, const float* next_states,
+                               const float* critic_states, const float* critic_next_states, EnsDims* d) {
+  const std::string f(fn);
+  RLX_REQUIRE(pd.out_dim >= 1 && pd.out_dim <= 64, RLX_EUNSUP, f + ": act_dim (pdesc->out_dim) must be in 1..64");
+  return ens_dims(f, pd.out_dim, pd, qd, 1, "must be 1", states, next_states, critic_states, critic_next_states, d);
 }
 // the fields of SacSampleArgs that hold for a whole call
 static inline SacSampleArgs ens_sample_args(const EnsDims& d, float ls_min, float ls_max, int64_t B) {

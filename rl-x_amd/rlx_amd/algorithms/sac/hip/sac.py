@@ -62,9 +62,9 @@ class SAC:
         self.batch_size = int(config.algorithm.batch_size)
         self.tau = config.algorithm.get("tau", 0.0)                   # (crossq.hip, a subclass, has no target networks and no tau)
         self.gamma = config.algorithm.gamma
-        self.target_entropy = config.algorithm.target_entropy
-        self.log_std_min = float(config.algorithm.log_std_min)
-        self.log_std_max = float(config.algorithm.log_std_max)
+        self.target_entropy = config.algorithm.get("target_entropy", "auto")   # (td3.hip, a subclass, has no entropy term and no log-std)
+        self.log_std_min = float(config.algorithm.get("log_std_min", -20))
+        self.log_std_max = float(config.algorithm.get("log_std_max", 2))
         self.nr_hidden_units = int(config.algorithm.get("nr_hidden_units", None) or config.algorithm.policy_nr_hidden_units)   # (crossq.hip: two widths)
         self.logging_frequency = config.algorithm.logging_frequency
         self.evaluation_frequency = config.algorithm.evaluation_frequency
@@ -210,6 +210,28 @@ class SAC:
         self.ctx.random_bits(sub, bits, self.scheme)
         unit = (((bits >> 9) & 0x7FFFFF) | 0x3F800000).view(t.float32) - 1.0          # jax.random.uniform: mantissa bits -> [0, 1)
         return (unit * 2.0 - 1.0).view(self.nr_envs, self.act_dim)[off:off + nl]
+
+    def act(self, obs, action, processed):
+        """the stochastic action of a vector step into `action`, the env-facing one through processed = (low, half_range, out);
+        returns the advanced key"""
+        return self.ctx.sac_act(self.pdesc, self.pparams, obs, self.key, action, self.log_std_min, self.log_std_max, scheme=self.scheme,
+                                processed=processed, row_offset=getattr(self, "env_id_offset", 0), n_global=self.nr_envs)
+
+    def act_deterministic(self, obs, action):
+        """the evaluation action (tanh(mean), sac.py:217-221) into `action`; returns the env-facing one.  The key stays."""
+        self.ctx.sac_act(self.pdesc, self.pparams, obs, self.key, action, self.log_std_min, self.log_std_max, deterministic=True)
+        return self.processed_action(action)
+
+    def named_metrics(self, m, n_updates):
+        """the logged names of the metric means m over the n_updates updates since the last log"""
+        return {METRIC_NAMES[i]: m[i] for i in range(9)}
+
+    def update_counters(self, nr_updates):
+        return {"steps/nr_updates": nr_updates}
+
+    def logged_lr(self):
+        """lr/learning_rate of a log line"""
+        return self.current_lr()
 
     def policy_obs(self, state):
         """The observation columns the policy reads (the whole row unless the env defines policy_observation_indices)."""
@@ -365,9 +387,7 @@ class SAC:
                 ring_a.copy_(self.warmup_actions(gen))
                 t.addcmul(self._low, t.clamp(ring_a, -1.0, 1.0).add_(1.0), self._half_range, out=self._processed)
             else:
-                self.key = self.ctx.sac_act(self.pdesc, self.pparams, self.policy_obs(env.obs), self.key, ring_a,
-                                            self.log_std_min, self.log_std_max, scheme=self.scheme, processed=fused,
-                                            row_offset=getattr(self, "env_id_offset", 0), n_global=self.nr_envs)
+                self.key = self.act(self.policy_obs(env.obs), ring_a, fused)
             if prev_in_step:
                 env.step_into(self._processed, ring_ns, ring_r, ring_t, prev_obs_out=ring_s)
             else:
@@ -379,9 +399,7 @@ class SAC:
             action = self.warmup_actions(gen)
             t.addcmul(self._low, t.clamp(action, -1.0, 1.0).add_(1.0), self._half_range, out=self._processed)
         else:
-            self.key = self.ctx.sac_act(self.pdesc, self.pparams, self.policy_obs(state), self.key, self.action,
-                                        self.log_std_min, self.log_std_max, scheme=self.scheme, processed=fused,
-                                            row_offset=getattr(self, "env_id_offset", 0), n_global=self.nr_envs)
+            self.key = self.act(self.policy_obs(state), self.action, fused)
             action = self.action
         next_state, reward, terminated, truncated, info = env.step(self._processed)
         fin = info.get("final_observation") if isinstance(info, dict) else None
@@ -420,11 +438,11 @@ class SAC:
                 m = (metric_sum / max(metric_n, 1)).cpu().tolist()     # ONE D2H per logging interval
                 if metric_n and not all(np.isfinite(v) for v in m[:9]):
                     raise FloatingPointError(
-                        "sac.hip: non-finite loss / gradient norm since the last log " + str([round(v, 6) for v in m[:9]]) +
+                        (getattr(self, "_NAME", None) or "sac.hip") + ": non-finite loss / gradient norm since the last log " + str([round(v, 6) for v in m[:9]]) +
                         ".  If the training itself is sane, an operand left the fp16 window of the split-operand GEMM engine "
                         "(|activation or observation| >= 4094, |weight| >= 1023; rl-x_amd/csrc/gemm_bx.h): rerun with "
                         "RLX_GEMM_BX=0 (exact-fp32 MFMA engine) or enable observation normalisation.")
-                combined = {METRIC_NAMES[i]: m[i] for i in range(9)} if metric_n else {}
+                combined = self.named_metrics(m, metric_n) if metric_n else {}
                 if hasattr(env, "pop_episode_stats"):
                     n_done, mean_ret, mean_len = env.pop_episode_stats()
                     nr_episodes += n_done
@@ -436,8 +454,8 @@ class SAC:
                             self.save()
                 combined.update(pending_eval)
                 pending_eval = {}
-                combined.update({"steps/nr_env_steps": global_step, "steps/nr_updates": nr_updates,
-                                 "steps/nr_episodes": nr_episodes, "lr/learning_rate": self.current_lr(),
+                combined.update({"steps/nr_env_steps": global_step, **self.update_counters(nr_updates),
+                                 "steps/nr_episodes": nr_episodes, "lr/learning_rate": self.logged_lr(),
                                  "time/sps": int((global_step - last_log_step) / max(now - last_log_time, 1e-9))})
                 last_log_time, last_log_step = now, global_step
                 metric_sum.zero_()
@@ -462,9 +480,7 @@ class SAC:
             returns, lengths = [], []
             ep_ret, ep_len = t.zeros(ne, device=self.device), t.zeros(ne, device=self.device)
             while len(returns) < episodes:
-                self.ctx.sac_act(self.pdesc, self.pparams, self.policy_obs(state.contiguous()), self.key, action,
-                                 self.log_std_min, self.log_std_max, deterministic=True)
-                state, reward, terminated, truncated, info = env.step(self.processed_action(action))
+                state, reward, terminated, truncated, info = env.step(self.act_deterministic(self.policy_obs(state.contiguous()), action))
                 ep_ret += reward
                 ep_len += 1
                 done = terminated | truncated

@@ -85,6 +85,13 @@ class RedqHparams(Structure):
         ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
 
 
+class Td3Hparams(Structure):
+    """rlx_td3_hparams (td3/flax/default_config.py:9-27, ddpg/flax/default_config.py:9-24)"""
+    _fields_ = [(n, c_float) for n in ("gamma", "tau", "smoothing_epsilon", "smoothing_clip_value", "lr_policy", "lr_critic", "adam_b1",
+                                       "adam_b2", "adam_eps")] + [
+        ("nr_critics", c_int32), ("joint", c_int32), ("policy_step", c_int32), ("critic_states", c_void_p), ("critic_next_states", c_void_p)]
+
+
 class AqeHparams(Structure):
     """rlx_aqe_hparams (aqe/flax/default_config.py:9-28)"""
     _fields_ = [(n, c_float) for n in ("gamma", "tau", "target_entropy", "log_std_min", "log_std_max", "lr_policy", "lr_critic",
@@ -332,6 +339,11 @@ _SIGNATURES = {
     "rlx_redq_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(RedqHparams)] + [c_void_p] * 6),
     "rlx_redq_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                             + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(RedqHparams), c_void_p, POINTER(c_int32), c_void_p]),
+    "rlx_td3_act_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, _U32P, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p]),
+    "rlx_td3_losses_f32": (c_int, [c_void_p] * 5 + [c_int64, POINTER(Td3Hparams)] + [c_void_p] * 4),
+    "rlx_td3_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 9
+                           + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(Td3Hparams), c_void_p, c_void_p]),
     "rlx_aqe_losses_f32": (c_int, [c_void_p] * 8 + [c_int64, POINTER(AqeHparams)] + [c_void_p] * 6),
     "rlx_aqe_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 12
                            + [c_int64, _U32P, c_int, _I64P, _I64P, POINTER(AqeHparams), c_void_p, c_void_p]),
@@ -1271,6 +1283,36 @@ class Ctx:
             _ptr(critic_states, f, True), int(states.shape[0]), ctypes.byref(cnt), ctypes.byref(hp), _ptr(metrics_out, f), _stream()),
             "rlx_fasttd3_policy_update_f32")
         return cnt.value
+
+    # ---- TD3, DDPG (rl_x/algorithms/td3/flax, rl_x/algorithms/ddpg/flax)
+    def td3_act(self, pdesc, pparams, obs, key, action, processed, low, high, epsilon, scheme=THREEFRY_PARTITIONABLE):
+        """get_action: (action for the ring, processed action for the env); epsilon 0: the deterministic action, the key stays.
+        Returns the new key."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        _check(self.lib.rlx_td3_act_f32(self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(obs, f), k, scheme, float(epsilon),
+                                        _ptr(action, f), _ptr(processed, f), int(obs.shape[0]), _ptr(low, f), _ptr(high, f), _stream()),
+               "rlx_td3_act_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32)
+
+    def td3_losses(self, q, q_next, rewards, terminations, hp, dq_out, loss_out, y_out=None):
+        """TD3's critic loss on given values (include/rlx_hip.h): q / q_next / dq_out [E, B], loss_out [1], y_out None or [B]."""
+        f = self.torch.float32
+        _check(self.lib.rlx_td3_losses_f32(self.h, _ptr(q, f, True), _ptr(q_next, f, True), _ptr(rewards, f), _ptr(terminations, f),
+                                           int(rewards.shape[0]), ctypes.byref(hp), _ptr(y_out, f, True), _ptr(dq_out, f, True),
+                                           _ptr(loss_out, f, True), _stream()), "rlx_td3_losses_f32")
+
+    def td3_update(self, pdesc, pparams, pm, pv, ptarget, qdesc, qparams, qm, qv, qtarget, batch, key, q_count, pi_count, hp, metrics_out,
+                   scheme=THREEFRY_PARTITIONABLE):
+        """batch = (states, next_states, actions, rewards, terminations).  Returns (new_key, new_q_count, new_pi_count)."""
+        f = self.torch.float32
+        k = _key_arr(key)
+        qc, pc = c_int64(int(q_count)), c_int64(int(pi_count))
+        _check(self.lib.rlx_td3_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), _ptr(ptarget, f), ctypes.byref(qdesc), _ptr(qparams, f),
+            _ptr(qm, f), _ptr(qv, f), _ptr(qtarget, f), *[_ptr(x, f) for x in batch], int(batch[3].numel()), k, scheme, ctypes.byref(qc),
+            ctypes.byref(pc), ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_td3_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), qc.value, pc.value
 
     # ---- REPPO (rl_x/algorithms/reppo/pytorch)
     def reppo_param_count(self, desc, net):
