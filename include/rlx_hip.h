@@ -1414,6 +1414,53 @@ int rlx_td3_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, floa
                        uint32_t key_io[2], int scheme, int64_t* q_opt_count_io, int64_t* pi_opt_count_io, const rlx_td3_hparams* hp,
                        float* metrics_out /*DEVICE [5]*/, void* stream);
 
+/* =================================== PPO-DTRL ============================================
+ * PPO with differentiable trust-region layers (rl_x/algorithms/ppo_dtrl/flax_full_jit; Otto et al. 2021, arXiv 2101.09207).  The
+ * nets are the full-jit PPO's (policy.py, critic.py: arch B with the trailing policy_logstd), so acting, next values and GAE are
+ * rlx_ppo_rollout_f32 / rlx_actor_critic_fwd_sample_f32, rlx_ppo_next_values_f32 and rlx_gae_f32 (ppo_dtrl.py:133-180).  What
+ * this section adds is loss_fn (ppo_dtrl.py:184-245) with kl_projection, kl_cov_proj and its hand-written backward rule, and
+ * entropy_projection (trust_region_layer.py:8-233), and the update loop around it.
+ * Envelope: pdesc / cdesc with 1..3 hidden layers, act ELU or TANH, widths multiples of 64 up to 1024 (behind ln_first's LayerNorm:
+ * 768 with ELU, 512 with TANH), pdesc: out_dim = action dim 1..64 (a row's components sit in one wave), has_logstd 1; cdesc:
+ * out_dim 1, has_logstd 0; any minibatch of at least two rows.  A descriptor outside that is RLX_EUNSUP, every other bad argument
+ * RLX_EINVAL; rlx_last_error() names the rule.  All passes run on the exact-fp32 engine.                                       */
+typedef struct rlx_dtrl_hparams { /* ppo_dtrl/flax_full_jit/default_config.py:10-32 */
+  float clip_range, entropy_coef, critic_coef;
+  float max_grad_norm;               /* optax.clip_by_global_norm (ppo_dtrl.py:98, :107); <= 0: none */
+  float adam_b1, adam_b2, adam_eps;  /* optax.adam defaults 0.9, 0.999, 1e-8 */
+  float mean_bound, cov_bound;       /* the two KL bounds of kl_projection (ppo_dtrl.py:193) */
+  float trust_region_coef;           /* weight of the regression loss (ppo_dtrl.py:227) */
+  float total_timesteps;             /* the entropy bound decays as 0.5^(10 global_step / total_timesteps) (ppo_dtrl.py:191) */
+  const float* critic_states;        /* as in rlx_ppo_hparams: the critic's own observation columns of the same rows, or NULL */
+} rlx_dtrl_hparams;
+
+/* loss_fn meaned over ONE minibatch of given rows and its gradients (ppo_dtrl.py:184-245, :259-262, :272-286), no optimiser step:
+ * states [mb, pdesc->in_dim], actions / old_means [mb, A], old_logstd [A] (the rollout policy), log_probs / returns / advantages
+ * [mb] (advantages as stored: normalised here with the minibatch's mean and population std + 1e-8); global_step as the reference
+ * passes it, a float.  pgrads / cgrads: DEVICE, the flat layouts of the parameters (d policy_logstd in its slot).  metrics: DEVICE
+ * float[12] = {policy_gradient_loss, critic_loss, entropy_loss, trust_region_loss, approx_kl, clip_fraction, eta_mu, eta_cov,
+ * unprojected_kl_mean, projected_kl_mean, unprojected_kl_cov, projected_kl_cov} (ppo_dtrl.py:230-243).  The covariance projection
+ * is solved once per call (every row has the same std pair) by a bracketed Newton iteration in double; its backward rule
+ * (trust_region_layer.py:82-135) is applied per row, with the reference's clamp of d_cov_pred at 1e-20.                          */
+int rlx_dtrl_loss_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, const float* pparams, float* pgrads, const rlx_mlp_desc* cdesc,
+                      const float* cparams, float* cgrads, const float* states, const float* actions, const float* old_means,
+                      const float* old_logstd, const float* log_probs, const float* returns, const float* advantages, int mb,
+                      float global_step, const rlx_dtrl_hparams* hp, float* metrics /*DEVICE [12]*/, void* stream);
+
+/* the whole `update` of one learning iteration (ppo_dtrl.py:248-300): nr_epochs * (T N / minibatch_size) minibatch steps on both
+ * networks, each loss_fn + optax.chain(clip_by_global_norm, adam), in one call without host synchronisation.  key_io, scheme,
+ * opt_count_io (HOST, advanced by the number of steps) and lr_schedule (HOST float per step) as in rlx_ppo_update_f32; the
+ * permutation is drawn as PPO's (:264-267) and a matching rlx_ppo_prefetch_permutation is consumed.  old_means: DEVICE [T N, A],
+ * or NULL: the call computes them from the incoming policy parameters before its first step (they are the rollout's means when
+ * nothing has changed the parameters since).  The rollout policy's logstd is read from pparams at entry (:162).  metrics_out:
+ * DEVICE float[steps, 14] = the 12 metrics above + policy_grad_norm + critic_grad_norm (before clipping).  A step whose gradient
+ * norm is not finite is skipped on the device, as everywhere in this library.                                               */
+int rlx_dtrl_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, float* pm, float* pv, const rlx_mlp_desc* cdesc,
+                        float* cparams, float* cm, float* cv, const float* states, const float* actions, const float* old_means,
+                        const float* log_probs, const float* returns, const float* advantages, int T, int N, int nr_epochs,
+                        int minibatch_size, uint32_t key_io[2], int scheme, int64_t* opt_count_io, const float* lr_schedule,
+                        float global_step, const rlx_dtrl_hparams* hp, float* metrics_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

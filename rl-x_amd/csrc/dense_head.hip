@@ -434,7 +434,7 @@ static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, 
   RLX_REQUIRE(D % 64 == 0 && D <= (th ? 512 : 768), RLX_EUNSUP, "norm_act: the row-norm kernels hold a row in one wave");
   if (ln && o.act == RLX_ACT_RELU && o.eps == 1e-6f) return launch_drop_ln_relu<BWD>(o, p, Z, Y, part, grid, M, 8 * row, st, dk);
   RLX_REQUIRE(o.drop == 0.f, RLX_EUNSUP, "norm_act: dropout has a kernel in front of (LayerNorm eps 1e-6, ReLU) only");
-  if (ln && o.act == RLX_ACT_SILU)      // (the activation as a run-time argument: k_ln_act_wide takes the switch once per launch)
+  if (ln && (o.act == RLX_ACT_SILU || o.act == RLX_ACT_ELU))   // (a run-time argument: k_ln_act_wide takes the switch once per launch)
     hipLaunchKernelGGL(k_ln_act_wide<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.act, o.eps);
   else if (ln && th)
     hipLaunchKernelGGL(k_mpo_ln_tanh<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.eps);

@@ -211,6 +211,12 @@ class EspoHparams(Structure):
                                        "adam_eps")] + [("delta_op", c_int32)]
 
 
+class DtrlHparams(Structure):
+    """rlx_dtrl_hparams (ppo_dtrl/flax_full_jit/default_config.py:10-32)"""
+    _fields_ = [(n, c_float) for n in ("clip_range", "entropy_coef", "critic_coef", "max_grad_norm", "adam_b1", "adam_b2", "adam_eps",
+                                       "mean_bound", "cov_bound", "trust_region_coef", "total_timesteps")] + [("critic_states", c_void_p)]
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -423,6 +429,10 @@ _SIGNATURES = {
     "rlx_espo_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                     c_int, _I64P, c_float, POINTER(EspoHparams), c_void_p, POINTER(c_int32), c_void_p]),
+    "rlx_dtrl_loss_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, _DESCP] + [c_void_p] * 9 + [c_int, c_float, POINTER(DtrlHparams),
+                                  c_void_p, c_void_p]),
+    "rlx_dtrl_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 9 + [c_int] * 4 +
+                            [_U32P, c_int, _I64P, _F32HP, c_float, POINTER(DtrlHparams), c_void_p, c_void_p]),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1474,6 +1484,32 @@ class Ctx:
             _ptr(advantages, f), int(states.shape[0]), _ptr(idx, i32), int(idx.shape[1]), int(idx.shape[0]), ctypes.byref(cnt), float(lr),
             ctypes.byref(hp), _ptr(metrics_out, f), ctypes.byref(run), _stream()), "rlx_espo_update_f32")
         return run.value, cnt.value
+
+    # ---- PPO-DTRL (rl_x/algorithms/ppo_dtrl/flax_full_jit)
+    def dtrl_loss(self, pdesc, pparams, pgrads, cdesc, cparams, cgrads, states, actions, old_means, old_logstd, log_probs, returns,
+                  advantages, global_step, hp, metrics):
+        """loss_fn on one minibatch of given rows: gradients of both nets and the 12 metrics, no optimiser step"""
+        f = self.torch.float32
+        _check(self.lib.rlx_dtrl_loss_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pgrads, f), ctypes.byref(cdesc), _ptr(cparams, f), _ptr(cgrads, f),
+            _ptr(states, f), _ptr(actions, f), _ptr(old_means, f), _ptr(old_logstd, f), _ptr(log_probs, f), _ptr(returns, f),
+            _ptr(advantages, f), int(actions.shape[0]), float(global_step), ctypes.byref(hp), _ptr(metrics, f), _stream()), "rlx_dtrl_loss_f32")
+
+    def dtrl_update(self, pdesc, pparams, pm, pv, cdesc, cparams, cm, cv, states, actions, old_means, log_probs, returns, advantages,
+                    nr_epochs, minibatch_size, key, opt_count, lr_schedule, global_step, hp, metrics_out, scheme=THREEFRY_PARTITIONABLE):
+        """The whole update of one iteration; arrays time-major [T, N, .]; old_means None: computed from the incoming policy.
+        metrics_out float [nr_epochs * T N / minibatch_size, 14] -> (new_key, new_opt_count)"""
+        f = self.torch.float32
+        T, N = log_probs.shape
+        k = _key_arr(key)
+        cnt = c_int64(int(opt_count))
+        lr = np.ascontiguousarray(lr_schedule, dtype=np.float32)
+        _check(self.lib.rlx_dtrl_update_f32(
+            self.h, ctypes.byref(pdesc), _ptr(pparams, f), _ptr(pm, f), _ptr(pv, f), ctypes.byref(cdesc), _ptr(cparams, f), _ptr(cm, f),
+            _ptr(cv, f), _ptr(states, f), _ptr(actions, f), _ptr(old_means, f, True), _ptr(log_probs, f), _ptr(returns, f),
+            _ptr(advantages, f), T, N, nr_epochs, minibatch_size, k, scheme, ctypes.byref(cnt), lr.ctypes.data_as(_F32HP), float(global_step),
+            ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_dtrl_update_f32")
+        return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
