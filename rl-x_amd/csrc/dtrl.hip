@@ -500,8 +500,8 @@ int rlx_dtrl_update_f32(rlx_ctx* ctx, const rlx_mlp_desc* pdesc, float* pparams,
   int rc = dt_check_hp(hp, f);
   if (rc) return rc;
   const int64_t B = (int64_t)T * N;
-  RLX_REQUIRE(T > 0 && N > 0 && nr_epochs > 0 && minibatch_size > 0 && B % minibatch_size == 0, RLX_EINVAL,
-              f + ": batch (T*N) must be a positive multiple of minibatch_size");
+  RLX_REQUIRE(T > 0 && N > 0 && nr_epochs > 0, RLX_EINVAL, f + ": T, N and nr_epochs must be positive");
+  RLX_REQUIRE(minibatch_size > 0 && B % minibatch_size == 0, RLX_EINVAL, f + ": batch (T*N) must be a positive multiple of minibatch_size");
   RLX_REQUIRE(B <= INT32_MAX, RLX_EINVAL, f + ": T*N must fit the permutation's int32 indices");
   RLX_REQUIRE(*opt_count_io >= 0, RLX_EINVAL, f + ": *opt_count_io >= 0");
   RLX_REQUIRE(ctx->world == 1, RLX_EUNSUP, f + ": no data-parallel form (the context's world size must be 1)");

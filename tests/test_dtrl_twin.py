@@ -46,3 +46,38 @@ def test_without_projections_the_twin_is_ppo():
         assert abs(met[I[k]] - m0[k]) < 1e-12, k
     assert np.abs(gp - gp0).max() < 1e-12 and np.abs(gc - gc0).max() < 1e-12 and np.abs(gp0).max() > 1e-4
 
+
+
+def test_critic_states_equal_to_states_change_no_bit():
+    """cstates = states is the shared-observation twin, bit for bit; and the defaults of case() draw what they drew before it had
+    options (the numbers the 60 GPU cases were measured on)"""
+    c = tw.case(117, 17, 11, 1, 1, 0)
+    assert c["cstates"] is None
+    base, same = tw.run_case(c), tw.run_case(dict(c, cstates=c["states"].copy()))
+    assert base[0] == same[0]
+    for a, b in zip(base[1:4], same[1:4]):
+        assert np.array_equal(a, b)
+    rng = np.random.default_rng(117)
+    pp = rng.normal(0, 0.12, c["pspec"].n_params)
+    assert np.array_equal(np.asarray(pp[:c["pspec"].logstd], np.float32).astype(np.float64), c["pp"][:c["pspec"].logstd])
+
+
+def test_permuted_critic_columns_with_permuted_weight_rows_change_nothing():
+    """the critic reads cstates and nothing else does: permuting its observation columns together with the rows of its first-layer
+    weight leaves the loss and the policy gradient where they were (1e-12), and moves the critic's gradient rows with them"""
+    c = tw.case(31, 3, 9, 1, 1, 0, obs=5, cobs=11, chidden=(128, 64))
+    assert c["cspec"].in_dim == 11 and c["pspec"].in_dim == 5 and c["cstates"].shape == (9, 11)
+    perm = np.random.default_rng(0).permutation(11)
+    W = c["cspec"].layers[0]
+    n_w = 11 * W["out"]
+    cp2 = c["cp"].copy()
+    cp2[W["W"]:W["W"] + n_w] = c["cp"][W["W"]:W["W"] + n_w].reshape(11, -1)[perm].reshape(-1)
+    base, moved = tw.run_case(c), tw.run_case(dict(c, cp=cp2, cstates=c["cstates"][:, perm]))
+    assert abs(base[0] - moved[0]) < 1e-12 and np.abs(base[1] - moved[1]).max() < 1e-12
+    assert np.abs(base[2] - moved[2]).max() < 1e-12 and np.abs(base[2]).max() > 1e-4
+    g0 = base[3].copy()
+    g0[W["W"]:W["W"] + n_w] = base[3][W["W"]:W["W"] + n_w].reshape(11, -1)[perm].reshape(-1)
+    assert np.abs(g0 - moved[3]).max() < 1e-12 and np.abs(base[3][W["W"]:W["W"] + n_w]).max() > 1e-6
+    # and the critic does not read the policy's observations any more
+    other = tw.run_case(dict(c, cstates=c["cstates"] + 1.0))
+    assert np.abs(other[3] - base[3]).max() > 1e-6 and np.array_equal(other[2], base[2])
