@@ -1461,6 +1461,51 @@ int rlx_dtrl_update_f32(rlx_ctx*, const rlx_mlp_desc* pdesc, float* pparams, flo
                         int minibatch_size, uint32_t key_io[2], int scheme, int64_t* opt_count_io, const float* lr_schedule,
                         float global_step, const rlx_dtrl_hparams* hp, float* metrics_out, void* stream);
 
+/* =================================== banded attention and the transformer encoder ============================================
+ * The memory of the reference's ppo_transformer policy (rl_x/algorithms/ppo_transformer/flax_full_jit/policy.py): multi-head
+ * self-attention over an environment's token sequence under the AND of a causal band of tf_context_len keys, "same episode segment"
+ * (the running count of done flags, policy.py:322-336) and "token present" (the padding of a fresh history, :315, :89-92), and the
+ * pre-norm encoder layer around it (:57-123).  A library component like rlx_brn_f32: the plugin above it is not part of this
+ * section, and positional encoding and the observation encoder stay with the policy.
+ *
+ * Attention (replaces nn.MultiHeadDotProductAttention's dot_product_attention under `keep`, policy.py:77-110).  All DEVICE:
+ * qkv float32 [S T, 3 d_model], d_model = nhead head_dim, columns q | k | v, each head-major (what one fused QKV GEMM writes);
+ * seg int32 [S, T], non-decreasing along T; valid uint8 [S, T].  Query i of a sequence attends key j iff 0 <= i - j < window,
+ * seg[i] == seg[j], valid[i] and valid[j].  fp32 throughout; the query is scaled by head_dim^-0.5 before the dot product (Flax's
+ * order); masked logits take probability exactly 0; softmax with the row maximum subtracted.  out [S T, d_model] (heads
+ * concatenated), lse [S T, nhead] the rows' log-sum-exp.  d_out == NULL: forward only.  Else the call also runs the backward from
+ * d_out [S T, d_model] into dqkv [S T, 3 d_model] (the qkv layout: it feeds the QKV GEMM's backward), flash-style from out and lse,
+ * every sum in a fixed order (identical calls give identical bits).
+ * ROWS WITH valid == 0 ARE DON'T-CARE BY CONTRACT: the reference softmaxes such a fully masked row to a uniform one that no valid
+ * row ever reads.  Here their out and lse are 0, their dqkv is exactly 0, and their d_out reaches nothing.
+ * Envelope: head_dim in {16, 32, 64}, nhead <= 16, 1 <= window <= 64, T >= 1, S >= 1 (T and window need not be multiples of
+ * anything); outside it RLX_EUNSUP, rlx_last_error() names the field.  qkv, out, d_out, dqkv 16-byte aligned.                */
+int rlx_band_attn_f32(rlx_ctx*, const float* qkv, const int32_t* seg, const uint8_t* valid, int64_t S, int64_t T, int nhead, int head_dim,
+                      int window, float* out, float* lse, const float* d_out /*NULL: forward only*/, float* dqkv, void* stream);
+
+/* The encoder stack (TransformerEncoder, policy.py:126-158; default_config.py: tf_d_model, tf_nhead, tf_dim_feedforward,
+ * tf_num_layers, tf_context_len, tf_layer_norm_eps, tf_dropout).  Per layer (policy.py:108-121):
+ *   x += Wo attention(ln1(x) Wqkv + bqkv) + bo;   x += W2 relu(W1 ln2(x) + b1) + b2
+ * FLAT LAYOUT, per layer, in this order: ln1 scale [d], ln1 bias [d], Wqkv [d, 3 d], bqkv [3 d], Wo [d, d], bo [d], ln2 scale [d],
+ * ln2 bias [d], W1 [d, ff], b1 [ff], W2 [ff, d], b2 [d] (rlx_tf_param_count; INTEGRATION.md maps Flax's kernels onto it).
+ * Envelope: d_model a multiple of 64 up to 512 and of nhead, dim_ff a multiple of 4, 1 <= n_layers <= 4, dropout 0 (a non-zero
+ * rate is refused), and the attention's; outside it RLX_EUNSUP.                                                              */
+typedef struct rlx_tf_desc {
+  int32_t d_model, nhead, dim_ff, n_layers;
+  int32_t window;                /* tf_context_len */
+  float ln_eps;                  /* tf_layer_norm_eps (1e-5) */
+  float dropout;                 /* tf_dropout: must be 0 */
+} rlx_tf_desc;
+int64_t rlx_tf_param_count(const rlx_tf_desc*);   /* -1 for a descriptor without layers or widths */
+
+/* TransformerEncoder.__call__ (policy.py:135-158) on x [S T, d_model] under seg / valid as above -> out [S T, d_model].  d_out ==
+ * NULL: forward only.  Else also the backward from d_out [S T, d_model]: grads (the flat layout, every entry written) and dx
+ * [S T, d_model], activations in the context's scratch arena.  Rows with valid == 0: out is don't-care, d_out is not read into
+ * anything, dx is exactly 0.  GEMMs on the exact-fp32 engine below 4096 rows, on the split-operand engine from there.       */
+int rlx_tf_encoder_f32(rlx_ctx*, const rlx_tf_desc*, const float* params, const float* x /*[S*T, d_model]*/, const int32_t* seg,
+                       const uint8_t* valid, int64_t S, int64_t T, float* out, const float* d_out /*NULL: forward only*/, float* grads,
+                       float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

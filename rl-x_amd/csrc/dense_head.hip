@@ -427,11 +427,20 @@ int launch_normal_noise(float* out, int64_t n, uint32_t k0, uint32_t k1, int sch
 
 template <bool BWD>
 static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
-                      const DropKeys* dk) {
+                      const DropKeys* dk, const NormRes* res) {
   const int D = o.out;
   const size_t row = BWD ? (size_t)D * sizeof(float) : 0;   // LDS: four waves of [dg | db] (LayerNorm) or [dg] (RMSNorm)
   const bool ln = o.norm == NORM_LAYER, th = o.act == RLX_ACT_TANH;
   RLX_REQUIRE(D % 64 == 0 && D <= (th ? 512 : 768), RLX_EUNSUP, "norm_act: the row-norm kernels hold a row in one wave");
+  if (ln && o.act == RLX_ACT_NONE && o.eps > 0.f && o.drop == 0.f) {   // the pre-norm transformer layer's pair (tf_encoder.h)
+    RLX_REQUIRE(!res || res->add, RLX_EUNSUP, "norm_act: a residual needs its addend");
+    RLX_REQUIRE(!res || BWD || res->out, RLX_EUNSUP, "norm_act: the forward residual needs a place for the sum");
+    hipLaunchKernelGGL(k_ln_plain<BWD>, dim3(grid), dim3(256), 8 * row, st, Z, Y, p + o.g, p + o.be, part, M, D, o.eps,
+                       res ? res->add : nullptr, res ? res->out : nullptr);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+  }
+  RLX_REQUIRE(!res, RLX_EUNSUP, "norm_act: the residual rides on (LayerNorm, no activation) only");
   if (ln && o.act == RLX_ACT_RELU && o.eps == 1e-6f) return launch_drop_ln_relu<BWD>(o, p, Z, Y, part, grid, M, 8 * row, st, dk);
   RLX_REQUIRE(o.drop == 0.f, RLX_EUNSUP, "norm_act: dropout has a kernel in front of (LayerNorm eps 1e-6, ReLU) only");
   if (ln && (o.act == RLX_ACT_SILU || o.act == RLX_ACT_ELU))   // (a run-time argument: k_ln_act_wide takes the switch once per launch)
@@ -445,8 +454,8 @@ static int norm_act_t(const Block& o, const float* p, const float* Z, float* Y, 
   return RLX_OK;
 }
 int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
-             const DropKeys* dk) {
-  return part ? norm_act_t<true>(o, p, Z, Y, part, grid, M, st, dk) : norm_act_t<false>(o, p, Z, Y, part, grid, M, st, dk);
+             const DropKeys* dk, const NormRes* res) {
+  return part ? norm_act_t<true>(o, p, Z, Y, part, grid, M, st, dk, res) : norm_act_t<false>(o, p, Z, Y, part, grid, M, st, dk, res);
 }
 
 }  // namespace rlx

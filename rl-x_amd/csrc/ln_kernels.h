@@ -109,6 +109,84 @@ __global__ __launch_bounds__(256) void k_ln_act_wide(const float* __restrict__ Z
   else ln_act_body<BWD, 12>(Z, Y, g, be, partials, M, D, act, eps);
 }
 
+// LayerNorm with NO activation at a caller-given eps (the pre-norm transformer layer's ln1 / ln2, tf_layer_norm_eps;
+// ppo_transformer/flax_full_jit/policy.py:74-75), D <= 768, with the residual add next to it riding along (net_pass.h: NormRes):
+//   fwd: z = Z (+ add, the sum stored to out), Y = LN(z) g + b
+//   bwd: dZ = LNbwd(dY) (+ add, the gradient arriving over the residual branch, added last) into out when given, else over Y;
+//        partials as ln_act_body's.  Same statistics ("fast variance") and the same partial order as ln_act_body.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_ln_plain(const float* __restrict__ Z, float* Y, const float* __restrict__ g,
+                                                  const float* __restrict__ be, float* __restrict__ partials, int64_t M, int D, float eps,
+                                                  const float* add, float* out) {
+  constexpr int NJMAX = 12;
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // bwd: [4][2*D]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int NJ = D >> 6;
+  float gam[NJMAX], bet[NJMAX], dg[NJMAX], db[NJMAX];
+#pragma unroll
+  for (int j = 0; j < NJMAX; ++j) {
+    gam[j] = j < NJ ? g[lane + 64 * j] : 0.f;
+    bet[j] = (!BWD && j < NJ) ? be[lane + 64 * j] : 0.f;
+    dg[j] = db[j] = 0.f;
+  }
+  const float invD = 1.0f / (float)D;
+  float* dst = (BWD && out) ? out : Y;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + w; row < M; row += (int64_t)gridDim.x * 4) {
+    float z[NJMAX], dy[NJMAX], ad[NJMAX];
+    float s = 0.f, ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j) {
+      const int64_t at = row * D + lane + 64 * j;
+      z[j] = j < NJ ? Z[at] : 0.f;
+      ad[j] = (add && j < NJ) ? add[at] : 0.f;
+      if (BWD) dy[j] = j < NJ ? Y[at] : 0.f;
+      if (!BWD && add) {
+        z[j] += ad[j];
+        if (j < NJ) out[at] = z[j];
+      }
+      s += z[j];
+      ss += z[j] * z[j];
+    }
+    s = wave_sum(s);
+    ss = wave_sum(ss);
+    const float mean = s * invD;
+    const float rstd = rsqrtf(fmaxf(0.f, ss * invD - mean * mean) + eps);
+    if (!BWD) {
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) Y[row * D + lane + 64 * j] = (z[j] - mean) * rstd * gam[j] + bet[j];
+    } else {
+      float m1 = 0.f, m2 = 0.f, xh[NJMAX], dxh[NJMAX];
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j) {
+        xh[j] = (z[j] - mean) * rstd;
+        const float d = (j < NJ) ? dy[j] : 0.f;
+        dg[j] += d * xh[j];
+        db[j] += d;
+        dxh[j] = d * gam[j];
+        m1 += dxh[j];
+        m2 += dxh[j] * xh[j];
+      }
+      m1 = wave_sum(m1) * invD;
+      m2 = wave_sum(m2) * invD;
+#pragma unroll
+      for (int j = 0; j < NJMAX; ++j)
+        if (j < NJ) dst[row * D + lane + 64 * j] = rstd * (dxh[j] - m1 - xh[j] * m2) + ad[j];
+    }
+  }
+  if (BWD) {
+#pragma unroll
+    for (int j = 0; j < NJMAX; ++j)
+      if (j < NJ) {
+        smem[w * 2 * D + lane + 64 * j] = dg[j];
+        smem[w * 2 * D + D + lane + 64 * j] = db[j];
+      }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * D; i += 256)
+      partials[(int64_t)blockIdx.x * 2 * D + i] = (smem[i] + smem[2 * D + i]) + (smem[4 * D + i] + smem[6 * D + i]);
+  }
+}
+
 // two nets of the same shape in one launch (grid.y == 2): blockIdx.y == 1 takes {Z, Y, g, partials} from tw; its LayerNorm bias
 // sits at the same distance from its scale as the first net's (same parameter layout)
 template <bool BWD>

@@ -48,8 +48,12 @@ struct DropKeys { uint32_t k0, k1; int scheme; uint32_t base, stride, count; int
 // row norm + activation of a block over [M, out] (dense_head.hip).  part == NULL: forward Y = act(norm(Z)); else backward: dY (in
 // Y) -> dZ, per-workgroup partials [grid][norm_part_width].  RLX_EUNSUP for a (norm, act) pair without a kernel, and for dropout
 // in front of any other pair than (LayerNorm eps 1e-6, ReLU).  Z stays pre-dropout: both directions regenerate the mask from dk.
+// res (optional; the pair (LayerNorm at the block's eps, no activation) only -- the pre-norm transformer layer's, tf_encoder.h --
+// RLX_EUNSUP elsewhere): the residual add next to the norm rides on it.  Forward: the norm reads Z + add and stores that sum to out
+// [M, D].  Backward: the input gradient is LNbwd(dY) + add, written to out when that is not NULL (else over Y); Z is the stored sum.
+struct NormRes { const float* add; float* out; };
 int norm_act(const Block& o, const float* p, const float* Z, float* Y, float* part, int grid, int64_t M, hipStream_t st,
-             const DropKeys* dk = nullptr);
+             const DropKeys* dk = nullptr, const NormRes* res = nullptr);
 static inline int norm_part_width(const Block& o) { return (o.be >= 0 ? 2 : 1) * o.out; }   // [d scale | d bias] or [d scale]
 
 // ---- sizes and grids

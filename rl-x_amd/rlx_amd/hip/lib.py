@@ -217,6 +217,21 @@ class DtrlHparams(Structure):
                                        "mean_bound", "cov_bound", "trust_region_coef", "total_timesteps")] + [("critic_states", c_void_p)]
 
 
+class TfDesc(Structure):
+    """rlx_tf_desc: the pre-norm transformer encoder (ppo_transformer/flax_full_jit/default_config.py:26-33)"""
+    _fields_ = [("d_model", c_int32), ("nhead", c_int32), ("dim_ff", c_int32), ("n_layers", c_int32), ("window", c_int32),
+                ("ln_eps", c_float), ("dropout", c_float)]
+
+
+def tf_desc(d_model=128, nhead=4, dim_ff=512, n_layers=2, window=16, ln_eps=1e-5, dropout=0.0):
+    return TfDesc(int(d_model), int(nhead), int(dim_ff), int(n_layers), int(window), float(ln_eps), float(dropout))
+
+
+def tf_param_count(desc):
+    """floats of the encoder's flat parameter vector (include/rlx_hip.h: the layout); host only"""
+    return int(load_library().rlx_tf_param_count(ctypes.byref(desc)))
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -433,6 +448,9 @@ _SIGNATURES = {
                                   c_void_p, c_void_p]),
     "rlx_dtrl_update_f32": (c_int, [c_void_p, _DESCP, c_void_p, c_void_p, c_void_p, _DESCP] + [c_void_p] * 9 + [c_int] * 4 +
                             [_U32P, c_int, _I64P, _F32HP, c_float, POINTER(DtrlHparams), c_void_p, c_void_p]),
+    "rlx_band_attn_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int] + [c_void_p] * 5),
+    "rlx_tf_param_count": (c_int64, [POINTER(TfDesc)]),
+    "rlx_tf_encoder_f32": (c_int, [c_void_p, POINTER(TfDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 5),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1510,6 +1528,24 @@ class Ctx:
             _ptr(advantages, f), T, N, nr_epochs, minibatch_size, k, scheme, ctypes.byref(cnt), lr.ctypes.data_as(_F32HP), float(global_step),
             ctypes.byref(hp), _ptr(metrics_out, f), _stream()), "rlx_dtrl_update_f32")
         return np.array([k[0], k[1]], dtype=np.uint32), cnt.value
+
+    # ---- banded attention and the transformer encoder (attn.hip)
+    def band_attn(self, qkv, seg, valid, nhead, window, out, lse, d_out=None, dqkv=None):
+        """Banded, segment- and padding-masked attention on qkv [S T, 3 d_model] with seg int32 [S, T] and valid uint8 [S, T]:
+        out [S T, d_model], lse [S T, nhead]; with d_out also the backward into dqkv (include/rlx_hip.h: rlx_band_attn_f32)."""
+        f, t = self.torch.float32, self.torch
+        S, T = (int(v) for v in seg.shape)
+        _check(self.lib.rlx_band_attn_f32(self.h, _ptr(qkv, f), _ptr(seg, t.int32), _ptr(valid, t.uint8), S, T, int(nhead),
+                                          int(qkv.shape[1]) // (3 * int(nhead)), int(window), _ptr(out, f), _ptr(lse, f),
+                                          _ptr(d_out, f, True), _ptr(dqkv, f, True), _stream()), "rlx_band_attn_f32")
+
+    def tf_encoder(self, desc, params, x, seg, valid, out, d_out=None, grads=None, dx=None):
+        """The encoder stack on x [S T, d_model] -> out; with d_out also grads (flat layout) and dx (rlx_tf_encoder_f32)."""
+        f, t = self.torch.float32, self.torch
+        S, T = (int(v) for v in seg.shape)
+        _check(self.lib.rlx_tf_encoder_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), _ptr(seg, t.int32), _ptr(valid, t.uint8),
+                                           S, T, _ptr(out, f), _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()),
+               "rlx_tf_encoder_f32")
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
