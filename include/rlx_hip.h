@@ -1506,6 +1506,64 @@ int rlx_tf_encoder_f32(rlx_ctx*, const rlx_tf_desc*, const float* params, const 
                        const uint8_t* valid, int64_t S, int64_t T, float* out, const float* d_out /*NULL: forward only*/, float* grads,
                        float* dx, void* stream);
 
+/* =================================== selective state-space scan and the Mamba2 block =========================================
+ * The memory of the reference's ppo_mamba2 policy (rl_x/algorithms/ppo_mamba2/flax_full_jit/policy.py:40-175): the depthwise causal
+ * convolution with its episode reset (causal_conv_one_step under forward_sequence's reset, :83-97, :156-162), the selective diagonal
+ * state-space recurrence (ssm_one_step, :100-119) and the gated block around them (apply_one_step, :122-141).  A library component
+ * like rlx_band_attn_f32: the plugin above it, the observation encoders and the rollout's carry handling are not part of this
+ * section.  All pointers DEVICE, float32 throughout, every sum in a fixed order (identical calls give identical bits).
+ * S sequences of T tokens, row s T + t; I = d_model expand the inner width, N the state width, K the convolution width.
+ * done uint8 [S, T]: the episode ended AFTER token t.  r_t = 0 iff t > 0 and done[s, t - 1]: what enters token t from before it (the
+ * state, the convolution window) counts as 0.  Token 0 is never reset -- its carry comes in valid -- and done[s, T - 1] changes
+ * nothing in the call: the carries go out unreset, the caller resets them (ppo_mamba2.py:152-155).
+ * Envelope of all three: I a multiple of 64 up to 1024, N in {4, 8, 16}, 1 <= K <= 4, T >= 1, S >= 1 (neither a multiple of
+ * anything); outside it RLX_EUNSUP, rlx_last_error() names the field, nothing is written.  Row pointers 16-byte aligned.
+ *
+ * Convolution.  proj [S T, 2 I] (columns u0 | z: what the in_proj GEMM writes; only u0 is read), conv0 [S, K - 1, I] the window in
+ * front of token 0 (NULL: zeros), conv_w [K, I], conv_b [I]:
+ *   u1_t[i] = conv_b[i] + sum_k conv_w[k, i] v_{t-(K-1)+k},  u_t = silu(u1_t),  v = u0 (conv0 in front of token 0), 0 behind a reset
+ * u [S T, I]; convT [S, K - 1, I] (NULL: not wanted) the window after token T - 1.  K = 1 has no state (conv0 / convT ignored).
+ * d_u == NULL: forward only.  Else also d_proj [S T, 2 I] (ONLY the u0 columns are written), d_conv_w [K, I], d_conv_b [I].
+ * No gradient for conv0 (the reference does not differentiate init_carry).                                                   */
+int rlx_ssm_conv_f32(rlx_ctx*, const float* proj, const uint8_t* done, const float* conv0 /*NULL: zeros*/, const float* conv_w,
+                     const float* conv_b, int64_t S, int64_t T, int I, int K, float* u, float* convT /*NULL ok*/,
+                     const float* d_u /*NULL: forward only*/, float* d_proj, float* d_conv_w, float* d_conv_b, void* stream);
+
+/* Scan.  u [S T, I], xp [S T, I + 2 N] (columns dt_raw | B | C: what the x_proj GEMM writes), proj [S T, 2 I] (only z is read),
+ * h0 [S, I, N] (NULL: zeros), dt_bias [I], A_log [I, N], D [I]:
+ *   delta_t = softplus(dt_raw_t[i] + dt_bias[i]),  A = -exp(A_log[i, n]),  a_t = exp(delta_t A)
+ *   h_t[i, n] = a_t (r_t h_{t-1}) + delta_t B_t[n] u_t[i],   y_t[i] = sum_n h_t[i, n] C_t[n] + D[i] u_t[i],   g_t = y_t silu(z_t)
+ * g [S T, I]; hT [S, I, N] (NULL: not wanted) = h_{T-1}.  d_g == NULL: forward only.  Else also d_u [S T, I], d_xp [S T, I + 2 N]
+ * (every column: it feeds the x_proj GEMM's backward), d_proj [S T, 2 I] (ONLY the z columns are written), d_dt_bias [I], d_A_log
+ * [I, N], d_D [I]; the states at every 16th token that the backward restarts from live in the context's scratch arena.  No gradient
+ * for h0.  n_chunks: the time chunks a workgroup's waves split a sequence into -- 1, 2, 4 or 8, or 0 for the recorded default
+ * (DESIGN.md 4.5n); the results agree within rounding, and are bit-identical from call to call for the same value.           */
+int rlx_ssm_scan_f32(rlx_ctx*, const float* u, const float* xp, const float* proj, const uint8_t* done, const float* h0 /*NULL: zeros*/,
+                     const float* dt_bias, const float* A_log, const float* D, int64_t S, int64_t T, int I, int N, float* g,
+                     float* hT /*NULL ok*/, const float* d_g /*NULL: forward only*/, float* d_u, float* d_xp, float* d_proj,
+                     float* d_dt_bias, float* d_A_log, float* d_D, int n_chunks, void* stream);
+
+/* The block stack (Mamba2Block, policy.py:122-175; default_config.py: mamba_d_model, mamba_expand, mamba_state_dim, mamba_conv_kernel,
+ * mamba_num_layers, mamba_layer_norm_eps).  Per layer:
+ *   u0 | z = ln(x) W_in + b_in;  u = conv(u0);  dt_raw | B | C = u W_x + b_x;  g = scan(...);  x += g W_out + b_out
+ * FLAT LAYOUT, per layer, in this order: ln scale [d], ln bias [d], W_in [d, 2 I], b_in [2 I], conv_w [K, I], conv_b [I],
+ * W_x [I, I + 2 N], b_x [I + 2 N], dt_bias [I], A_log [I, N], D [I], W_out [I, d], b_out [d] (rlx_mamba2_param_count; INTEGRATION.md
+ * maps the Flax names onto it).  Envelope: d_model a multiple of 64 up to 512, 1 <= n_layers <= 4, and the scan's.           */
+typedef struct rlx_mamba2_desc {
+  int32_t d_model, expand, state_dim, conv_kernel, n_layers;
+  float ln_eps;                  /* mamba_layer_norm_eps */
+} rlx_mamba2_desc;
+int64_t rlx_mamba2_param_count(const rlx_mamba2_desc*);   /* -1 for a descriptor without layers or widths */
+
+/* Mamba2 stack on x [S T, d_model] under done [S, T] with the carries h0 [S, L, I, N] and conv0 [S, L, K - 1, I] (the reference's
+ * initialize_carry shapes; NULL: zeros) -> out [S T, d_model], hT, convT (same shapes; NULL: not wanted; not reset by done[s, T - 1]).
+ * T = 1 with carries in and out is the acting step.  d_out == NULL: forward only.  Else also the backward from d_out [S T, d_model]:
+ * grads (the flat layout, every entry written) and dx [S T, d_model]; activations and checkpoints in the context's scratch arena.
+ * GEMMs on the exact-fp32 engine below 4096 rows, on the split-operand engine from there.                                    */
+int rlx_mamba2_f32(rlx_ctx*, const rlx_mamba2_desc*, const float* params, const float* x /*[S*T, d_model]*/, const uint8_t* done,
+                   const float* h0, const float* conv0, int64_t S, int64_t T, float* out, float* hT, float* convT,
+                   const float* d_out /*NULL: forward only*/, float* grads, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

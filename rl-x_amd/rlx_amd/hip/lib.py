@@ -232,6 +232,21 @@ def tf_param_count(desc):
     return int(load_library().rlx_tf_param_count(ctypes.byref(desc)))
 
 
+class Mamba2Desc(Structure):
+    """rlx_mamba2_desc: the Mamba2 block stack (ppo_mamba2/flax_full_jit/default_config.py: mamba_*)"""
+    _fields_ = [("d_model", c_int32), ("expand", c_int32), ("state_dim", c_int32), ("conv_kernel", c_int32), ("n_layers", c_int32),
+                ("ln_eps", c_float)]
+
+
+def mamba2_desc(d_model=128, expand=2, state_dim=8, conv_kernel=4, n_layers=1, ln_eps=1e-5):
+    return Mamba2Desc(int(d_model), int(expand), int(state_dim), int(conv_kernel), int(n_layers), float(ln_eps))
+
+
+def mamba2_param_count(desc):
+    """floats of the stack's flat parameter vector (include/rlx_hip.h: the layout); host only"""
+    return int(load_library().rlx_mamba2_param_count(ctypes.byref(desc)))
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -451,6 +466,10 @@ _SIGNATURES = {
     "rlx_band_attn_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int] + [c_void_p] * 5),
     "rlx_tf_param_count": (c_int64, [POINTER(TfDesc)]),
     "rlx_tf_encoder_f32": (c_int, [c_void_p, POINTER(TfDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 5),
+    "rlx_ssm_conv_f32": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int, c_int] + [c_void_p] * 7),
+    "rlx_ssm_scan_f32": (c_int, [c_void_p] * 9 + [c_int64, c_int64, c_int, c_int] + [c_void_p] * 9 + [c_int, c_void_p]),
+    "rlx_mamba2_param_count": (c_int64, [POINTER(Mamba2Desc)]),
+    "rlx_mamba2_f32": (c_int, [c_void_p, POINTER(Mamba2Desc)] + [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 7),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1546,6 +1565,38 @@ class Ctx:
         _check(self.lib.rlx_tf_encoder_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), _ptr(seg, t.int32), _ptr(valid, t.uint8),
                                            S, T, _ptr(out, f), _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()),
                "rlx_tf_encoder_f32")
+
+    # ---- selective state-space scan and the Mamba2 block (ssm.hip)
+    def ssm_conv(self, proj, done, conv_w, conv_b, u, conv0=None, convT=None, d_u=None, d_proj=None, d_conv_w=None, d_conv_b=None):
+        """Depthwise causal convolution + SiLU over the u0 columns of proj [S T, 2 I] under done uint8 [S, T], conv_w [K, I]: u
+        [S T, I], convT [S, K - 1, I]; with d_u also d_proj (u0 columns), d_conv_w, d_conv_b (include/rlx_hip.h: rlx_ssm_conv_f32)."""
+        f = self.torch.float32
+        S, T = (int(v) for v in done.shape)
+        _check(self.lib.rlx_ssm_conv_f32(self.h, _ptr(proj, f), _ptr(done, self.torch.uint8), _ptr(conv0, f, True), _ptr(conv_w, f),
+                                         _ptr(conv_b, f), S, T, int(conv_w.shape[1]), int(conv_w.shape[0]), _ptr(u, f), _ptr(convT, f, True),
+                                         _ptr(d_u, f, True), _ptr(d_proj, f, True), _ptr(d_conv_w, f, True), _ptr(d_conv_b, f, True),
+                                         _stream()), "rlx_ssm_conv_f32")
+
+    def ssm_scan(self, u, xp, proj, done, dt_bias, A_log, D, g, h0=None, hT=None, d_g=None, d_u=None, d_xp=None, d_proj=None,
+                 d_dt_bias=None, d_A_log=None, d_D=None, n_chunks=0):
+        """Selective scan with the z gate on u [S T, I], xp [S T, I + 2 N] (dt_raw | B | C), the z columns of proj [S T, 2 I], A_log
+        [I, N]: g [S T, I], hT [S, I, N]; with d_g also d_u, d_xp, d_proj (z columns), d_dt_bias, d_A_log, d_D (rlx_ssm_scan_f32)."""
+        f = self.torch.float32
+        S, T = (int(v) for v in done.shape)
+        _check(self.lib.rlx_ssm_scan_f32(self.h, _ptr(u, f), _ptr(xp, f), _ptr(proj, f), _ptr(done, self.torch.uint8), _ptr(h0, f, True),
+                                         _ptr(dt_bias, f), _ptr(A_log, f), _ptr(D, f), S, T, int(A_log.shape[0]), int(A_log.shape[1]),
+                                         _ptr(g, f), _ptr(hT, f, True), _ptr(d_g, f, True), _ptr(d_u, f, True), _ptr(d_xp, f, True),
+                                         _ptr(d_proj, f, True), _ptr(d_dt_bias, f, True), _ptr(d_A_log, f, True), _ptr(d_D, f, True),
+                                         int(n_chunks), _stream()), "rlx_ssm_scan_f32")
+
+    def mamba2(self, desc, params, x, done, out, h0=None, conv0=None, hT=None, convT=None, d_out=None, grads=None, dx=None):
+        """The Mamba2 stack on x [S T, d_model] under done uint8 [S, T] with the carries h0 [S, L, I, N] / conv0 [S, L, K - 1, I] -> out,
+        hT, convT; with d_out also grads (flat layout) and dx (rlx_mamba2_f32)."""
+        f = self.torch.float32
+        S, T = (int(v) for v in done.shape)
+        _check(self.lib.rlx_mamba2_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), _ptr(done, self.torch.uint8),
+                                       _ptr(h0, f, True), _ptr(conv0, f, True), S, T, _ptr(out, f), _ptr(hT, f, True), _ptr(convT, f, True),
+                                       _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()), "rlx_mamba2_f32")
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
