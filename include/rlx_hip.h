@@ -1564,6 +1564,42 @@ int rlx_mamba2_f32(rlx_ctx*, const rlx_mamba2_desc*, const float* params, const 
                    const float* h0, const float* conv0, int64_t S, int64_t T, float* out, float* hT, float* convT,
                    const float* d_out /*NULL: forward only*/, float* grads, float* dx, void* stream);
 
+/* =================================== hyperspherical networks (SimbaV2's encoder) ==============================================
+ * The network of the reference's simbav2 family (rl_x/algorithms/simbav2/flax/layers.py:8-93: Scaler, HyperDense, HyperEmbedder,
+ * HyperMLP, HyperLERPBlock; critic.py / policy.py stack them) and the projection of its kernels back to unit column norm after every
+ * optimizer step (l2normalize_params, layers.py:131-143; simbav2.py:178, :233).  A library component like rlx_mamba2_f32: the
+ * simbav2 plugin, the heads (HyperNormalTanhPolicy, HyperCategoricalValue), the running normalisers and the initialisation are not
+ * part of this section.  All pointers DEVICE, float32 throughout, every sum in a fixed order (identical calls give identical bits).
+ *   EPS = 1e-8,  l2n(v) = v / max(|v|_2, EPS) along the last axis,  c = scaler_init / scaler_scale,  c_a = alpha_init / alpha_scale
+ *   H = hidden,  X = expansion H  (the block's inner Scaler has the same ratio c: both are divided by sqrt(expansion), layers.py:87-88)
+ *   embedder:  xt = l2n([x, c_shift]) [M, in_dim + 1];  z = xt W_e;  e = l2n(s_e * (c z))
+ *   block:     z1 = x W1;  h = relu(s1 * (c z1)) + EPS;  z2 = h W2;  y = l2n(z2);  v = x + a * (c_a (y - x));  x' = l2n(v)
+ * Where a norm is clamped (|v| <= EPS) its gradient is d / EPS, the gradient of a division by a constant.
+ * FLAT LAYOUT, in this order: W_e [in_dim + 1, H], s_e [H], then per block W1 [H, X], s1 [X], W2 [X, H], a [H]
+ * (rlx_hyper_param_count; INTEGRATION.md maps the Flax names onto it).  No HyperDense has a bias.
+ * Envelope: hidden a multiple of 64 up to 1024, expansion >= 1 with expansion hidden <= 4096, 1 <= n_blocks <= 4, 1 <= in_dim <= 1024,
+ * scaler_scale and alpha_scale non-zero, 1 <= M <= 2^20 (no multiple of anything); outside it RLX_EUNSUP, rlx_last_error() names the field,
+ * nothing is written.                                                                                                        */
+typedef struct rlx_hyper_desc {
+  int32_t in_dim, hidden, n_blocks, expansion;
+  float c_shift, scaler_init, scaler_scale, alpha_init, alpha_scale;
+} rlx_hyper_desc;
+int64_t rlx_hyper_param_count(const rlx_hyper_desc*);          /* -1 for a descriptor without widths */
+
+/* The network on x [M, in_dim] -> out [M, hidden].  d_out == NULL: forward only.  Else also the backward from d_out [M, hidden]:
+ * grads (the flat layout, every entry written) and, where dx != NULL, dx [M, in_dim] (SAC's policy loss differentiates the critic
+ * with respect to the action); activations in the context's scratch arena.  params, out, d_out, grads 16-byte aligned.  GEMMs on
+ * the exact-fp32 engine below 4096 rows, the blocks' on the split-operand engine from there.                                 */
+int rlx_hyper_net_f32(rlx_ctx*, const rlx_hyper_desc*, const float* params, const float* x /*[M, in_dim]*/, int64_t M,
+                      float* out /*[M, hidden]*/, const float* d_out /*NULL: forward only*/, float* grads, float* dx /*NULL ok*/,
+                      void* stream);
+/* l2normalize_params on the flat layout, in place, one launch: every matrix W [K, N] becomes W[:, n] / max(|W[:, n]|_2, EPS), the
+ * norm over the input axis K; Scalers and alphas are not touched.                                                            */
+int rlx_hyper_project_f32(rlx_ctx*, const rlx_hyper_desc*, float* params /*in place*/, void* stream);
+/* The same projection on E matrices [K, N] that lie `stride` floats apart (E == 1: stride is not read), any N (heads: N = action_dim,
+ * N = 101 bins); K, N <= 2^20.  A column of zeros stays zeros.                                                               */
+int rlx_colnorm_f32(rlx_ctx*, float* W /*[E][K, N] in place*/, int64_t K, int64_t N, int E, int64_t stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,29 @@ def mamba2_param_count(desc):
     return int(load_library().rlx_mamba2_param_count(ctypes.byref(desc)))
 
 
+class HyperDesc(Structure):
+    """rlx_hyper_desc: SimbaV2's hyperspherical network (simbav2/flax/layers.py: HyperEmbedder, HyperLERPBlock)"""
+    _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_blocks", c_int32), ("expansion", c_int32), ("c_shift", c_float),
+                ("scaler_init", c_float), ("scaler_scale", c_float), ("alpha_init", c_float), ("alpha_scale", c_float)]
+
+
+def hyper_desc(in_dim, hidden=512, n_blocks=2, expansion=4, c_shift=3.0, scaler_init=None, scaler_scale=None, alpha_init=None,
+               alpha_scale=None):
+    """The reference's constants where None: scaler_init = scaler_scale = sqrt(2 / hidden), alpha_init = 1 / (n_blocks + 1),
+    alpha_scale = 1 / sqrt(hidden)."""
+    width = max(int(hidden), 1)      # (a descriptor without widths is the library's to refuse)
+    si = (2.0 / width) ** 0.5 if scaler_init is None else scaler_init
+    ss = (2.0 / width) ** 0.5 if scaler_scale is None else scaler_scale
+    ai = 1.0 / (n_blocks + 1) if alpha_init is None else alpha_init
+    asc = width ** -0.5 if alpha_scale is None else alpha_scale
+    return HyperDesc(int(in_dim), int(hidden), int(n_blocks), int(expansion), float(c_shift), float(si), float(ss), float(ai), float(asc))
+
+
+def hyper_param_count(desc):
+    """floats of the network's flat parameter vector (include/rlx_hip.h: the layout); host only"""
+    return int(load_library().rlx_hyper_param_count(ctypes.byref(desc)))
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -470,6 +493,10 @@ _SIGNATURES = {
     "rlx_ssm_scan_f32": (c_int, [c_void_p] * 9 + [c_int64, c_int64, c_int, c_int] + [c_void_p] * 9 + [c_int, c_void_p]),
     "rlx_mamba2_param_count": (c_int64, [POINTER(Mamba2Desc)]),
     "rlx_mamba2_f32": (c_int, [c_void_p, POINTER(Mamba2Desc)] + [c_void_p] * 5 + [c_int64, c_int64] + [c_void_p] * 7),
+    "rlx_hyper_param_count": (c_int64, [POINTER(HyperDesc)]),
+    "rlx_hyper_net_f32": (c_int, [c_void_p, POINTER(HyperDesc), c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
+    "rlx_hyper_project_f32": (c_int, [c_void_p, POINTER(HyperDesc), c_void_p, c_void_p]),
+    "rlx_colnorm_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p]),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1597,6 +1624,25 @@ class Ctx:
         _check(self.lib.rlx_mamba2_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), _ptr(done, self.torch.uint8),
                                        _ptr(h0, f, True), _ptr(conv0, f, True), S, T, _ptr(out, f), _ptr(hT, f, True), _ptr(convT, f, True),
                                        _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()), "rlx_mamba2_f32")
+
+    # ---- hyperspherical networks (hyper.hip)
+    def hyper_net(self, desc, params, x, out, d_out=None, grads=None, dx=None):
+        """SimbaV2's hyperspherical network on x [M, in_dim] -> out [M, hidden]; with d_out also grads (flat layout) and, where given,
+        dx [M, in_dim] (include/rlx_hip.h: rlx_hyper_net_f32)."""
+        f = self.torch.float32
+        _check(self.lib.rlx_hyper_net_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), int(x.shape[0]), _ptr(out, f),
+                                          _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()), "rlx_hyper_net_f32")
+
+    def hyper_project(self, desc, params):
+        """l2normalize_params on the flat parameter vector, in place, one launch (rlx_hyper_project_f32)."""
+        _check(self.lib.rlx_hyper_project_f32(self.h, ctypes.byref(desc), _ptr(params, self.torch.float32), _stream()),
+               "rlx_hyper_project_f32")
+
+    def colnorm(self, W):
+        """Every column of W [K, N] or of each matrix of W [E, K, N] to unit l2 norm over K, in place (rlx_colnorm_f32)."""
+        E, K, N = (1, *W.shape) if W.dim() == 2 else W.shape
+        _check(self.lib.rlx_colnorm_f32(self.h, _ptr(W, self.torch.float32), int(K), int(N), int(E), int(K) * int(N), _stream()),
+               "rlx_colnorm_f32")
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
