@@ -1600,6 +1600,55 @@ int rlx_hyper_project_f32(rlx_ctx*, const rlx_hyper_desc*, float* params /*in pl
  * N = 101 bins); K, N <= 2^20.  A column of zeros stays zeros.                                                               */
 int rlx_colnorm_f32(rlx_ctx*, float* W /*[E][K, N] in place*/, int64_t K, int64_t N, int E, int64_t stride, void* stream);
 
+/* =================================== BroNet and BRO's quantile critic loss ====================================================
+ * The network of the reference's bro family (rl_x/algorithms/bro/flax/layers.py:10-29; critic.py / policy.py put heads on it) and
+ * the distributional branch of its critic loss (bro.py:29-32 quantile_huber_loss, :179-189).  Library components like
+ * rlx_hyper_net_f32: the bro plugin, the two policies' heads, the optimism / regulariser duals, the parameter resets and the
+ * non-distributional (MSE) branch are not part of this section.  All pointers DEVICE, float32 throughout, every sum in a fixed
+ * order (identical calls give identical bits), no atomics.
+ *   LN(z) = (z - mean) rsqrt(max(E[z^2] - mean^2, 0) + ln_eps) along the last axis (flax.linen.LayerNorm, ln_eps = 1e-6, "fast variance")
+ *   first layer:  z0 = x W0 + b0;  x_0 = relu(LN(z0) g0 + be0)
+ *   block b:      za = x_b Wa + ba;  ya = relu(LN(za) ga + bea);  zb = ya Wb + bb;  x_{b+1} = LN(zb) gb + beb + x_b   (post-norm residual)
+ *   output:       out = x_n Wo + bo where out_dim > 0, else out = x_n                                    (H = hidden, n = n_blocks)
+ * FLAT LAYOUT, in this order: W0 [in_dim, H], b0, g0, be0 [H]; per block Wa [H, H], ba, ga, bea, Wb [H, H], bb, gb, beb; then
+ * Wo [H, out_dim], bo [out_dim] where out_dim > 0 (rlx_bro_param_count; INTEGRATION.md maps the Flax names onto it).
+ * fwd_path chooses the route of a forward-only call: 1 = layered (one GEMM launch and one row-kernel launch per Dense), 2 = fused
+ * (one launch per Dense that normalises the previous layer's rows while it loads them: 32-row x 64-column workgroups, for calls of
+ * few rows), 0 = the recorded rule: fused for M <= 1024 rows, layered above.  A call with d_out always takes the layered route;
+ * fwd_path = 2 with d_out is RLX_EINVAL.
+ * Envelope: hidden a multiple of 64 up to 1024, 1 <= n_blocks <= 4, 1 <= in_dim <= 1024, 0 <= out_dim <= 128, ln_eps > 0, fwd_path 0..2,
+ * 1 <= M <= 2^20 (no multiple of anything); outside it RLX_EUNSUP, rlx_last_error() names the field, nothing is written.     */
+typedef struct rlx_bro_desc {
+  int32_t in_dim, hidden, n_blocks, out_dim;      /* out_dim == 0: no output layer */
+  float ln_eps;
+  int32_t fwd_path;
+} rlx_bro_desc;
+int64_t rlx_bro_param_count(const rlx_bro_desc*);              /* -1 for a descriptor without widths */
+
+/* The network on x [M, in_dim] -> out [M, out_dim] (out_dim > 0) or [M, hidden].  d_out == NULL: forward only.  Else also the
+ * backward from d_out (the shape of out): grads (the flat layout, every entry written) and, where dx != NULL, dx [M, in_dim] (the
+ * policy loss differentiates the critic with respect to the action); activations in the context's scratch arena.  params, out,
+ * d_out, grads 16-byte aligned.  H x H GEMMs of the layered route: the exact-fp32 engine below 4096 rows, the split-operand
+ * engine from there; the first layer and the fused route are exact fp32 at every M.                                          */
+int rlx_bro_net_f32(rlx_ctx*, const rlx_bro_desc*, const float* params, const float* x /*[M, in_dim]*/, int64_t M, float* out,
+                    const float* d_out /*NULL: forward only*/, float* grads, float* dx /*NULL ok*/, void* stream);
+
+/* BRO's distributional critic loss on given quantiles (bro.py:179-189): q1, q2 [B, N] the two critics' predictions, next_q1,
+ * next_q2 [B, N] the target critics' at the next state and action, rewards, terminations, next_logp [B], log_alpha DEVICE [1].
+ *   alpha = exp(log_alpha)                                                        (entropy_coefficient.py:12)
+ *   next_q[b, j] = (next_q1 + next_q2) / 2 - pessimism |next_q1 - next_q2| / 2
+ *   y[b, j] = r[b] + gamma (1 - term[b]) (next_q[b, j] - alpha next_logp[b])       (no gradient flows into y)
+ *   tau_i = (i + 0.5) / N,   td = y[b, j] - q_c[b, i],   huber_k(td) = td^2 / 2 where |td| <= kappa, else kappa (|td| - kappa / 2)
+ *   loss = sum_c sum_{b, i, j} |tau_i - 1[td < 0]| huber_k(td) / kappa / (B N)
+ *   dq_c[b, i] = d loss / d q_c[b, i] = -sum_j |tau_i - 1[td < 0]| clip(td, -kappa, kappa) / kappa / (B N)
+ * Every predicted quantile meets every target quantile; nothing is pooled, sorted or truncated (rlx_tqc_quantile_loss_f32 is
+ * a different function).  Writes dq1, dq2 [B, N], loss_out [1] and, where y_out != NULL, y_out [B, N].
+ * Envelope: 1 <= N <= 128, kappa > 0, B >= 1; outside it RLX_EUNSUP.                                                        */
+int rlx_bro_quantile_loss_f32(rlx_ctx*, const float* q1, const float* q2, const float* next_q1, const float* next_q2,
+                              const float* rewards, const float* terminations, const float* next_logp, const float* log_alpha,
+                              int64_t B, int N, float gamma, float pessimism, float kappa, float* dq1, float* dq2, float* loss_out,
+                              float* y_out /*NULL ok*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

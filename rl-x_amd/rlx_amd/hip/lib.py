@@ -270,6 +270,22 @@ def hyper_param_count(desc):
     return int(load_library().rlx_hyper_param_count(ctypes.byref(desc)))
 
 
+class BroDesc(Structure):
+    """rlx_bro_desc: BroNet (bro/flax/layers.py:10-29); out_dim 0: no output layer; fwd_path 0 the recorded rule, 1 layered, 2 fused"""
+    _fields_ = [("in_dim", c_int32), ("hidden", c_int32), ("n_blocks", c_int32), ("out_dim", c_int32), ("ln_eps", c_float),
+                ("fwd_path", c_int32)]
+
+
+def bro_desc(in_dim, hidden=512, n_blocks=2, out_dim=0, ln_eps=1e-6, fwd_path=0):
+    """The reference's critic: bro_desc(obs_dim + action_dim, 512, 2, nr_quantiles); its policy trunk: bro_desc(obs_dim, 256, 1)."""
+    return BroDesc(int(in_dim), int(hidden), int(n_blocks), int(out_dim), float(ln_eps), int(fwd_path))
+
+
+def bro_param_count(desc):
+    """floats of the network's flat parameter vector (include/rlx_hip.h: the layout); host only"""
+    return int(load_library().rlx_bro_param_count(ctypes.byref(desc)))
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -497,6 +513,9 @@ _SIGNATURES = {
     "rlx_hyper_net_f32": (c_int, [c_void_p, POINTER(HyperDesc), c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
     "rlx_hyper_project_f32": (c_int, [c_void_p, POINTER(HyperDesc), c_void_p, c_void_p]),
     "rlx_colnorm_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p]),
+    "rlx_bro_param_count": (c_int64, [POINTER(BroDesc)]),
+    "rlx_bro_net_f32": (c_int, [c_void_p, POINTER(BroDesc), c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
+    "rlx_bro_quantile_loss_f32": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_float, c_float, c_float] + [c_void_p] * 5),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1643,6 +1662,24 @@ class Ctx:
         E, K, N = (1, *W.shape) if W.dim() == 2 else W.shape
         _check(self.lib.rlx_colnorm_f32(self.h, _ptr(W, self.torch.float32), int(K), int(N), int(E), int(K) * int(N), _stream()),
                "rlx_colnorm_f32")
+
+    # ---- BroNet and BRO's quantile critic loss (bro.hip)
+    def bro_net(self, desc, params, x, out, d_out=None, grads=None, dx=None):
+        """BroNet on x [M, in_dim] -> out [M, out_dim or hidden]; with d_out also grads (flat layout) and, where given, dx [M, in_dim]
+        (include/rlx_hip.h: rlx_bro_net_f32).  desc.fwd_path picks the route of a forward-only call."""
+        f = self.torch.float32
+        _check(self.lib.rlx_bro_net_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, f), int(x.shape[0]), _ptr(out, f),
+                                        _ptr(d_out, f, True), _ptr(grads, f, True), _ptr(dx, f, True), _stream()), "rlx_bro_net_f32")
+
+    def bro_quantile_loss(self, q1, q2, next_q1, next_q2, rewards, terminations, next_logp, log_alpha, gamma, pessimism, kappa, dq1, dq2,
+                          loss_out, y_out=None):
+        """BRO's pairwise quantile-Huber critic loss on given quantiles [B, N] (include/rlx_hip.h: rlx_bro_quantile_loss_f32)."""
+        f = self.torch.float32
+        B, N = q1.shape
+        _check(self.lib.rlx_bro_quantile_loss_f32(self.h, _ptr(q1, f), _ptr(q2, f), _ptr(next_q1, f), _ptr(next_q2, f), _ptr(rewards, f),
+                                                  _ptr(terminations, f), _ptr(next_logp, f), _ptr(log_alpha, f), int(B), int(N),
+                                                  float(gamma), float(pessimism), float(kappa), _ptr(dq1, f), _ptr(dq2, f),
+                                                  _ptr(loss_out, f), _ptr(y_out, f, True), _stream()), "rlx_bro_quantile_loss_f32")
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
