@@ -1649,6 +1649,56 @@ int rlx_bro_quantile_loss_f32(rlx_ctx*, const float* q1, const float* q2, const 
                               int64_t B, int N, float gamma, float pessimism, float kappa, float* dq1, float* dq2, float* loss_out,
                               float* y_out /*NULL ok*/, void* stream);
 
+/* =================================== the convolutional torso of the image families ============================================
+ * The network of the reference's image-observation families (rl_x/algorithms/pqn/flax/critic.py:21-36 with a LayerNorm after
+ * every convolution and after the hidden Dense; the same stack without them in the Critic modules of dqn, ddqn, c51 and
+ * dqn_hl_gauss, each in its flax/critic.py).  A library component like rlx_bro_net_f32: the five plugins, the replay of image frames and the value-based losses are
+ * not part of this section.  All pointers DEVICE; the observation is uint8, everything else float32; every sum in a fixed order
+ * (identical calls give identical bits), no atomics.
+ *   x [M, in_c, in_h, in_w] uint8  ->  float(x) / 255.0f, seen as NHWC
+ *   conv l:  z = conv(y_{l-1}, W) + b, VALID padding, kernel[l] x kernel[l], stride[l], ch[l] output channels (NHWC activations)
+ *            y_l = relu(z)                                 (norm 0)
+ *            y_l = relu(LN_c(z) g + be)                    (norm 1; LN_c over the channel axis of each pixel)
+ *   flatten in (h, w, c) order (a view of the NHWC map);  hd = relu(f Wd + bd)  or  relu(LN(f Wd + bd) g + be);  out = hd Wo + bo
+ *   LN(z) = (z - mean) rsqrt(max(E[z^2] - mean^2, 0) + ln_eps) along the last axis (flax.linen.LayerNorm, "fast variance")
+ * FLAT LAYOUT, in this order: per convolution W [k, k, ci, co] (flax's HWIO), b [co], and with norm g, be [co]; then Wd [F, hidden]
+ * with F = OH OW ch_last, bd, and with norm g, be [hidden]; then Wo [hidden, out_dim], bo (rlx_cnn_param_count; INTEGRATION.md
+ * maps the Flax names onto it).
+ * Envelope: n_conv 1..3, ch in {32, 64}, 1 <= stride <= kernel <= 8, in_c 1..8, in_h, in_w <= 128 and every map at least `kernel`
+ * wide and high, hidden a multiple of 64 up to 1024, 1 <= out_dim <= 2048, ln_eps > 0, 1 <= M <= 2^16.  Narrower where a kernel's
+ * smallest tile of a map must fit the LDS one workgroup may take (L, the device's limit less 2 KB; CIe = ci rounded up to even;
+ * each line is sufficient, the library computes the exact footprint):
+ *   forward:          the `kernel` input rows under one output row:  4 kernel (stride CIe (ceil(in_w / stride) | 1) + 31) + 8 kernel^2 CIe/2 + 4 in_w + 72 <= L
+ *   weight gradient:  the same rows as NHWC and one output row of d z:  4 (kernel in_w ci + (OW + 15) (co + 1)) <= L
+ *   input gradient (every layer but the first, calls with a backward):  the layer's whole output map inside a halo of
+ *                     HL = ceil(kernel / stride) pixels:  4 (OH + 2 HL) (co ((OW + 2 HL) | 1) + 31) + 8 (kernel^2 co / 2 + 8 stride^2) <= L
+ * (with L = 158 KB every layer of the reference shape fits many times over; a 128 x 128 x 64 map under an 8 x 8 kernel does not).
+ * Outside the envelope RLX_EUNSUP, rlx_last_error() names the field, nothing is written.                                       */
+typedef struct rlx_cnn_desc {
+  int32_t in_c, in_h, in_w;                 /* the uint8 observation [M, in_c, in_h, in_w]                       */
+  int32_t n_conv;                           /* 1..3                                                              */
+  int32_t ch[3], kernel[3], stride[3];      /* the reference: {32,64,64}, {8,4,3}, {4,2,1}                       */
+  int32_t hidden, out_dim;                  /* Dense(hidden) -> Dense(out_dim); out_dim = actions x atoms / bins */
+  int32_t norm;                             /* 0: dqn, ddqn, c51, dqn_hl_gauss;  1: pqn's LayerNorms             */
+  float ln_eps;                             /* flax: 1e-6                                                        */
+} rlx_cnn_desc;
+int64_t rlx_cnn_param_count(const rlx_cnn_desc*);      /* -1 for a descriptor without widths */
+
+/* The torso on x -> out [M, out_dim].  d_out == NULL: forward only.  Else also the backward from d_out [M, out_dim]: grads (the
+ * flat layout, every entry written); the image gets no gradient.  Activations in the context's scratch arena.  params, out, d_out,
+ * grads 16-byte aligned.  The convolutions and the Dense layers are exact fp32 (v_mfma_f32_32x32x2_f32) at every M.           */
+int rlx_cnn_net_f32(rlx_ctx*, const rlx_cnn_desc*, const float* params, const uint8_t* x, int64_t M, float* out /*[M, out_dim]*/,
+                    const float* d_out /*NULL: forward only*/, float* grads, void* stream);
+
+/* One layer, for tests and for callers with their own stack: exactly one of x_u8 [M, CI, H, W] (CI 1..8) / x_f32 [M, H, W, CI]
+ * (CI 32 or 64) non-NULL.  y = relu(conv + b), or with g_be = [g | be] relu(LN_c(conv + b) g + be).  With d_y (the gradient of y)
+ * also gW, gb, g_gbe = [d g | d be] (with norm) and, where dx != NULL, dx [M, H, W, CI]: input rows and columns that VALID padding
+ * never reads are written as exact zeros.  The envelope is the section's, per layer.                                          */
+int rlx_conv2d_f32(rlx_ctx*, const uint8_t* x_u8, const float* x_f32, int64_t M, int H, int W, int CI, int kernel, int stride, int CO,
+                   const float* Wt /*[k, k, CI, CO]*/, const float* b, const float* g_be /*NULL: no norm; else [2 CO]*/, float ln_eps,
+                   float* y /*[M, OH, OW, CO]*/, const float* d_y /*NULL: forward only*/, float* dx /*NULL ok; f32 input only*/,
+                   float* gW, float* gb, float* g_gbe /*[2 CO] with norm*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,6 @@ from rlx_amd.hip.lib import (  # noqa: F401
     FastTd3Hparams, relu_mlp_desc, ReppoDesc, ReppoHparams, reppo_desc, MpoDesc, MpoHparams, mpo_desc, EspoHparams, TqcHparams,
     RedqHparams, redq_subset, Td3Hparams, AqeHparams, DroqHparams, FastMpoDesc, FastMpoHparams, fastmpo_desc, DtrlHparams,
     TfDesc, tf_desc, tf_param_count, Mamba2Desc, mamba2_desc, mamba2_param_count, HyperDesc, hyper_desc, hyper_param_count,
-    BroDesc, bro_desc, bro_param_count,
+    BroDesc, bro_desc, bro_param_count, CnnDesc, cnn_desc, cnn_param_count,
     ACT_TANH, ACT_ELU, ACT_RELU, THREEFRY_LEGACY, THREEFRY_PARTITIONABLE,
 )

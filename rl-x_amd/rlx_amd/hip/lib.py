@@ -286,6 +286,23 @@ def bro_param_count(desc):
     return int(load_library().rlx_bro_param_count(ctypes.byref(desc)))
 
 
+class CnnDesc(Structure):
+    """rlx_cnn_desc: the convolutional torso of dqn, ddqn, c51, dqn_hl_gauss (norm 0) and pqn (norm 1) (*/flax/critic.py)"""
+    _fields_ = [("in_c", c_int32), ("in_h", c_int32), ("in_w", c_int32), ("n_conv", c_int32), ("ch", c_int32 * 3), ("kernel", c_int32 * 3),
+                ("stride", c_int32 * 3), ("hidden", c_int32), ("out_dim", c_int32), ("norm", c_int32), ("ln_eps", c_float)]
+
+
+def cnn_desc(out_dim, in_c=4, in_h=84, in_w=84, convs=((32, 8, 4), (64, 4, 2), (64, 3, 1)), hidden=512, norm=0, ln_eps=1e-6):
+    """The reference's torso: convs = ((channels, kernel, stride), ...); out_dim = actions x atoms / bins; norm=1 is pqn."""
+    pad = lambda i: (c_int32 * 3)(*([int(c[i]) for c in convs] + [0] * (3 - len(convs))))
+    return CnnDesc(int(in_c), int(in_h), int(in_w), len(convs), pad(0), pad(1), pad(2), int(hidden), int(out_dim), int(norm), float(ln_eps))
+
+
+def cnn_param_count(desc):
+    """floats of the torso's flat parameter vector (include/rlx_hip.h: the layout); host only"""
+    return int(load_library().rlx_cnn_param_count(ctypes.byref(desc)))
+
+
 def relu_mlp_desc(in_dim, hidden, out_dim):
     """FastTD3's networks: rlx_mlp_desc with Dense -> ReLU per hidden layer and a plain Dense head (no LayerNorm, no log-std)."""
     return mlp_desc(in_dim, hidden, out_dim, ACT_RELU, False, False)
@@ -516,6 +533,9 @@ _SIGNATURES = {
     "rlx_bro_param_count": (c_int64, [POINTER(BroDesc)]),
     "rlx_bro_net_f32": (c_int, [c_void_p, POINTER(BroDesc), c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
     "rlx_bro_quantile_loss_f32": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_float, c_float, c_float] + [c_void_p] * 5),
+    "rlx_cnn_param_count": (c_int64, [POINTER(CnnDesc)]),
+    "rlx_cnn_net_f32": (c_int, [c_void_p, POINTER(CnnDesc), c_void_p, c_void_p, c_int64] + [c_void_p] * 4),
+    "rlx_conv2d_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 6 + [c_void_p] * 3 + [c_float] + [c_void_p] * 7),
     "rlx_fastmpo_param_count": (c_int64, [POINTER(FastMpoDesc), c_int]),
     "rlx_fastmpo_act_f32": (c_int, [c_void_p, POINTER(FastMpoDesc), c_void_p, c_void_p, c_int, c_void_p, _U32P, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int64, c_int, POINTER(FastMpoHparams), c_void_p]),
@@ -1680,6 +1700,25 @@ class Ctx:
                                                   _ptr(terminations, f), _ptr(next_logp, f), _ptr(log_alpha, f), int(B), int(N),
                                                   float(gamma), float(pessimism), float(kappa), _ptr(dq1, f), _ptr(dq2, f),
                                                   _ptr(loss_out, f), _ptr(y_out, f, True), _stream()), "rlx_bro_quantile_loss_f32")
+
+    # ---- the convolutional torso of the image families (cnn.hip)
+    def cnn_net(self, desc, params, x, out, d_out=None, grads=None):
+        """The torso on the uint8 observation x [M, in_c, in_h, in_w] -> out [M, out_dim]; with d_out also grads (flat layout)
+        (include/rlx_hip.h: rlx_cnn_net_f32)."""
+        f = self.torch.float32
+        _check(self.lib.rlx_cnn_net_f32(self.h, ctypes.byref(desc), _ptr(params, f), _ptr(x, self.torch.uint8), int(x.shape[0]), _ptr(out, f),
+                                        _ptr(d_out, f, True), _ptr(grads, f, True), _stream()), "rlx_cnn_net_f32")
+
+    def conv2d(self, x, W, b, stride, y, g_be=None, ln_eps=1e-6, d_y=None, dx=None, gW=None, gb=None, g_gbe=None):
+        """One convolution layer: x uint8 [M, CI, H, W] or float32 [M, H, W, CI], W [k, k, CI, CO] -> y [M, OH, OW, CO] = relu(conv + b),
+        with g_be [2 CO] relu(LN_c(conv + b) g + be); with d_y also gW, gb, g_gbe and, for a float32 x, dx
+        (include/rlx_hip.h: rlx_conv2d_f32)."""
+        f, u8 = self.torch.float32, x.dtype == self.torch.uint8
+        M, CI, H, Wd = (x.shape if u8 else (x.shape[0], x.shape[3], x.shape[1], x.shape[2]))
+        _check(self.lib.rlx_conv2d_f32(self.h, _ptr(x, self.torch.uint8) if u8 else None, None if u8 else _ptr(x, f), int(M), int(H), int(Wd),
+                                       int(CI), int(W.shape[0]), int(stride), int(W.shape[3]), _ptr(W, f), _ptr(b, f), _ptr(g_be, f, True),
+                                       float(ln_eps), _ptr(y, f), _ptr(d_y, f, True), _ptr(dx, f, True), _ptr(gW, f, True), _ptr(gb, f, True),
+                                       _ptr(g_gbe, f, True), _stream()), "rlx_conv2d_f32")
 
     def dist_overflow_counts(self):
         """(rows dropped by ANY rank -- identical on every rank, minibatches THIS rank truncated); blocking on the current
