@@ -215,6 +215,15 @@ int rlx_prof_union_ms(rlx_ctx* ctx, double* out);
  *   partials cross row groups as 16-byte LDS stores and loads; 65920 instead of 65600 bytes of LDS.  Every sum keeps its operands
  *   and their order: bit-identical results (tests/test_gpu_tail32_lean.py); 0, and "tail32_waves" = 4, run the earlier kernels
  *   unchanged.
+ * "gemm_small_m" (0 default; 0 or 1, anything else is RLX_EINVAL): the forward products of rlx_cnn_net_f32 (the hidden Dense),
+ *   rlx_hyper_net_f32 (the blocks' two products) and the layered route of rlx_bro_net_f32.  0: every one of them runs the
+ *   128 x 128-tile kernel k_gemm_fwd as before, bit for bit.  1: a product goes to the split-K kernel of gemm_sk.hip (32 x 64
+ *   tiles, the K axis split over up to 64 workgroups and summed in slice order: deterministic, results within rounding of
+ *   k_gemm_fwd's) where the 128 x 128 tiling gives fewer than a quarter of the CUs a tile, K >= 512 and M <= 1024 (the measured
+ *   rule) and no split-operand weight image is registered for the weight; backward passes are unchanged.
+ * "gemm_sk_slices" (0 default; 0 .. 64, anything else is RLX_EINVAL): K slices of that kernel.  0: the host rule (about one
+ *   workgroup per CU); 1 .. 64: forced, clamped so that a slice keeps its floor of 32 k.  Results agree within rounding whatever
+ *   the count; identical calls give identical bits.
  * "espo_chunk" (2): rlx_espo_update_f32 submits that many epochs between two copies of its device-side stop word to the host
  *   (at most two chunks of epochs run as wasted work after a stop); the result does not depend on it.
  * (The measured-negative experiments of rounds 2-4 -- hipGraph replay, fused forward, 64-row / pipelined first-layer backward,
@@ -226,7 +235,8 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value);
  * communicator or the all-reduce hook) -- bench.py's multi_gpu.collectives_per_step is the difference over the timed steps;
  * "dx_l1bwd_wrap_launches" = launches of k_dx_l1bwd_stats_wrap so far (option "l1_wrap_refill"; the profiler books both forms of
  * the kernel under one row); "l12fwd_pf_launches" = launches of k_l12fwd_pf so far (option "l12_prefetch"; the profiler books both
- * forms of k_l12fwd under one row); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
+ * forms of k_l12fwd under one row); "gemm_sk_launches" = launches of k_gemm_sk so far (option "gemm_small_m": which route a pass
+ * took); "bx_window_fallbacks" = rollouts (rlx_ppo_rollout_begin) that found a weight of the acting nets at or above 1023 -- outside
  * the fp16 window of the split-operand engine -- and therefore ran their T steps on the exact-fp32 engine; "gemm_bx" = the
  * current value of that option; "ro_persistent_launches" / "ro_step_launches" = launches of k_rollout_steps / of
  * k_rollout_step so far (option "rollout_persistent": which path a rollout took); "ro_critic_es_ptr" = device address of the
@@ -245,7 +255,10 @@ int rlx_dbg_set_stamps(rlx_ctx* ctx, void* stamps);
 /* debug / micro-benchmark hook: run ONE of the exact-fp32 MFMA GEMM kernels on caller buffers.
  *   mode 0: C[M,N]  = act(A[M,K] @ B[K,N] + aux[N])                 forward hidden layer
  *   mode 1: C[M,K] <- (A[M,N] @ B[K,N]^T) * act'(C[M,K]) in place   input gradient (act < 0: no act')
- *   mode 2: C[K,N]  = A[M,K]^T @ B[M,N]; aux[N] = column sums of B  weight gradient (split-M + reduce) */
+ *   mode 2: C[K,N]  = A[M,K]^T @ B[M,N]; aux[N] = column sums of B  weight gradient (split-M + reduce)
+ *   (modes 3 / 4 / 5: the split-operand forms of modes 0 / 1 / 2, see "bx_debug")
+ *   mode 6: mode 0's product on the split-K kernel for few rows     gemm_sk.hip, under the option "gemm_sk_slices"; 1 <= M <=
+ *           1024, outside the envelope RLX_EUNSUP names the field and C is left untouched */
 int rlx_dbg_gemm_f32(rlx_ctx* ctx, int mode, const float* A, const float* B, float* C, float* aux, int64_t M, int N,
                      int K, int act, void* stream);
 

@@ -135,13 +135,13 @@ static inline int bro_fwd(rlx_ctx* ctx, const Bro& E, const float* p, const floa
                           hipStream_t st) {
   const int H = E.H;
   int rc = fs_concat(x, E.in, nullptr, 0, B.xp, E.ld, M, st);
-  if (!rc) rc = launch_gemm_fwd(ctx, B.xp, p + E.W0, p + E.b0, B.z0, M, H, E.in, RLX_ACT_NONE, st, E.ld);
+  if (!rc) rc = gemm_fwd_auto(ctx, B.xp, p + E.W0, p + E.b0, B.z0, M, H, E.in, RLX_ACT_NONE, st, E.ld);
   if (!rc) rc = bro_ln(ctx, B.z0, p + E.g0, p + E.be0, nullptr, E.eps, M, H, B.X[0], B.st0, st);
   for (int b = 0; b < E.n_blocks && !rc; ++b) {
     const BroBlock& L = E.blk[b];
-    rc = launch_gemm_fwd(ctx, B.X[b], p + L.Wa, p + L.ba, B.za[b], M, H, H, RLX_ACT_NONE, st, H);
+    rc = gemm_fwd_auto(ctx, B.X[b], p + L.Wa, p + L.ba, B.za[b], M, H, H, RLX_ACT_NONE, st, H);
     if (!rc) rc = bro_ln(ctx, B.za[b], p + L.ga, p + L.bea, nullptr, E.eps, M, H, B.ya[b], B.sta[b], st);
-    if (!rc) rc = launch_gemm_fwd(ctx, B.ya[b], p + L.Wb, p + L.bb, B.zb[b], M, H, H, RLX_ACT_NONE, st, H);
+    if (!rc) rc = gemm_fwd_auto(ctx, B.ya[b], p + L.Wb, p + L.bb, B.zb[b], M, H, H, RLX_ACT_NONE, st, H);
     if (!rc) rc = bro_ln(ctx, B.zb[b], p + L.gb, p + L.beb, B.X[b], E.eps, M, H, B.X[b + 1], B.stb[b], st);
   }
   if (rc || E.out == 0) return rc;

@@ -128,8 +128,8 @@ static inline int cnn_fwd(rlx_ctx* ctx, const Cnn& E, const float* p, const uint
                   E.eps, M, B.y[l], B.z[l], B.st[l], st);
   }
   const float* f = B.y[E.n_conv - 1];      // the flatten: a view
-  if (!rc && !E.norm) rc = launch_gemm_fwd(ctx, f, p + E.Wd, p + E.bd, B.hd, M, E.hidden, E.F, RLX_ACT_RELU, st, E.F);
-  if (!rc && E.norm) rc = launch_gemm_fwd(ctx, f, p + E.Wd, p + E.bd, B.zd, M, E.hidden, E.F, RLX_ACT_NONE, st, E.F);
+  if (!rc && !E.norm) rc = gemm_fwd_auto(ctx, f, p + E.Wd, p + E.bd, B.hd, M, E.hidden, E.F, RLX_ACT_RELU, st, E.F);
+  if (!rc && E.norm) rc = gemm_fwd_auto(ctx, f, p + E.Wd, p + E.bd, B.zd, M, E.hidden, E.F, RLX_ACT_NONE, st, E.F);
   if (!rc && E.norm) rc = bro_ln(ctx, B.zd, p + E.gd, p + E.bed, nullptr, E.eps, M, E.hidden, B.hd, B.std, st);
   return rc ? rc : fs_head_fwd(B.hd, p + E.Wo, p + E.bo, out, M, E.hidden, E.out, st);
 }

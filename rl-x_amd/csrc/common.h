@@ -49,7 +49,7 @@ enum ScratchSlot {
   SL_MB_X, SL_MB_XC, SL_MB_AUX, SL_STATS,
   SL_ACT_P0, SL_ACT_P1, SL_ACT_P2, SL_ACT_C0, SL_ACT_C1, SL_ACT_C2,
   SL_DACT_0, SL_DACT_1, SL_LN_P, SL_LN_C,
-  SL_PARTIAL, SL_HEAD_PART, SL_NORM, SL_NORM2, SL_FWD_A, SL_FWD_B, SL_KEYS, SL_GRAD_P, SL_GRAD_C, SL_MEAN, SL_VALUE, SL_RO_NETS, SL_SAC, SL_LSTM, SL_LSTM_IDX, SL_STAGE, SL_OPT_A, SL_OPT_B, SL_STATS_ALL, SL_ZEROS, SL_STAT_PART, SL_LIDX, SL_COUNTS, SL_DIST_STATS, SL_OVERFLOW, SL_SCHED, SL_NV_ROWS, SL_WFRAG, SL_WFRAG_RO, SL_XMAX, SL_MB_GROUP_X, SL_MB_GROUP_AUX, SL_DZ0, SL_WFRAG_SAC, SL_ROW_REC, SL_RO_CRITIC_ES, SL_TF, SL_SSM, SL_HYPER, SL_BRO, SL_CNN,
+  SL_PARTIAL, SL_HEAD_PART, SL_NORM, SL_NORM2, SL_FWD_A, SL_FWD_B, SL_KEYS, SL_GRAD_P, SL_GRAD_C, SL_MEAN, SL_VALUE, SL_RO_NETS, SL_SAC, SL_LSTM, SL_LSTM_IDX, SL_STAGE, SL_OPT_A, SL_OPT_B, SL_STATS_ALL, SL_ZEROS, SL_STAT_PART, SL_LIDX, SL_COUNTS, SL_DIST_STATS, SL_OVERFLOW, SL_SCHED, SL_NV_ROWS, SL_WFRAG, SL_WFRAG_RO, SL_XMAX, SL_MB_GROUP_X, SL_MB_GROUP_AUX, SL_DZ0, SL_WFRAG_SAC, SL_ROW_REC, SL_RO_CRITIC_ES, SL_TF, SL_SSM, SL_HYPER, SL_BRO, SL_CNN, SL_GEMM_SK,
   SL_COUNT
 };
 
@@ -61,6 +61,7 @@ enum ProfKernel { PK_GEMM_FWD = 0, PK_GEMM_DX, PK_GEMM_DW, PK_DX_L1BWD,
                   PK_L12FWD, // first + second layer forward in one launch (l1fused.hip: k_l12fwd): engine 1, shape (rows, hidden[1], 512)
                   PK_TAIL,   // row-tile-local tail of a network's pass (ppo.hip: k_tail_bx): engine 1, shape (rows, 128, hidden[1])
                   PK_FWD2H,  // whole two-hidden-layer forward + head in one launch (fwd2h.hip: k_fwd2h): engine 1, shape (rows, 256, in_dim)
+                  PK_GEMM_SK, // split-K forward GEMM for few rows and a long K (gemm_sk.hip: k_gemm_sk): engine 0, shape (rows, N, K)
                   PK_COUNT };
 constexpr int PROF_ENGINE_HBM = 2;
 struct ProfRec {
@@ -227,6 +228,10 @@ struct rlx_ctx {
   int64_t ro_persistent_launches = 0;     // launches of k_rollout_steps / of k_rollout_step since the context was created
   int64_t ro_step_launches = 0;
   const void* ro_critic_es = nullptr;     // the critic workgroups' episode-step counters of the last persistent rollout (counter "ro_critic_es_ptr")
+  int gemm_small_m = 0;                   // 1: gemm_fwd_auto (net_pass.h) sends the forward products of the recorded rule to the split-K kernel (gemm_sk.hip); 0 (default):
+                                          // every call site runs launch_gemm_fwd as before, bit for bit
+  int gemm_sk_slices = 0;                 // K slices of the split-K kernel: 0 the host rule (gemm_sk_slices, mlp.h), 1 .. 64 forced (a slice keeps its floor)
+  int64_t gemm_sk_launches = 0;           // launches of k_gemm_sk since the context was created
   int64_t bx_window_fallbacks = 0;        // rollouts whose acting nets had a weight outside the fp16 window and ran on the exact engine (rollout.hip)
   int64_t ar_calls = 0;                   // all-reduces issued through dist_allreduce (communicator or hook) since the context was created
   // ---- SAC update (sac.hip): critic-loss chain on the caller's stream, policy-loss chain on `side`

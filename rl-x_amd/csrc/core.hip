@@ -159,7 +159,7 @@ int rlx_prof_kernel_count(void) { return rlx::PK_COUNT; }
 
 const char* rlx_prof_kernel_name(int k) {
   static const char* names[rlx::PK_COUNT] = {"k_gemm_fwd", "k_gemm_dx", "k_gemm_dw", "k_dx_l1bwd",
-                                              "k_l1fwd_mfma", "k_head_loss", "k_reduce_segments", "k_l12fwd", "k_tail", "k_fwd2h"};
+                                              "k_l1fwd_mfma", "k_head_loss", "k_reduce_segments", "k_l12fwd", "k_tail", "k_fwd2h", "k_gemm_sk"};
   return (k >= 0 && k < rlx::PK_COUNT) ? names[k] : nullptr;
 }
 
@@ -276,6 +276,16 @@ int rlx_dbg_set_option(rlx_ctx* ctx, const char* name, int value) {
     ctx->l12_prefetch = value;
     return RLX_OK;
   }
+  if (std::string(name) == "gemm_small_m") {
+    RLX_REQUIRE(value == 0 || value == 1, RLX_EINVAL, "rlx_dbg_set_option: gemm_small_m is 0 or 1");
+    ctx->gemm_small_m = value;
+    return RLX_OK;
+  }
+  if (std::string(name) == "gemm_sk_slices") {
+    RLX_REQUIRE(value >= 0 && value <= 64, RLX_EINVAL, "rlx_dbg_set_option: gemm_sk_slices is 0 .. 64");
+    ctx->gemm_sk_slices = value;
+    return RLX_OK;
+  }
   if (std::string(name) == "bx_force_mi") { ctx->bx_force_mi = value; return RLX_OK; }
   if (std::string(name) == "adam_emit") { ctx->adam_emit = value != 0; return RLX_OK; }
   if (std::string(name) == "bx_debug") { ctx->bx_debug = value; return RLX_OK; }
@@ -301,6 +311,7 @@ int rlx_dbg_get_counter(rlx_ctx* ctx, const char* name, int64_t* out) {
   if (std::string(name) == "allreduce_calls") { *out = ctx->ar_calls; return RLX_OK; }
   if (std::string(name) == "dx_l1bwd_wrap_launches") { *out = ctx->dx_l1bwd_wrap_launches; return RLX_OK; }
   if (std::string(name) == "l12fwd_pf_launches") { *out = ctx->l12fwd_pf_launches; return RLX_OK; }
+  if (std::string(name) == "gemm_sk_launches") { *out = ctx->gemm_sk_launches; return RLX_OK; }
   if (std::string(name) == "ro_persistent_launches") { *out = ctx->ro_persistent_launches; return RLX_OK; }
   if (std::string(name) == "ro_step_launches") { *out = ctx->ro_step_launches; return RLX_OK; }
   if (std::string(name) == "ro_critic_es_ptr") { *out = (int64_t)reinterpret_cast<uintptr_t>(ctx->ro_critic_es); return RLX_OK; }

@@ -129,9 +129,9 @@ static inline int hyper_fwd(rlx_ctx* ctx, const Hyper& E, const float* p, const 
   for (int b = 0; b < E.n_blocks && !rc; ++b) {
     const HyperBlock& L = E.blk[b];
     const HyperBlockBufs& k = B.b[b];
-    rc = launch_gemm_fwd(ctx, k.x, p + L.W1, zero, k.z1, M, X, H, RLX_ACT_NONE, st, H);
+    rc = gemm_fwd_auto(ctx, k.x, p + L.W1, zero, k.z1, M, X, H, RLX_ACT_NONE, st, H);
     if (!rc) rc = hyper_relu(k.z1, p + L.s1, E.c, M, X, k.h, st);
-    if (!rc) rc = launch_gemm_fwd(ctx, k.h, p + L.W2, zero, k.z2, M, H, X, RLX_ACT_NONE, st, X);
+    if (!rc) rc = gemm_fwd_auto(ctx, k.h, p + L.W2, zero, k.z2, M, H, X, RLX_ACT_NONE, st, X);
     if (!rc) rc = hyper_lerp(ctx, k.z2, k.x, p + L.a, E.ca, M, H, b + 1 < E.n_blocks ? B.b[b + 1].x : out, k.rn, st);
   }
   return rc;

@@ -43,6 +43,17 @@ int mlp_check_desc(const rlx_mlp_desc& d);
 // launch covers M rows (a capacity the host knows) and the row tiles beyond *m_dev leave at once
 int launch_gemm_fwd(rlx_ctx* ctx, const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K,
                     int act, hipStream_t st, int lda, const int32_t* m_dev = nullptr);
+// gemm_sk.hip: the same product for few rows and a long K -- 32 x 64 tiles, the K axis split over `slices` workgroups (0: the host
+// rule gemm_sk_slices; 1 .. 64 forced, a slice keeping its floor of 32 k) and summed in slice order; S > 1 takes S M N floats of
+// SL_GEMM_SK (at most 64 MiB).  Envelope: 1 <= M <= GEMM_SK_MAX_M, N % 4 == 0, K % 4 == 0, lda 0 or a multiple of 4 >= K; outside
+// it RLX_EUNSUP names the field and nothing is written.  Split-operand weight images are not looked up.
+constexpr int GEMM_SK_MAX_M = 1024;
+int gemm_sk_slices(int64_t M, int N, int K, int num_cus, int forced = 0);
+int launch_gemm_fwd_sk(rlx_ctx* ctx, const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, int act,
+                       hipStream_t st, int lda, int slices = 0);
+// The recorded rule of gemm_fwd_auto (net_pass.h; DESIGN.md section 4.5r has the table it comes from): the split-K route where the
+// 128 x 128 tiling gives fewer than a quarter of the CUs a tile, K >= GEMM_SK_K_STAR and M <= GEMM_SK_M_STAR.
+constexpr int GEMM_SK_K_STAR = 512, GEMM_SK_M_STAR = 1024;
 int launch_head_fwd(const float* H, const float* W, const float* b, float* out, int64_t M, int K, int A,
                     hipStream_t st, const int32_t* m_dev = nullptr, const Twin* tw = nullptr);
 bool dx_cols_ok(int K, int nc);      // launch_dx_cols takes the shape (at most 64 columns, K % 4 == 0, tile within the LDS budget)

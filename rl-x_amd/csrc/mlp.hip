@@ -1625,6 +1625,7 @@ using namespace rlx;
 //   mode 0: C[M,N]  = act(A[M,K] @ B[K,N] + bias[N])                (k_gemm_fwd;  aux = bias)
 //   mode 1: C[M,K] <- (A[M,N] @ B[K,N]^T) * act'(C[M,K]) in place    (k_gemm_dx;   aux unused, act applied iff act>=0)
 //   mode 2: C[K,N]  = A[M,K]^T @ B[M,N], aux[N] = column sums of B   (k_gemm_dw + slab reduction)
+//   mode 6: mode 0's product on the split-K kernel for few rows      (gemm_sk.hip: k_gemm_sk [+ k_gemm_sk_finish]; aux = bias)
 extern "C" int rlx_dbg_gemm_f32(rlx_ctx* ctx, int mode, const float* A, const float* B, float* C, float* aux,
                                 int64_t M, int N, int K, int act, void* stream) {
   RLX_REQUIRE(ctx && A && B && C && M > 0 && N > 0 && K > 0, RLX_EINVAL, "rlx_dbg_gemm_f32: bad args");
@@ -1699,7 +1700,11 @@ extern "C" int rlx_dbg_gemm_f32(rlx_ctx* ctx, int mode, const float* A, const fl
     ctx->gemm_bx = was;
     return rc;
   }
-  RLX_REQUIRE(false, RLX_EINVAL, "rlx_dbg_gemm_f32: mode must be 0 .. 5");
+  if (mode == 6) {   // the split-K forward kernel (gemm_sk.hip) under the option "gemm_sk_slices"
+    RLX_REQUIRE(aux, RLX_EINVAL, "rlx_dbg_gemm_f32: mode 6 needs bias");
+    return launch_gemm_fwd_sk(ctx, A, B, aux, C, M, N, K, act, st, 0, ctx->gemm_sk_slices);
+  }
+  RLX_REQUIRE(false, RLX_EINVAL, "rlx_dbg_gemm_f32: mode must be 0 .. 6");
 }
 
 // debug / micro-benchmark hook for the first-layer kernel (fwd: H out; bwd: H = dH in -> dZ1 out)

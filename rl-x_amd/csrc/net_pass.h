@@ -167,6 +167,18 @@ static inline int net_images(rlx_ctx* ctx, const BxMat* mats, int n, int64_t M, 
   ctx->bx_n[1] = ctx->bx_n[0];
   return RLX_OK;
 }
+// ---- the forward product of a pass at the reference's batch sizes: launch_gemm_fwd, or under the option "gemm_small_m" the split-K
+// kernel where the recorded rule (mlp.h) takes the shape and no split-operand weight image is registered for W
+static inline bool gemm_small_m_rule(const rlx_ctx* ctx, int64_t M, int N, int K, int lda) {
+  return M <= GEMM_SK_M_STAR && K >= GEMM_SK_K_STAR && N % 4 == 0 && K % 4 == 0 && (lda == 0 || (lda % 4 == 0 && lda >= K)) &&
+         (int64_t)div_up(M, G_BM) * div_up(N, G_BN) * 4 < ctx->num_cus;
+}
+static inline int gemm_fwd_auto(rlx_ctx* ctx, const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, int act,
+                                hipStream_t st, int lda) {
+  if (!ctx->gemm_small_m || !gemm_small_m_rule(ctx, M, N, K, lda) || bx_lookup(ctx, W, 0, K, N))
+    return launch_gemm_fwd(ctx, A, W, bias, C, M, N, K, act, st, lda);
+  return launch_gemm_fwd_sk(ctx, A, W, bias, C, M, N, K, act, st, lda, ctx->gemm_sk_slices);
+}
 // ---- backward tails
 // The row-norm backward kernels leave per-workgroup partials: [grid][D] of d scale (RMSNorm: g_bias == NULL) or [grid][2 D] of
 // [d scale | d bias] (LayerNorm).  Their column sums, in workgroup order, are the gradients.

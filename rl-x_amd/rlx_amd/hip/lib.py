@@ -748,6 +748,9 @@ class Ctx:
         _check(self.lib.rlx_dbg_set_stamps(self.h, c_void_p(stamps.data_ptr()) if stamps is not None else None), "rlx_dbg_set_stamps")
 
     def dbg_gemm(self, mode, A, B, C, aux, M, N, K, act):
+        """rlx_dbg_gemm_f32: one GEMM kernel on caller buffers.  Modes 0 / 1 / 2: forward, input gradient, weight gradient on the
+        exact-fp32 engine; 3 / 4 / 5: their split-operand forms; 6: mode 0's product C = act(A @ B + aux) on the split-K kernel
+        for few rows (gemm_sk.hip; 1 <= M <= 1024, N and K multiples of 4, K slices from the option "gemm_sk_slices")."""
         f = self.torch.float32
         _check(self.lib.rlx_dbg_gemm_f32(self.h, mode, _ptr(A, f), _ptr(B, f), _ptr(C, f), _ptr(aux, f, True), M, N, K,
                                          act, _stream()), "rlx_dbg_gemm_f32")

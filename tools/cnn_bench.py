@@ -7,8 +7,9 @@ as many at the small batches: some 0.3 s and more of device time per window.  Me
 only: one JSON line per run, no pass / fail; the largest difference of `out` and of the gradients between the library and torch is
 printed so that a wrong result cannot post a time.
 
-    python tools/cnn_bench.py [--warmup 5] [--iters 100] [--runs 2] [--rows 0] [--eager 1]
-                              (--rows M --eager 0: one batch, library kernels only -- for a kernel trace)
+    python tools/cnn_bench.py [--warmup 5] [--iters 100] [--runs 2] [--rows 0] [--eager 1] [--small-m 0]
+                              (--rows M --eager 0: one batch, library kernels only -- for a kernel trace;
+                               --small-m 1: the option gemm_small_m, the hidden Dense on the split-K kernel of gemm_sk.hip)
 """
 import argparse
 import json
@@ -104,10 +105,11 @@ def one_run(a, ctx, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    for name, default in (("warmup", 5), ("iters", 100), ("runs", 2), ("rows", 0), ("eager", 1)):
+    for name, default in (("warmup", 5), ("iters", 100), ("runs", 2), ("rows", 0), ("eager", 1), ("small-m", 0)):
         ap.add_argument("--" + name, type=int, default=default)
     a = ap.parse_args()
     dev, ctx = torch.device("cuda:0"), Ctx(0)
+    ctx.set_option("gemm_small_m", a.small_m)
     for _ in range(a.runs):
         print(json.dumps(one_run(a, ctx, dev)), flush=True)
 

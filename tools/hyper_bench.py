@@ -5,7 +5,9 @@ same tensors.  Measurement only: prints one JSON line, no pass / fail; the large
 parameters between the two is printed so that a wrong result cannot post a time.
 
     python tools/hyper_bench.py [--in_dim 23] [--hidden 512] [--blocks 2] [--expansion 4] [--warmup 5] [--iters 50]
-                                [--rows 0] [--eager 1]       (--rows M --eager 0: one shape, library kernels only -- for a kernel trace)
+                                [--rows 0] [--eager 1] [--small-m 0]
+        (--rows M --eager 0: one shape, library kernels only -- for a kernel trace; --small-m 1: the option gemm_small_m, the blocks'
+         products on the split-K kernel of gemm_sk.hip where its rule takes them)
 """
 import argparse
 import json
@@ -25,10 +27,11 @@ def l2n(v):
 def main():
     ap = argparse.ArgumentParser()
     for name, default in (("in_dim", 23), ("hidden", 512), ("blocks", 2), ("expansion", 4), ("warmup", 5), ("iters", 50), ("rows", 0),
-                          ("eager", 1)):
+                          ("eager", 1), ("small-m", 0)):
         ap.add_argument("--" + name, type=int, default=default)
     a = ap.parse_args()
     dev, ctx = torch.device("cuda:0"), Ctx(0)
+    ctx.set_option("gemm_small_m", a.small_m)
     g = torch.Generator(device="cpu").manual_seed(0)
     I, H, X, nb = a.in_dim, a.hidden, a.hidden * a.expansion, a.blocks
     desc = hyper_desc(I, H, nb, a.expansion)
